@@ -5,7 +5,15 @@ H = I) on MI355X.  One "step" = one batched pass of the hot path (caldera() of
 alg.py:24-112) over B matrices resident in HBM.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload cfg2|cfg3|cfg5|model|main]
-                  [--no-cpu-baseline] [--no-parity] [--no-api-path]
+                  [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-parity] [--no-api-path]]
+
+A plain run sets up, warms up, times the K steps and prints the result line (throughput, ms_per_step
+and the rooflines of the kernels probed with HIP events inside the timed region).  --full adds what
+takes work of its own after the timed steps: parity of the last timed step against the reference's
+golden runs, the CPU baseline, the drop-in API path and the one-part (solo) roofline step, each of
+which --no-parity / --no-cpu-baseline / --no-api-path switch off again.  --dump-outputs DIR writes
+what the last timed step returned (Q, L, R, scales, error histories) as DIR/<name>.npy: a fixed,
+seeded sample of the entries of the large tensors (dump_outputs), whole small ones.
 
 Multi-GPU: one process per GPU.  `python bench.py --gpus N` (N > 1, WORLD_SIZE unset) starts
 `python -m torch.distributed.run --nproc-per-node N bench.py <same args>` as a child process
@@ -18,13 +26,14 @@ packed results (2-bit codes, L, R, scales) are gathered to rank 0 over RCCL -- t
 collective of the path; the timed region is bracketed by barrier + synchronize and the max
 over ranks is reported.
 
-Prints ONE JSON line (rank 0) with value = matrices/s over all ranks, the roofline of the
-dominant kernel (timed with HIP events on its stream inside the timed region), parity of the
-LAST TIMED STEP's own results (matrices 0-3 of rank 0's batch, seeds 0-3, against the
-reference's golden sketches; matrix 0 also against the CPU baseline's output), the CPU
-baseline (the reference's torch-CPU op sequence, oracle/caldera_torch_cpu.py, on this host),
-and the drop-in API path (caldera_batch with the reference's output placement) timed on one
-extra step of the same batch.
+Prints ONE JSON line (rank 0) with value = matrices/s over all ranks and the roofline of the
+dominant kernel (timed with HIP events on its stream inside the timed region).  Only with --full
+does the line also hold: parity of the LAST TIMED STEP's own results (matrices 0-3 of rank 0's
+batch, seeds 0-3, against the reference's golden sketches; matrix 0 also against the CPU
+baseline's output), the CPU baseline (the reference's torch-CPU op sequence,
+oracle/caldera_torch_cpu.py, on this host), the drop-in API path (caldera_batch with the
+reference's output placement) timed on one extra step of the same batch, and roofline_solo (the
+dominant kernel in one untimed one-part step).
 
 Workloads (BASELINE.json configs): cfg2 (default, the headline metric) 4096x4096, r 128, Q2,
 L/R 16, iters 5, H = I; cfg3 4096x11008, diag H (the golden fixture's resampled
@@ -121,6 +130,56 @@ def synth_batch(wl, B, seed0, dev, host=PINNED):
 def _sketch(Q, L, R, n):
     om = torch.from_numpy(np.random.default_rng(1234).standard_normal((n, 16))).to(Q.device)
     return (Q.double() @ om + L.double() @ (R.double() @ om)).cpu().numpy()
+
+
+DUMP_BUDGET = 48 << 20  # bytes of tensor entries per dump (the scalars add a few KB: under 64 MB in all)
+DUMP_SEED = 274
+
+
+def dump_outputs(path, tensors, scalars):
+    """--dump-outputs: what the last timed step returned, as path/<name>.npy (float32; float64 stays).
+    tensors: name -> one tensor per matrix of the step.  The names share DUMP_BUDGET equally; a
+    matrix's tensor that fits its share is written whole, of a larger one the entries at fixed,
+    distinct flat positions (the head of a permutation seeded with DUMP_SEED + size, sorted), so
+    two runs with the same arguments write the same positions.  Equal lengths stack to (matrices,
+    entries), or to the tensors' own shape when whole; ragged ones are concatenated.
+    scalars: name -> per-matrix numbers or equal-length lists (float64)."""
+    os.makedirs(path, exist_ok=True)
+    picks = {}
+
+    def pick(numel, cap, dev):
+        if (numel, cap, dev) not in picks:
+            g = torch.Generator().manual_seed(DUMP_SEED + numel)
+            picks[numel, cap, dev] = torch.randperm(numel, generator=g)[:cap].sort().values.to(dev)
+        return picks[numel, cap, dev]
+
+    for name, ts in tensors.items():
+        cap = max(1, DUMP_BUDGET // len(tensors) // (8 * len(ts)))
+        whole = all(t.numel() <= cap for t in ts)
+        rows = []
+        for t in ts:
+            t = t.detach()
+            flat = t if whole else t.reshape(-1)
+            if flat.numel() > cap:
+                flat = flat[pick(flat.numel(), cap, flat.device)]
+            rows.append(flat.to(torch.float64 if flat.dtype == torch.float64 else torch.float32).cpu())
+        same = all(r.shape == rows[0].shape for r in rows)
+        arr = torch.stack(rows) if same else torch.cat([r.reshape(-1) for r in rows])
+        np.save(os.path.join(path, f"{name}.npy"), arr.numpy())
+    for name, vs in scalars.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.asarray(vs, dtype=np.float64))
+
+
+def _scalar(x):
+    return float(x.reshape(-1)[0]) if torch.is_tensor(x) else float(x)
+
+
+def dump_results(path, out):
+    """dump_outputs of gathered sharding.MatrixResult records (packed codes, L, R, scales, errors)."""
+    errs = {f"errors_{k}": [r.errors[k] for r in out] for k in out[0].errors}
+    dump_outputs(path, {"codes": [r.codes for r in out], "L": [r.L for r in out], "R": [r.R for r in out]},
+                 {"Q_scale": [_scalar(r.Q_scale) for r in out], "global_scale": [_scalar(r.global_scale) for r in out],
+                  **errs})
 
 
 def parity_of_timed_step(name, decs, wl):
@@ -501,6 +560,8 @@ def run_model(args):
         el = float(t.item())
     if rank == 0:
         assert out is not None and [r.name for r in out] == [it[0] for it in items], "gather incomplete"
+        if args.dump_outputs:
+            dump_results(args.dump_outputs, out)
         result = {
             "metric": "weight matrices/sec (Llama-2-7B linear weights, rank-128, Q=2-bit, whole model)",
             "value": len(items) * args.steps / el, "unit": "matrices/s", "n_gpus": world, "steps": args.steps,
@@ -551,7 +612,7 @@ def run_main(args):
     lplr_iters 5, sigma_reg 1e-8, scale_W=False), on synthetic fp16 weights (randn * 0.02, seed =
     100 + layer-major index).  One step = every layer decomposed through the drop-in API as the
     layer-replacement caller runs it (model.py: api.caldera_groups -- same-shape layers batched with
-    per-matrix Hessians, the three shape batches interleaved on HIP streams).  Beside it, the
+    per-matrix Hessians, the three shape batches interleaved on HIP streams).  Beside it (--full), the
     reference's calling pattern: one drop-in caldera() per layer (B = 1, main.py:189-196), timed
     over the same 35 layers."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -596,25 +657,41 @@ def run_main(args):
         out = step()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    loop()  # warm-up of the B = 1 path
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    ref = loop()
-    torch.cuda.synchronize()
-    el1 = time.perf_counter() - t1
-    # the batched results against the per-layer calls on the same matrices (another batch size:
-    # split-K and lockstep scheduling differ, so agreement is to the solver tolerance, not bits)
+    n_mat = len(jobs)
     flat = [d for g in out for d in g]
     order = [j[0] for g in groups for j in g]
-    by_name = dict(zip(order, flat))
-    rel, flips = [], 0
-    for (name, W, h), d1 in zip(jobs, ref):
-        d = by_name[name]
-        n = W.shape[1]
-        a, b = _sketch(d.Q.to(dev), d.L.to(dev), d.R.to(dev), n), _sketch(d1.Q.to(dev), d1.L.to(dev), d1.R.to(dev), n)
-        rel.append(float(np.linalg.norm(a - b) / np.linalg.norm(b)))
-        flips += int((d.Q_idxs.cpu() != d1.Q_idxs.cpu()).sum())
-    n_mat = len(jobs)
+    if args.dump_outputs:
+        by = dict(zip(order, flat))
+        ds = [by[j[0]] for j in jobs]
+        dump_outputs(args.dump_outputs, {k: [getattr(d, k) for d in ds] for k in ("Q", "L", "R")},
+                     {"Q_scale": [_scalar(d.Q_scale) for d in ds],
+                      "global_scale": [_scalar(d.global_scale) for d in ds],
+                      **{f"errors_{k}": [d.errors[k] for d in ds] for k in ds[0].errors}})
+    extra = {}
+    if args.full:
+        loop()  # warm-up of the B = 1 path
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        ref = loop()
+        torch.cuda.synchronize()
+        el1 = time.perf_counter() - t1
+        # the batched results against the per-layer calls on the same matrices (another batch size:
+        # split-K and lockstep scheduling differ, so agreement is to the solver tolerance, not bits)
+        by_name = dict(zip(order, flat))
+        rel, flips = [], 0
+        for (name, W, h), d1 in zip(jobs, ref):
+            d = by_name[name]
+            n = W.shape[1]
+            a, b = _sketch(d.Q.to(dev), d.L.to(dev), d.R.to(dev), n), _sketch(d1.Q.to(dev), d1.L.to(dev), d1.R.to(dev), n)
+            rel.append(float(np.linalg.norm(a - b) / np.linalg.norm(b)))
+            flips += int((d.Q_idxs.cpu() != d1.Q_idxs.cpu()).sum())
+        extra = {
+            "b1_loop": {"matrices_per_s": n_mat / el1, "ms_per_layer": 1000.0 * el1 / n_mat,
+                        "note": "the reference's calling pattern: one drop-in caldera() per layer (B = 1, "
+                                "main.py:189-196), same 35 layers, resident in HBM"},
+            "speedup_vs_b1_loop": (n_mat * args.steps / el) / (n_mat / el1),
+            "batched_vs_b1": {"max_rel_frob_QLR": max(rel), "median_rel_frob_QLR": float(np.median(rel)),
+                              "final_code_flips_total": flips}}
     print(json.dumps({
         "metric": "weight matrices/sec (main.py layer set: 35 projections of layers 17-23, rank-200, Q=2-bit, "
                   "per-layer real diag Hessians)",
@@ -631,12 +708,7 @@ def run_main(args):
                    "shape_batches": {f"{k[0]}x{k[1]}": len(v) for k, v in shapes.items()},
                    "parallelism": "dp1 (same-shape layers batched with per-matrix Hessians; shape batches "
                                   "interleaved on HIP streams)"},
-        "b1_loop": {"matrices_per_s": n_mat / el1, "ms_per_layer": 1000.0 * el1 / n_mat,
-                    "note": "the reference's calling pattern: one drop-in caldera() per layer (B = 1, "
-                            "main.py:189-196), same 35 layers, resident in HBM"},
-        "speedup_vs_b1_loop": (n_mat * args.steps / el) / (n_mat / el1),
-        "batched_vs_b1": {"max_rel_frob_QLR": max(rel), "median_rel_frob_QLR": float(np.median(rel)),
-                          "final_code_flips_total": flips},
+        **extra,
     }), flush=True)
 
 
@@ -700,6 +772,8 @@ def run_dry(args):
         el = float(t.item())
     if rank == 0:
         assert out is not None and len(out) == B * world, "gather incomplete"
+        if args.dump_outputs:
+            dump_results(args.dump_outputs, out)
         print(json.dumps({
             "metric": "dry run (stub decomposer, gloo): N-rank launch + gather plumbing, not a measurement",
             "value": B * world * args.steps / el, "unit": "matrices/s", "n_gpus": world, "steps": args.steps,
@@ -720,9 +794,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=None, help="matrices per GPU (default: per workload)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS) + ["model", "main"], default="cfg2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-api-path", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: parity against the reference's golden runs, the CPU "
+                         "baseline, the drop-in API path and the one-part roofline step (a plain run skips them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (a fixed, seeded sample of "
+                         "the large tensors' entries; rank 0's results)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the parity checks")
+    ap.add_argument("--no-api-path", action="store_true", help="with --full: skip the drop-in API path")
     ap.add_argument("--model-parts", type=int, default=1,
                     help="model workload: each same-shape batch as this many interleaved parts")
     ap.add_argument("--model-group", type=int, default=None,
@@ -754,6 +834,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if not args.full:  # a plain run: nothing beyond the timed steps
+        args.no_cpu_baseline = args.no_parity = args.no_api_path = True
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # the driver's form `python bench.py --gpus N`: one process per GPU, started here
         return launch_ranks(args.gpus, sys.argv[1:])
@@ -899,6 +981,11 @@ def main():
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: [d[k] for d in decs] for k in ("Q", "L", "R")},
+                     {"Q_scale": [_scalar(d["Q_scale"]) for d in decs],
+                      "global_scale": [_scalar(d["global_scale"]) for d in decs],
+                      **{f"errors_{k}": [d["errors"][k] for d in decs] for k in decs[0]["errors"]}})
     total = args.steps * B * world
     value = total / el
     metric = ("weight matrices/sec (4096x4096, rank-128, Q=2-bit) + Frob err vs ref" if args.workload == "cfg2"
@@ -982,8 +1069,8 @@ def main():
             result["roofline"]["concurrency"] = (
                 f"{parts} interleaved batch parts on separate HIP streams: each launch shares the chip with the "
                 "other part's kernels (the one-CU-per-matrix eigensolves and whitening run beside it), so its "
-                "duration and this frac are per launch under that sharing; roofline_solo times the same kernel "
-                "with one part")
+                "duration and this frac are per launch under that sharing; roofline_solo (with --full) times the "
+                "same kernel with one part")
     # the quantise kernel (fused Q update, every pass of a call; SURVEY.md 8(d) bytes_Q per call):
     # "w" = first Q step (quantise W itself, pure HBM), "lr" = Q steps recomputing W - L R on
     # split-fp16 MFMAs (3 fp16 products per fp32-equivalent flop; one recompute on the 2-bit list path)
@@ -1101,7 +1188,7 @@ def main():
                               "note": "one step through api.caldera_batch (drop-in layout, W to host)"}
         if rank == 0 and world == 1:
             result["api_single"] = single_call_latency(qp, Wb[0], h, dev)
-    if parts > 1 and world == 1 and probe["count"]:
+    if args.full and parts > 1 and world == 1 and probe["count"]:
         # the dominant kernel alone: one untimed step of the whole batch as one part (launches of
         # B matrices, nothing beside them), HIP events as in the timed region.  The parts' cached
         # scratch (scratch.py: per stream and shape) goes back to the device first: the one-part

@@ -32,7 +32,7 @@ def main():
         init(self, *a, **k)
 
     solver.RankRSolver.__init__ = patched
-    sys.argv = ["bench.py", "--no-cpu-baseline", "--no-api-path"]
+    sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-api-path"]
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         bench.main()

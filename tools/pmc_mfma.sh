@@ -6,7 +6,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 OUT=${1:-gpurun_out/pmc_mfma}; shift
-ARGS=${*:---steps 1 --warmup 0 --batch 64 --no-cpu-baseline --no-api-path --no-parity}
+ARGS=${*:---steps 1 --warmup 0 --batch 64 --full --no-cpu-baseline --no-api-path --no-parity}
 mkdir -p $OUT
 timeout -s KILL 60 rocprofv3 -L > $OUT/counters.txt 2>&1 || true
 pick() {  # the counters of "$@" that rocprofv3 -L lists

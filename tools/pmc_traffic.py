@@ -43,6 +43,7 @@ out = {
                   "of the same grid (no recurrence operands); the single-product launches are reported apart",
     "single_product_launches": single,
     "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) --kernel-include-regex gemm_x3 "
-              f"-- python3 bench.py --batch {B} --steps 1 --warmup 0 --no-parity",
+              f"-- python3 bench.py --batch {B} --steps 1 --warmup 0 --full --no-parity --no-cpu-baseline "
+              f"--no-api-path (tools/profile_round.sh)",
 }
 print(json.dumps(out, indent=1))

@@ -40,4 +40,4 @@ print(json.dumps({"config": {"batch": B, "m": m, "n": n, "bits": bits}, "kernels
                   "correction": "hbm = 2*FETCH_SIZE + WRITE_SIZE (KB*1024), gfx950 (MI355X_MICROARCH.md HBM)",
                   "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) "
                             f"--kernel-include-regex 'quant_w_stream|q_update_p|q_update_v' -- python3 bench.py --batch {B} "
-                            f"--steps 1 --warmup 0 --no-parity --no-cpu-baseline --no-api-path"}, indent=1))
+                            f"--steps 1 --warmup 0 --full --no-parity --no-cpu-baseline --no-api-path"}, indent=1))

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${TAG:-r04_tolsweep}; mkdir -p $O
 for sched in ${SCHEDS:-none 3e-6 1e-6 1e-6,3e-6}; do
   arg=""; [ "$sched" = none ] || arg="--solver-tol-steps $sched"
-  timeout -k 10 300 python3 -u bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-api-path $arg > $O/b_$sched.log 2>&1 || exit $?
+  timeout -k 10 300 python3 -u bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-api-path $arg > $O/b_$sched.log 2>&1 || exit $?
   python3 - "$sched" $O/b_$sched.log <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

@@ -32,7 +32,7 @@ def main():
         buf = io.StringIO()
         if wl == "main":
             with contextlib.redirect_stdout(buf):
-                bench.run_main(argparse.Namespace(steps=2, warmup=1))
+                bench.run_main(argparse.Namespace(steps=2, warmup=1, full=True, dump_outputs=None))
             d = json.loads(buf.getvalue().strip().splitlines()[-1])
             print(json.dumps({"spec": spec, "matrices_per_s": round(d["value"], 1),
                               "b1_ms_per_layer": round(d["b1_loop"]["ms_per_layer"], 1),
