@@ -671,7 +671,8 @@ def sym_split_f16(G: torch.Tensor, x_scale: float, *, hi=None, lo=None, scale=No
 def transpose_split(X: torch.Tensor, *, out=None, hi=None, lo=None, scale: float | torch.Tensor = 1.0,
                     blocked: bool = False):
     """X (B, r, c) fp32 contiguous -> X^T (B, c, r) fp32 (out) and/or its fp16 split (hi, lo)
-    scaled by `scale` (a float, or a (B,) fp32 tensor of per-matrix scales)."""
+    scaled by `scale` (a float, or a (B,) fp32 tensor of per-matrix scales); hi without lo: the
+    hi half alone (the operand of a single product)."""
     _require_hip(X)
     assert X.dtype == torch.float32 and X.is_contiguous() and X.dim() == 3
     B, r, c = X.shape
@@ -784,7 +785,8 @@ def gemm_x3(Ah, Al, Bh, Bl, inv_scale, C, *, P=None, D=None, alpha_v=None, beta_
     term of column j scaled by colw[j] (before beta P + gamma D; (B, N): per matrix).  absmax_out (B,) int32/uint32/fp32
     (plain products): zeroed here, receives the bits of max|C[b]| (pow2_from_absmax turns them
     into the next split's scale without a pass over C).  Ct (B, N, M) fp32: C^T as well (not
-    with tri / sym_out; C required)."""
+    with tri / sym_out); C may then be None (only C^T is written).  out_l may be None with
+    out_h given (hi halves only, for a single product that follows; not with sym_bound)."""
     assert Bl is not None or b_exact or single
     _require_hip(Ah, Al, Bh, Bl, C)
     Bt, MA, Kd = Ah.shape
@@ -811,7 +813,7 @@ def gemm_x3(Ah, Al, Bh, Bl, inv_scale, C, *, P=None, D=None, alpha_v=None, beta_
     g.beta_v = beta_v.data_ptr() if beta_v is not None else None
     g.gamma_v = gamma_v.data_ptr() if gamma_v is not None else None
     if out_h is not None and sym_bound is None:
-        g.out_h, g.out_l, g.ldo, g.stride_o = out_h.data_ptr(), out_l.data_ptr(), N, M * N
+        g.out_h, g.out_l, g.ldo, g.stride_o = out_h.data_ptr(), (out_l.data_ptr() if out_l is not None else None), N, M * N
         g.out_scale = out_scale
         g.overflow = overflow.data_ptr()
     g.tri = int(bool(tri))
@@ -830,7 +832,7 @@ def gemm_x3(Ah, Al, Bh, Bl, inv_scale, C, *, P=None, D=None, alpha_v=None, beta_
         g.absmax_out = absmax_out.data_ptr()
     if Ct is not None:
         _require_hip(Ct)
-        assert C is not None and not tri and Ct.dtype == torch.float32 and Ct.is_contiguous() and Ct.shape == (Bt, N, M)
+        assert not tri and Ct.dtype == torch.float32 and Ct.is_contiguous() and Ct.shape == (Bt, N, M)
         g.Ct, g.stride_ct = Ct.data_ptr(), N * M
     # split-K where the batch has fewer output tiles than the chip has CUs (one caldera() call:
     # the filter's 192 x 4096 product is 11 tiles): chunks of >= 8 K steps, ~512 workgroups.
@@ -838,7 +840,7 @@ def gemm_x3(Ah, Al, Bh, Bl, inv_scale, C, *, P=None, D=None, alpha_v=None, beta_
     # decomposed alone (or in a small batch) and the same matrix inside a large batch agree to
     # the products' rounding, not bit for bit; AUTO_SPLIT_K = False pins one pass everywhere
     tiles = -(-N // 384) * -(-M // 192) * Bt
-    splittable = not tri and sym_bound is None and C is not None and N % 4 == 0
+    splittable = not tri and sym_bound is None and (C is not None or Ct is not None) and N % 4 == 0
     if ksplit is None and not auto_split_k():
         ksplit = 1
     if ksplit is None:  # automatic

@@ -606,66 +606,108 @@ __global__ __launch_bounds__(XW_THREADS, 1) void gemm_x3v_kernel(X3K a) {
     // fp16 accesses (host guarantees N % 4 == 0 and 16-byte aligned rows)
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     auto al8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; };
-    const bool vec = (a.N & 3) == 0 && (a.ldc & 3) == 0 && (a.sc & 3) == 0 && al16(a.C) &&
+    // (a null C -- only C^T is wanted -- or a null Ol -- hi halves only -- is not written)
+    const bool vec = (a.N & 3) == 0 && (!a.C || ((a.ldc & 3) == 0 && (a.sc & 3) == 0 && al16(a.C))) &&
                      (!a.P || ((a.ldp & 3) == 0 && (a.sp & 3) == 0 && al16(a.P))) &&
                      (!a.D || ((a.ldd & 3) == 0 && (a.sd & 3) == 0 && al16(a.D))) &&
-                     (!a.Oh || ((a.o_blocked || (a.ldo & 3) == 0) && (a.so & 3) == 0 && al8(a.Oh) && al8(a.Ol)));
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int64_t row = m0 + 96 * wm + 16 * i + l16;
-        if (row >= a.M) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t col = n0 + 64 * wn + 16 * j + 4 * lq;
-            if (col >= a.N) continue;
+                     (!a.Oh || ((a.o_blocked || (a.ldo & 3) == 0) && (a.so & 3) == 0 && al8(a.Oh) && (!a.Ol || al8(a.Ol))));
+    if (vec) {
+        // An item q = 4 i + j is the lane's 4 columns of block (i, j).  fetch: its P and D
+        // values; finish: combine and store.  P may alias C exactly (the recurrence overwrites
+        // prev): an item's values are read before that item is written, and no other item's.
+        // Addresses are a scalar base (the tile's corner, plus the item's offset) and one 32-bit
+        // byte offset per lane and operand (the lane's row and column inside the tile; the host
+        // bounds the leading dimensions), so the 24 items share their address registers.
+        const bool useP = a.P && be_ != 0.f, useD = a.D && ga_ != 0.f;
+        const int mr = (int)min<int64_t>(a.M - m0, XW_BM), nr = (int)min<int64_t>(a.N - n0, XW_BN);  // live rows, columns
+        const uint32_t lr = 96 * wm + l16, lc = 64 * wn + 4 * lq;
+        auto corner = [&](const void* p, int64_t sb_, int64_t ld, int esz) __attribute__((always_inline)) {
+            return p ? reinterpret_cast<const char*>(p) + (b * sb_ + m0 * ld + n0) * esz : nullptr;
+        };
+        const char* Pt = corner(a.P, a.sp, a.ldp, 4);
+        const char* Dt = corner(a.D, a.sd, a.ldd, 4);
+        char* Ct_ = const_cast<char*>(corner(a.C, a.sc, a.ldc, 4));
+        char* Tt = a.Ct ? reinterpret_cast<char*>(a.Ct + b * a.sct + n0 * a.M + m0) : nullptr;
+        const float* cwt = a.colw ? a.colw + b * a.scolw + n0 : nullptr;
+        const uint32_t vP = (lr * (uint32_t)a.ldp + lc) * 4u, vD = (lr * (uint32_t)a.ldd + lc) * 4u,
+                       vC = (lr * (uint32_t)a.ldc + lc) * 4u, vT = (lc * (uint32_t)a.M + lr) * 4u;
+        // split output: blocked, column c of the tile lies in K block n0 / 32 + c / 32 (n0 % 32 == 0)
+        const int64_t oblk = a.M * 32;
+        const int64_t ocorner = b * a.so + (a.o_blocked ? (n0 >> 5) * oblk + m0 * 32 : m0 * a.ldo + n0);
+        const uint32_t vO = (a.o_blocked ? (uint32_t)(2 * wn) * (uint32_t)oblk + lr * 32u + 4u * lq
+                                         : lr * (uint32_t)a.ldo + lc) * 2u;
+        auto inside = [&](int q) __attribute__((always_inline)) {
+            return (int)lr < mr - 16 * (q >> 2) && (int)lc < nr - 16 * (q & 3);
+        };
+        auto fetch = [&](int q, float4& pv, float4& dv) __attribute__((always_inline)) {
+            if (!inside(q)) return;
+            const int i = q >> 2, j = q & 3;
+            if (useP) pv = *reinterpret_cast<const float4*>(Pt + (16 * i * a.ldp + 16 * j) * 4 + vP);
+            if (useD) dv = *reinterpret_cast<const float4*>(Dt + (16 * i * a.ldd + 16 * j) * 4 + vD);
+        };
+        auto finish = [&](int q, const float4& pv, const float4& dv) __attribute__((always_inline)) {
+            if (!inside(q)) return;
+            const int i = q >> 2, j = q & 3;
+            const f32x4v ac = acc[i][j];
             float v[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = al_ * (acc[i][j][r] * sc);
-            if (a.colw) {
-                const float* cw = a.colw + b * a.scolw;
+            for (int r = 0; r < 4; ++r) v[r] = al_ * (ac[r] * sc);
+            if (cwt) {
 #pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (col + r < a.N) v[r] *= cw[col + r];
+                for (int r = 0; r < 4; ++r) v[r] *= cwt[lc + (uint32_t)(16 * j + r)];   // (N % 4 == 0: in range)
             }
-            if (vec) {
-                if (a.P && be_ != 0.f) {
-                    const float4 pv = *reinterpret_cast<const float4*>(a.P + b * a.sp + row * a.ldp + col);
-                    v[0] += be_ * pv.x; v[1] += be_ * pv.y; v[2] += be_ * pv.z; v[3] += be_ * pv.w;
-                }
-                if (a.D && ga_ != 0.f) {
-                    const float4 dv = *reinterpret_cast<const float4*>(a.D + b * a.sd + row * a.ldd + col);
-                    v[0] += ga_ * dv.x; v[1] += ga_ * dv.y; v[2] += ga_ * dv.z; v[3] += ga_ * dv.w;
-                }
-                *reinterpret_cast<float4*>(a.C + b * a.sc + row * a.ldc + col) = make_float4(v[0], v[1], v[2], v[3]);
-                if (a.Ct) {   // C^T: lanes l16 (consecutive rows) make 64-byte runs per column
+            if (useP) { v[0] += be_ * pv.x; v[1] += be_ * pv.y; v[2] += be_ * pv.z; v[3] += be_ * pv.w; }
+            if (useD) { v[0] += ga_ * dv.x; v[1] += ga_ * dv.y; v[2] += ga_ * dv.z; v[3] += ga_ * dv.w; }
+            if (Ct_) *reinterpret_cast<float4*>(Ct_ + (16 * i * a.ldc + 16 * j) * 4 + vC) = make_float4(v[0], v[1], v[2], v[3]);
+            if (Tt) {   // C^T: lanes l16 (consecutive rows) make 64-byte runs per column
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) a.Ct[b * a.sct + (col + r) * a.M + row] = v[r];
-                }
-                if (a.absmax_out)
-                    amx = max(amx, max(max(abs_bits(v[0]), abs_bits(v[1])), max(abs_bits(v[2]), abs_bits(v[3]))));
-                if (a.Oh) {
-                    _Float16 h[4], l[4];
+                for (int r = 0; r < 4; ++r) *reinterpret_cast<float*>(Tt + ((16 * j + r) * a.M + 16 * i) * 4 + vT) = v[r];
+            }
+            if (a.absmax_out)
+                amx = max(amx, max(max(abs_bits(v[0]), abs_bits(v[1])), max(abs_bits(v[2]), abs_bits(v[3]))));
+            if (a.Oh) {
+                _Float16 h[4], l[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float hs = v[r] * a.out_scale;
-                        h[r] = (_Float16)hs;
-                        l[r] = (_Float16)(hs - (float)h[r]);
-                        ovf |= !(fabsf(hs) < 65504.f);
-                    }
-                    const int64_t o = b * a.so + (a.o_blocked ? (col >> 5) * (a.M * 32) + row * 32 + (col & 31)
-                                                              : row * a.ldo + col);
-                    *reinterpret_cast<uint2*>(a.Oh + o) = *reinterpret_cast<const uint2*>(h);
-                    *reinterpret_cast<uint2*>(a.Ol + o) = *reinterpret_cast<const uint2*>(l);
+                for (int r = 0; r < 4; ++r) {
+                    const float hs = v[r] * a.out_scale;
+                    h[r] = (_Float16)hs;
+                    l[r] = (_Float16)(hs - (float)h[r]);
+                    ovf |= !(fabsf(hs) < 65504.f);
                 }
-            } else {
+                const int64_t oi = ocorner + (a.o_blocked ? (j >> 1) * oblk + 16 * i * 32 + 16 * (j & 1)
+                                                          : 16 * i * a.ldo + 16 * j);
+                *reinterpret_cast<uint2*>(reinterpret_cast<char*>(a.Oh + oi) + vO) = *reinterpret_cast<const uint2*>(h);
+                if (a.Ol) *reinterpret_cast<uint2*>(reinterpret_cast<char*>(a.Ol + oi) + vO) = *reinterpret_cast<const uint2*>(l);
+            }
+        };
+        // item by item: measured, keeping the P and D loads of later items in flight across the
+        // stores (rings of 2-4 items) is within noise of this -- the
+        // epilogue already moves its own bytes at the HBM rate
+#pragma unroll
+        for (int q = 0; q < 24; ++q) {
+            float4 pv = make_float4(0.f, 0.f, 0.f, 0.f), dv = pv;
+            fetch(q, pv, dv);
+            finish(q, pv, dv);
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const int64_t row = m0 + 96 * wm + 16 * i + l16;
+            if (row >= a.M) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t col = n0 + 64 * wn + 16 * j + 4 * lq;
+                if (col >= a.N) continue;
+                const float* cw = a.colw ? a.colw + b * a.scolw : nullptr;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int64_t c = col + r;
                     if (c >= a.N) continue;
-                    float w = v[r];
+                    float w = al_ * (acc[i][j][r] * sc);
+                    if (cw) w *= cw[c];
                     if (a.P && be_ != 0.f) w += be_ * a.P[b * a.sp + row * a.ldp + c];
                     if (a.D && ga_ != 0.f) w += ga_ * a.D[b * a.sd + row * a.ldd + c];
-                    a.C[b * a.sc + row * a.ldc + c] = w;
+                    if (a.C) a.C[b * a.sc + row * a.ldc + c] = w;
                     if (a.Ct) a.Ct[b * a.sct + c * a.M + row] = w;
                     amx = max(amx, abs_bits(w));
                     if (a.Oh) {
@@ -674,7 +716,7 @@ __global__ __launch_bounds__(XW_THREADS, 1) void gemm_x3v_kernel(X3K a) {
                         const int64_t o = b * a.so + (a.o_blocked ? (c >> 5) * (a.M * 32) + row * 32 + (c & 31)
                                                                   : row * a.ldo + c);
                         a.Oh[o] = h;
-                        a.Ol[o] = (_Float16)(hs - (float)h);
+                        if (a.Ol) a.Ol[o] = (_Float16)(hs - (float)h);
                         ovf |= !(fabsf(hs) < 65504.f);
                     }
                 }
@@ -833,7 +875,7 @@ __global__ __launch_bounds__(256) void x3_splitk_epi_kernel(X3K a) {
         if (a.colw) w *= a.colw[b * a.scolw + col + r];
         if (a.P && be_ != 0.f) w += be_ * a.P[b * a.sp + row * a.ldp + col + r];
         if (a.D && ga_ != 0.f) w += ga_ * a.D[b * a.sd + row * a.ldd + col + r];
-        a.C[b * a.sc + row * a.ldc + col + r] = w;
+        if (a.C) a.C[b * a.sc + row * a.ldc + col + r] = w;
         if (a.Ct) a.Ct[b * a.sct + (col + r) * a.M + row] = w;
         amx = max(amx, abs_bits(w));
         if (a.Oh) {
@@ -842,7 +884,7 @@ __global__ __launch_bounds__(256) void x3_splitk_epi_kernel(X3K a) {
             const int64_t c = col + r;
             const int64_t o = b * a.so + (a.o_blocked ? (c >> 5) * (a.M * 32) + row * 32 + (c & 31) : row * a.ldo + c);
             a.Oh[o] = h;
-            a.Ol[o] = (_Float16)(hs - (float)h);
+            if (a.Ol) a.Ol[o] = (_Float16)(hs - (float)h);
             ovf |= !(fabsf(hs) < 65504.f);
         }
     }
@@ -1688,7 +1730,7 @@ __global__ __launch_bounds__(256) void transpose_split_kernel(const float* __res
                 }
                 const int64_t o = blocked ? ob + (ocol >> 5) * cols * 32 + orow * 32 + (ocol & 31) : ob + orow * rows + ocol;
                 *reinterpret_cast<uint4*>(hi + o) = *reinterpret_cast<const uint4*>(h);
-                *reinterpret_cast<uint4*>(lo + o) = *reinterpret_cast<const uint4*>(l);
+                if (lo) *reinterpret_cast<uint4*>(lo + o) = *reinterpret_cast<const uint4*>(l);
             }
         }
         return;
@@ -1709,7 +1751,7 @@ __global__ __launch_bounds__(256) void transpose_split_kernel(const float* __res
                 // Y is cols x rows: K-blocked halves put (orow, ocol) at (ocol/32)*cols*32 + orow*32 + ocol%32
                 const int64_t o = blocked ? ob + (ocol >> 5) * cols * 32 + orow * 32 + (ocol & 31) : ob + orow * rows + ocol;
                 hi[o] = h;
-                lo[o] = (_Float16)(xs - (float)h);
+                if (lo) lo[o] = (_Float16)(xs - (float)h);
             }
         }
     }
@@ -1787,12 +1829,12 @@ int cq_split_f16(const float* X, int64_t n_per, int64_t batch, const float* scal
 int cq_transpose_split(const float* X, int64_t rows, int64_t cols, int64_t batch, float* Y, uint16_t* hi,
                        uint16_t* lo, float scale, const float* scale_v, int blocked, void* stream) {
     CQ_REQUIRE(!blocked || rows % 32 == 0, "cq_transpose_split: blocked halves need rows % 32 == 0");
-    CQ_REQUIRE(X && (Y || (hi && lo)), "cq_transpose_split: null pointer");
-    CQ_REQUIRE(!hi == !lo, "cq_transpose_split: hi and lo go together");
+    CQ_REQUIRE(X && (Y || hi), "cq_transpose_split: null pointer");
+    CQ_REQUIRE(hi || !lo, "cq_transpose_split: lo needs hi (hi alone: the operand of a single product)");
     CQ_REQUIRE(rows > 0 && cols > 0 && batch > 0 && batch < 65536, "cq_transpose_split: bad shape");
     dim3 grid((unsigned)ceil_div(cols, 64), (unsigned)ceil_div(rows, 64), (unsigned)batch);
     auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool vec = rows % 8 == 0 && cols % 4 == 0 && al16(X) && (!Y || al16(Y)) && (!hi || (al16(hi) && al16(lo)));
+    const bool vec = rows % 8 == 0 && cols % 4 == 0 && al16(X) && (!Y || al16(Y)) && (!hi || al16(hi)) && (!lo || al16(lo));
     if (vec)
         transpose_split_kernel<true><<<grid, 256, 0, as_stream(stream)>>>(
             X, rows, cols, Y, reinterpret_cast<_Float16*>(hi), reinterpret_cast<_Float16*>(lo), scale, scale_v, blocked);
@@ -2045,7 +2087,7 @@ int cq_residual_split(int dtype, const void* Ws, const uint8_t* packed, const fl
 
 int cq_gemm_x3(const cq_x3_args* g, void* stream) {
     CQ_REQUIRE(g, "cq_gemm_x3: null args");
-    CQ_REQUIRE(g->Ah && g->Al && g->Bh && (g->Bl || g->single || g->b_exact) && (g->C || g->sym_out) && g->inv_scale,
+    CQ_REQUIRE(g->Ah && g->Al && g->Bh && (g->Bl || g->single || g->b_exact) && (g->C || g->sym_out || g->Ct) && g->inv_scale,
                "cq_gemm_x3: null operand");
     CQ_REQUIRE(!g->sym_out || (g->tri && g->out_h && g->out_l && g->out_bound && g->scale_out && g->inv_out &&
                                g->out_scale > 0.f && g->N % 32 == 0),
@@ -2055,9 +2097,12 @@ int cq_gemm_x3(const cq_x3_args* g, void* stream) {
     CQ_REQUIRE(g->lda % 8 == 0 && g->ldb % 8 == 0 && g->stride_a % 8 == 0 && g->stride_b % 8 == 0,
                "cq_gemm_x3: operand rows must be 16-byte aligned");
     CQ_REQUIRE((g->a_blocked ? g->lda >= g->M : g->lda >= g->K) && (g->b_blocked ? g->ldb >= g->N : g->ldb >= g->K) &&
-                   g->ldc >= g->N,
+                   (!g->C || g->ldc >= g->N),
                "cq_gemm_x3: leading dimension too small");
-    CQ_REQUIRE(!g->out_h == !g->out_l, "cq_gemm_x3: out_h and out_l go together");
+    CQ_REQUIRE(g->out_h || !g->out_l, "cq_gemm_x3: out_l needs out_h (out_h alone: hi halves only)");
+    // (the vector epilogue addresses a tile with 32-bit byte offsets per lane: 192 rows of ld floats)
+    CQ_REQUIRE(g->M <= (1 << 21) && g->ldc <= (1 << 22) && g->ldp <= (1 << 22) && g->ldd <= (1 << 22) && g->ldo <= (1 << 22),
+               "cq_gemm_x3: M above 2^21 or a leading dimension above 2^22");
     CQ_REQUIRE(!g->out_h || g->sym_out || (g->overflow && g->out_scale > 0.f),
                "cq_gemm_x3: split output needs overflow flags");
     CQ_REQUIRE(!g->beta_v || g->P, "cq_gemm_x3: beta_v needs P");
@@ -2084,7 +2129,7 @@ int cq_gemm_x3(const cq_x3_args* g, void* stream) {
     a.absmax_out = g->absmax_out;
     a.Ct = g->Ct;
     a.sct = g->stride_ct;
-    CQ_REQUIRE(!g->Ct || (!g->sym_out && !g->tri && g->C), "cq_gemm_x3: Ct needs a non-symmetric product with C");
+    CQ_REQUIRE(!g->Ct || (!g->sym_out && !g->tri), "cq_gemm_x3: Ct needs a non-symmetric product");
     CQ_REQUIRE(!g->absmax_out || (!g->sym_out && !g->tri), "cq_gemm_x3: absmax_out needs a plain product");
     CQ_REQUIRE(!g->colw || (!g->sym_out && !g->tri), "cq_gemm_x3: colw needs a plain product");
     // single + sym_out: the Gram of an exactly-fp16 operand (lo = 0; A = W W^T of the sparse-code
@@ -2114,8 +2159,8 @@ int cq_gemm_x3(const cq_x3_args* g, void* stream) {
     a.ksplit = g->ksplit > 1 ? g->ksplit : 1;
     a.part = g->split_ws;
     if (a.ksplit > 1) {
-        CQ_REQUIRE(!a.tri && !a.sym_out && a.part && a.C && g->N % 4 == 0 && a.ksplit <= g->K / XW_BK,
-                   "cq_gemm_x3: split-K needs a plain product with C, N % 4 == 0, split_ws, ksplit <= K / 32");
+        CQ_REQUIRE(!a.tri && !a.sym_out && a.part && (a.C || a.Ct) && g->N % 4 == 0 && a.ksplit <= g->K / XW_BK,
+                   "cq_gemm_x3: split-K needs a plain product with C or Ct, N % 4 == 0, split_ws, ksplit <= K / 32");
         total *= a.ksplit;
     }
     CQ_REQUIRE(total < (1ll << 31), "cq_gemm_x3: grid too large");

@@ -95,11 +95,13 @@ class _EventProbe:
         ms = [a.elapsed_time(b) for a, b in pairs]
         groups = {}
         for t, (fl, nb, kn) in zip(ms, self.meta):
-            g = groups.setdefault(kn, {"count": 0, "ms": 0.0, "flops_per_launch": fl, "bytes_per_launch": nb})
+            g = groups.setdefault(kn, {"count": 0, "ms": 0.0, "flops_per_launch": fl, "bytes_per_launch": 0.0})
             g["count"] += 1
             g["ms"] += t
+            g["bytes_per_launch"] += nb   # (summed here, the mean below: a filter's last step moves fewer)
         for g in groups.values():
             g["avg_ms"] = g["ms"] / g["count"]
+            g["bytes_per_launch"] /= g["count"]
         top = max(groups, key=lambda k: groups[k]["ms"])
         g = groups[top]
         out = {"count": g["count"], "avg_ms": g["avg_ms"], "flops_per_launch": g["flops_per_launch"],
@@ -436,8 +438,10 @@ class RankRSolver:
             if self._halves_of is not X:   # (else the CholQR product wrote them)
                 K.transpose_split(X, hi=self._xh[0], lo=self._xl[0], scale=X3_SCALE, blocked=True)
             self._halves_of = None
-            K.gemm_x3(self._xh[0], self._xl[0], self._Gh, self._Gl, self._ginv, self._xt[0], b_blocked=self._g_blocked,
-                      a_blocked=True, single=single and self._x3f, Ct=Z if TRANSPOSED_OUT else None)
+            # (TRANSPOSED_OUT: only Z = C^T is read afterwards, so C is not written)
+            K.gemm_x3(self._xh[0], self._xl[0], self._Gh, self._Gl, self._ginv, None if TRANSPOSED_OUT else self._xt[0],
+                      b_blocked=self._g_blocked, a_blocked=True, single=single and self._x3f,
+                      Ct=Z if TRANSPOSED_OUT else None)
             if not TRANSPOSED_OUT:
                 K.transpose_split(self._xt[0], out=Z)
         else:
@@ -599,39 +603,54 @@ class RankRSolver:
         xt, xh, xl = self._xt, self._xh, self._xl
         self._halves_of = None
         # iterates' halves are K-blocked (each 32-deep step of a tile is one contiguous run)
-        K.transpose_split(X, out=xt[0], hi=xh[0], lo=xl[0], scale=X3_SCALE, blocked=True)
+        # (a single-product filter reads no lo half, the entry's or a step's: none is written;
+        # every later reader of the iterate halves -- _rr, _cholqr(halves), split_block_t --
+        # writes both halves itself first)
+        K.transpose_split(X, out=xt[0], hi=xh[0], lo=None if single else xl[0], scale=X3_SCALE, blocked=True)
         fl = 2.0 * self.k * self.k * self.p * self.B
-        # bytes a recurrence step moves: G halves (4 B/elem) + X^T halves + prev, cur in,
-        # new out (fp32) + new halves out
-        nb = float(self.B) * (4.0 * self.k * self.k + 20.0 * self.p * self.k)
-        kn = "gemm_x3v_kernel<0> (split-fp16 G X, Chebyshev filter)"
-        # the probe (bench.py's roofline) times both kinds of step, each with its own bytes: a
-        # single-product step moves G's hi half and one iterate half per matrix, 2k^2 + 18pk
-        if single:
-            nb = float(self.B) * (2.0 * self.k * self.k + 18.0 * self.p * self.k)
-            kn = "gemm_x3v_kernel<1> (single fp16 product G X, Chebyshev filter)"
+        # bytes a recurrence step moves per matrix: G's halves (4 B/elem) + the iterate's halves
+        # in (4pk) + prev, cur in (8pk) + new out (4pk) + new halves out (4pk): 4k^2 + 20pk.  The
+        # last step writes no halves, and its result once (in X's own k x p layout, Ct, when
+        # TRANSPOSED_OUT: no transpose pass, no C): 4k^2 + 16pk.  The probe (bench.py's roofline) times both kinds
+        # of step, each with its own bytes: a single-product step moves G's hi half and the hi
+        # half of the iterate in and out, 2k^2 + 16pk (the last one 2k^2 + 14pk)
+        pk = float(self.p) * self.k
+        gb = (2.0 if single else 4.0) * self.k * self.k
+        nb_mid = float(self.B) * (gb + (16.0 if single else 20.0) * pk)
+        kn = ("gemm_x3v_kernel<1> (single fp16 product G X, Chebyshev filter)" if single
+              else "gemm_x3v_kernel<0> (split-fp16 G X, Chebyshev filter)")
         probe = EVENT_PROBE.start
-        # the last step also writes its result in X's own k x p layout (Ct): no transpose pass
         out = self._free(X, *keep)
         ct = out if TRANSPOSED_OUT else None
+        nb_last = float(self.B) * (gb + (14.0 if single else 16.0) * pk)
+
+        def outputs(last, c):
+            """Where a step's result goes: every step but the last writes the next iterate (fp32
+            and its hi half; the lo half too unless the next product is single), the last one
+            the filter's result."""
+            if not last:
+                return dict(C=xt[c], out_h=xh[c], out_l=None if single else xl[c], Ct=None)
+            return dict(C=xt[c] if ct is None else None, out_h=None, out_l=None, Ct=ct)
+
         last = deg == 1
-        ev = probe(fl, nb, kn)
-        K.gemm_x3(xh[0], xl[0], self._Gh, self._Gl, self._ginv, xt[1], D=xt[0], alpha_v=coef[0, 0],
-                  gamma_v=coef[0, 2], out_h=None if last else xh[1], out_l=None if last else xl[1],
+        o = outputs(last, 1)
+        ev = probe(fl, nb_last if last else nb_mid, kn)
+        K.gemm_x3(xh[0], xl[0], self._Gh, self._Gl, self._ginv, o["C"], D=xt[0], alpha_v=coef[0, 0],
+                  gamma_v=coef[0, 2], out_h=o["out_h"], out_l=o["out_l"],
                   out_scale=X3_SCALE, overflow=self._ovf, b_blocked=self._g_blocked, active=self._active,
-                  a_blocked=True, o_blocked=True, single=single, Ct=ct if last else None)
+                  a_blocked=True, o_blocked=True, single=single, Ct=o["Ct"])
         EVENT_PROBE.stop(ev)
         self.stats.matvecs += 1
         prev, cur = 0, 1
         for i in range(1, deg):
             last = i == deg - 1
-            ev = probe(fl, nb, kn)
-            K.gemm_x3(xh[cur], xl[cur], self._Gh, self._Gl, self._ginv, xt[prev], P=xt[prev], D=xt[cur],
+            o = outputs(last, prev)
+            ev = probe(fl, nb_last if last else nb_mid, kn)
+            K.gemm_x3(xh[cur], xl[cur], self._Gh, self._Gl, self._ginv, o["C"], P=xt[prev], D=xt[cur],
                       alpha_v=coef[i, 0], beta_v=coef[i, 1], gamma_v=coef[i, 2],
-                      out_h=None if last else xh[prev], out_l=None if last else xl[prev],
+                      out_h=o["out_h"], out_l=o["out_l"],
                       out_scale=X3_SCALE, overflow=self._ovf, b_blocked=self._g_blocked,
-                      active=self._active, a_blocked=True, o_blocked=True, single=single,
-                      Ct=ct if last else None)
+                      active=self._active, a_blocked=True, o_blocked=True, single=single, Ct=o["Ct"])
             EVENT_PROBE.stop(ev)
             self.stats.matvecs += 1
             prev, cur = cur, prev

@@ -296,7 +296,8 @@ int cq_pow2_from_absmax(float* scale_inout, int64_t batch, int log2_target, void
 int cq_split_f16(const float* X, int64_t n_per, int64_t batch, const float* scale_v, float scale,
                  uint16_t* hi, uint16_t* lo, int64_t blocked_ncols, void* stream);
 /* Y[b] = X[b]^T (X rows x cols row-major -> Y cols x rows), and/or its split (scale_v[b], or
- * scale if scale_v is NULL); blocked: halves K-blocked over Y's columns (rows % 32 == 0). */
+ * scale if scale_v is NULL); blocked: halves K-blocked over Y's columns (rows % 32 == 0).
+ * lo may be NULL with hi given: the hi half alone (the operand of a single product). */
 int cq_transpose_split(const float* X, int64_t rows, int64_t cols, int64_t batch, float* Y,
                        uint16_t* hi, uint16_t* lo, float scale, const float* scale_v, int blocked,
                        void* stream);
@@ -315,14 +316,16 @@ typedef struct cq_x3_args {
     const uint16_t *Bh, *Bl;       /* N x K halves: op(B)[k][n] = B[n][k] */
     int64_t ldb, stride_b;
     const float* inv_scale;        /* [batch]: 1 / (scale_A * scale_B) */
-    float* C;                      /* M x N fp32 */
+    float* C;                      /* M x N fp32; may be NULL when Ct is given (C^T alone) */
     int64_t ldc, stride_c;
-    const float* P;                /* beta term operand (may alias C) */
+    const float* P;                /* beta term operand (may alias C: the same pointer, ld, stride) */
     int64_t ldp, stride_p;
     const float* D;                /* gamma term operand */
     int64_t ldd, stride_d;
     const float *alpha_v, *beta_v, *gamma_v;  /* [batch] each; NULL = 1, 0, 0 */
-    uint16_t *out_h, *out_l;       /* optional split of C (scale out_scale) */
+    uint16_t *out_h, *out_l;       /* optional split of C (scale out_scale); out_l may be NULL with
+                                      out_h given (hi halves only: the next product is single) --
+                                      not with sym_out; the overflow flags are the same */
     int64_t ldo, stride_o;
     float out_scale;
     int* overflow;                 /* [batch]: set to 1 when |C * out_scale| >= 65504 */
