@@ -1,5 +1,5 @@
-// Shared definitions of the split-fp16 kernels (cq_x3.hip) and the row-panel fused Q update
-// (cq_qupdate.hip): operand-tile argument blocks and vector types.
+// Shared definitions of the split-fp16 kernels (cq_x3.hip, cq_qtile.hip, cq_split.hip) and the
+// row-panel fused Q update (cq_qupdate.hip): operand-tile argument blocks and vector types.
 #pragma once
 
 #include "cq_common.h"

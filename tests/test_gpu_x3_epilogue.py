@@ -169,6 +169,31 @@ def test_split_k_optional_outputs(K, mode):
     _check_fp64(c, True, ref["C"])
 
 
+@pytest.mark.parametrize("Kd,ksplit", [(32, 1), (64, 1), (96, 1), (128, 1), (160, 1), (192, 1), (96, 2)])
+def test_ring_depths_agree(K, Kd, ksplit):
+    """The 2-, 3- and 4-slot K rings (split, exact-B, single) on operands that are fp16 at the
+    split scale (both lo halves zero: the extra products add exact zeros) give the same bits at
+    1 to 6 K steps -- below, at and above every ring's prologue depth -- and for split-K chunks
+    of 1 and 2 steps (a nonzero K offset with a chunk shorter than the prologue).  M = 96: the
+    second wave row is dead; N = 416: the second column tile is 32 wide."""
+    Bt, M = 2, 96
+    g = torch.Generator(device=DEV).manual_seed(Kd)
+    A = ((torch.randn(Bt, M, Kd, device=DEV, generator=g) * 0.1) * SA).half().float() / SA
+    Bm = (torch.randn(Bt, N, Kd, device=DEV, generator=g) * SB).half().float() / SB
+    Ah, Al = K.split_f16(A.contiguous(), SA, blocked=True)
+    Bh, Bl = K.split_f16(Bm.contiguous(), SB, blocked=True)
+    assert Ah.any() and Bh.any() and not Al.any() and not Bl.any()
+    inv = torch.full((Bt,), 1.0 / (SA * SB), device=DEV)
+    out = {}
+    for mode in MODES:
+        C = torch.full((Bt, M, N), float("nan"), device=DEV)
+        K.gemm_x3(Ah, Al, Bh, None if mode == "exact" else Bl, inv, C, a_blocked=True, b_blocked=True,
+                  single=mode == "single", b_exact=mode == "exact", ksplit=ksplit)
+        out[mode] = C
+    assert torch.isfinite(out["split"]).all() and out["split"].any()
+    assert torch.equal(out["single"], out["split"]) and torch.equal(out["exact"], out["split"])
+
+
 @pytest.mark.parametrize("rows,cols", [(96, 64), (70, 33)])
 def test_transpose_split_hi_only(K, rows, cols):
     """transpose_split without lo: X^T and the hi half as with it (vector and scalar kernels)."""

@@ -1,5 +1,5 @@
 // Probe (test infrastructure, not product code): what bounds the split-fp16 filter step
-// gemm_x3v_kernel<0> (cq_x3.hip xv_mainloop)?  Same tile (192 x 384 x 32, 12 waves of 96 x 64,
+// gemm_x3v_kernel<0> (cq_x3_tile.h xr_mainloop<0>)?  Same tile (192 x 384 x 32, 12 waves of 96 x 64,
 // 16x16x32 MFMAs, 2-stage LDS-DMA ring, swizzled images) on the config-2 B = 256 shapes
 // (A = X^T halves 192 x 4096, B = G halves 4096 x 4096, K-blocked), random fp16 operands,
 // with parts of the work removed:
