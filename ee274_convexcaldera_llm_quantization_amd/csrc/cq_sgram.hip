@@ -20,6 +20,8 @@
 //   sgram_combine_kernel G = A - s (P + P^T) per 64 x 64 tile pair (I <= J), P^T through LDS,
 //                        split halves written at (i, j) and mirrored (j, i).
 // Every sum runs in a fixed order (per row j the fill order): results are deterministic.
+#include <algorithm>
+
 #include "cq_common.h"
 
 namespace cq {
@@ -405,6 +407,7 @@ __global__ __launch_bounds__(256, 6) void sgram_fill_kernel(const uint8_t* __res
 // The ELL loads (L2) are software-pipelined SG_PF entries ahead of the LDS reads and FMAs.
 constexpr int SG_PF = 6;
 constexpr int SG_WAVES = 16, SG_THREADS = 64 * SG_WAVES;
+constexpr int64_t SG_NB_MAX = 8;   // row blocks per workgroup of the register-held SpMM, at most
 
 // E slab layout: planes of SG_PL rows, each plane l-major with SG_PL floats per l (16 bytes
 // for R >= 4: the l-th entry starts in LDS bank group l mod 16)
@@ -451,10 +454,25 @@ __device__ __forceinline__ void sg_slice(const float* __restrict__ slab, int64_t
 }
 
 // P[b, i0 + r, j] for r < R and every row j of c.  LDS: E rows i0 .. i0 + R - 1 as
-// the l-major slab (sg_slab_at, fp32), E_il = (W_il - (s/2) c_il) * w_l.  Wave wv takes the slices wv,
-// wv + 16, ...; with NSW > 0 (ceil(ns / 16) <= NSW) it keeps all of its results in registers and
-// the R output rows are assembled in LDS (the slab's space, k <= L, j-major) and stored over j
-// -- the sorted slices' rows are scattered over j, so direct stores would be 4-byte scatters
+// the l-major slab (sg_slab_at, fp32), E_il = (W_il - (s/2) c_il) * w_l.  The count-sorted slices
+// go to the waves in a snake (sg_wave_slice): slices 16 q .. 16 q + 15 in wave order for even q and
+// in reverse for odd q, so no wave gets the widest slice of every group.  With NSW > 0
+// (ceil(ns / 16) <= NSW) a wave keeps all of its results in registers and the R output rows are
+// assembled in LDS (the slab's space, k <= L, j-major) and stored over j -- the sorted slices'
+// rows are scattered over j, so direct stores would be 4-byte scatters.  That form takes nb
+// consecutive row blocks (i0, i0 + R, ...) per workgroup: the W and code loads of the next block
+// are issued before the current block's sweep and land under it (converted and written to the
+// slab after the block's output pass), and the slice offsets and perm entries are read once.
+struct SgStageRegs {
+    uint4 raw[4];
+    uint32_t two[4];
+};
+
+// q-th slice of wave wv
+__device__ __forceinline__ int64_t sg_wave_slice(int wv, int q) {
+    return (int64_t)SG_WAVES * q + ((q & 1) ? SG_WAVES - 1 - wv : wv);
+}
+
 template <int R, int NSW, bool SPLIT = false>
 __global__ __launch_bounds__(1024) void sgram_spmm_kernel(const _Float16* __restrict__ W, const uint8_t* __restrict__ packed,
                                                          const float* __restrict__ qscale, const float* __restrict__ wcol,
@@ -462,115 +480,186 @@ __global__ __launch_bounds__(1024) void sgram_spmm_kernel(const _Float16* __rest
                                                          const int32_t* __restrict__ perm,
                                                          const int64_t* __restrict__ slice_off,
                                                          const int32_t* __restrict__ slice_w1, int64_t Lh,
-                                                         int64_t stride_ell, float* __restrict__ P, int64_t wcs) {
+                                                         int64_t stride_ell, float* __restrict__ P, int64_t wcs, int nb) {
     extern __shared__ __attribute__((aligned(16))) float slab[];
     const int64_t b = blockIdx.y;
+    int tid = threadIdx.x;
     if (wcol) wcol += b * wcs;  // per-matrix column weights (stride 0: shared)
-    const int64_t i0 = (int64_t)blockIdx.x * R;
     const float hs = 0.5f * qscale[b];
     const int64_t KL = k * L;
     const int64_t Ls = SPLIT ? Lh : L;   // l-values a slab holds (SPLIT: each part of the contraction)
-    // stage E for l in [la, lb): per plane, a thread loads 8 consecutive l of each of its PL rows
-    // (16-byte W and 2-byte code loads) and stores the 8 l-entries (PL floats each) in an order
-    // rotated by its lane (t mod 8): the 8 lanes of a ds_write_b128 group then hit 8 different
-    // bank groups instead of one (the entries of consecutive lanes lie 128 bytes apart)
+    // stage E for l in [la, lb): a work item is 8 consecutive l of one plane's PL rows (16-byte W
+    // and 2-byte code loads); item `it` is plane it / ((lb - la) / 8), so both planes of R = 8 are
+    // staged in one pass by different threads.  A thread stores its 8 l-entries (PL floats each)
+    // in an order rotated by its lane (t mod 8): the 8 lanes of a ds_write_b128 group then hit 8
+    // different bank groups instead of one (the entries of consecutive lanes lie 128 bytes apart).
+    // issue: the loads only; commit: convert and write to the slab
     constexpr int PL = R < 4 ? R : 4;
-    auto stage = [&](int64_t la, int64_t lb) {
+    constexpr int NPL = R / PL;
+    auto issue = [&](int64_t i0, int pl, int64_t l0, SgStageRegs& g) {
 #pragma unroll
-    for (int pl = 0; pl < R / PL; ++pl) {
-        for (int64_t l0 = la + (int64_t)threadIdx.x * 8; l0 < lb; l0 += SG_THREADS * 8) {
-            float e[PL][8];
-#pragma unroll
-            for (int r = 0; r < PL; ++r) {
-                const int64_t i = i0 + pl * PL + r;
-                if (i < k) {
-                    const int64_t el = b * KL + i * L + l0;
-                    const uint4 raw = *reinterpret_cast<const uint4*>(W + el);
-                    const _Float16* hv = reinterpret_cast<const _Float16*>(&raw);
-                    const uint16_t two = *reinterpret_cast<const uint16_t*>(packed + el / 4);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const uint32_t byte = (u < 4) ? (two & 0xffu) : (two >> 8);
-                        const float c = (float)((int)((byte >> (6 - 2 * (u & 3))) & 3u) - 1);
-                        e[r][u] = (float)hv[u] - hs * c;
-                        if (wcol) e[r][u] *= wcol[l0 + u];
-                    }
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) e[r][u] = 0.f;
-                }
-            }
-            const int rot = threadIdx.x & 7;
-#pragma unroll
-            for (int sh = 1; sh < 8; sh <<= 1) {  // e[r][u] <- e[r][(u + rot) & 7], log shifter
-                if (rot & sh) {
-#pragma unroll
-                    for (int r = 0; r < PL; ++r) {
-                        float t8[8];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) t8[u] = e[r][(u + sh) & 7];
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) e[r][u] = t8[u];
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                float* dst = slab + (int64_t)pl * PL * Ls + (l0 - la + ((u + rot) & 7)) * PL;
-                if constexpr (PL == 4) *reinterpret_cast<float4*>(dst) = make_float4(e[0][u], e[1][u], e[2][u], e[3][u]);
-                else *reinterpret_cast<float2*>(dst) = make_float2(e[0][u], e[1][u]);
+        for (int r = 0; r < PL; ++r) {
+            const int64_t i = i0 + pl * PL + r;
+            if (i < k) {
+                const int64_t el = b * KL + i * L + l0;
+                g.raw[r] = *reinterpret_cast<const uint4*>(W + el);
+                g.two[r] = *reinterpret_cast<const uint16_t*>(packed + el / 4);
+            } else {
+                g.raw[r] = make_uint4(0u, 0u, 0u, 0u);
+                g.two[r] = 0x5555u;   // codes 0
             }
         }
-    }
     };
-    stage(0, SPLIT ? Lh : L);
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    auto commit = [&](int64_t i0, int pl, int64_t l0, int64_t la, const SgStageRegs& g) {
+        // the u-th store takes the l-entry m = (u + rot) & 7: the rows' 8 halves are rotated as
+        // loaded (by rot / 2 dwords, then by a half), so entry m is half u of the rotated row
+        const int rot = tid & 7;
+        uint32_t d[PL][4];
+#pragma unroll
+        for (int r = 0; r < PL; ++r) {
+            const uint32_t x[4] = {g.raw[r].x, g.raw[r].y, g.raw[r].z, g.raw[r].w};
+            uint32_t y[4], z[4];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) y[v] = (rot & 2) ? x[(v + 1) & 3] : x[v];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) z[v] = (rot & 4) ? y[(v + 2) & 3] : y[v];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) d[r][v] = __builtin_amdgcn_alignbit(z[(v + 1) & 3], z[v], 16 * (rot & 1));
+        }
+        float wv[4];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int m = (u + rot) & 7;
+            const int sh = 2 * (m & 4) + 6 - 2 * (m & 3);   // the code's bits: byte m / 4, MSB-first
+            if (wcol && (u & 3) == 0) {   // the weights of four stores in one batch of loads
+#pragma unroll
+                for (int v = 0; v < 4; ++v) wv[v] = wcol[l0 + ((u + v + rot) & 7)];
+            }
+            float e[PL];
+#pragma unroll
+            for (int r = 0; r < PL; ++r) {
+                const uint16_t hb = (uint16_t)(u & 1 ? d[r][u >> 1] >> 16 : d[r][u >> 1] & 0xffffu);
+                _Float16 h;
+                __builtin_memcpy(&h, &hb, 2);
+                const float c = (float)((int)((g.two[r] >> sh) & 3u) - 1);
+                e[r] = (float)h - hs * c;
+            }
+            if (wcol) {
+#pragma unroll
+                for (int r = 0; r < PL; ++r) e[r] *= wv[u & 3];
+            }
+#pragma unroll
+            for (int r = 0; r < PL; ++r)
+                if (!(i0 + pl * PL + r < k)) e[r] = 0.f;
+            float* dst = slab + (pl * PL * (int)Ls + ((int)(l0 - la) + m) * PL);
+            if constexpr (PL == 4) *reinterpret_cast<float4*>(dst) = make_float4(e[0], e[1], e[2], e[3]);
+            else *reinterpret_cast<float2*>(dst) = make_float2(e[0], e[1]);
+        }
+    };
+    // the items from `first` on (a thread's items: first + threadIdx.x, + SG_THREADS, ...)
+    auto stage = [&](int64_t i0, int64_t la, int64_t lb, int first) {
+        const int nl8 = (int)((lb - la) / 8);
+        for (int it = first + tid; it < NPL * nl8; it += SG_THREADS) {
+            const int pl = NPL > 1 && it >= nl8 ? 1 : 0;
+            const int64_t l0 = la + (int64_t)(it - pl * nl8) * 8;
+            SgStageRegs g;
+            issue(i0, pl, l0, g);
+            commit(i0, pl, l0, la, g);
+        }
+    };
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int lane = threadIdx.x & 63;
     const int64_t ns = (k + SG_SLICE - 1) / SG_SLICE;
     const int64_t* so = slice_off + b * (ns + 1);
-    const uint32_t* eb = ell + b * stride_ell + lane;
+    const uint32_t* eb = ell + b * stride_ell;   // + lane
     const int32_t* pm = perm + b * k;
     float* Pb = P + b * k * k;
     if constexpr (NSW > 0) {
-        float acc[NSW][R];
+        const int64_t nblk = (k + R - 1) / R;
+        const int64_t blk0 = (int64_t)blockIdx.x * nb;
+        const int nbk = (int)min<int64_t>(nb, nblk - blk0);
+        const int nl8 = (int)(L / 8);
+        // read once per workgroup: the wave's slices (offset, width) and the rows j of the thread's
+        // results, two to a register (k <= L and 32 L bytes of LDS: a row index is below 65535)
+        int64_t eoff[NSW];
+        int32_t wid[NSW];
+        uint32_t pmv[(NSW + 1) / 2] = {};
 #pragma unroll
         for (int q = 0; q < NSW; ++q) {
-            const int64_t s = wv + SG_WAVES * q;
-            if (s < ns) sg_slice<R>(slab, L, eb + so[s] * SG_SLICE, so[s + 1] - so[s], acc[q]);
+            const int64_t s = sg_wave_slice(wv, q);
+            eoff[q] = s < ns ? so[s] * SG_SLICE : 0;
+            wid[q] = s < ns ? (int32_t)(so[s + 1] - so[s]) : -1;
+            const int64_t p = s * SG_SLICE + lane;
+            pmv[q / 2] |= (p < k ? (uint32_t)pm[p] : 0xffffu) << (16 * (q & 1));
         }
-        __syncthreads();  // every wave is done with the slab: it becomes the k x R output block
-        // (j-major, one 16- or 8-byte store per PL rows: few LDS writes for the scattered j)
+        // a thread's first staging item (item tid) is the same in every block: its loads for the
+        // next block stay in g over the sweep
+        SgStageRegs g;
+        if (tid < NPL * nl8) issue(blk0 * R, NPL > 1 && tid >= nl8 ? 1 : 0, (int64_t)(tid >= nl8 ? tid - nl8 : tid) * 8, g);
+        for (int n = 0; n < nbk; ++n) {
+            // the thread's indices are recomputed in every block: hoisted out of this loop, the
+            // addresses derived from them would stay in registers over the sweep (scratch spills)
+            asm volatile("" : "+v"(tid), "+v"(lane));
 #pragma unroll
-        for (int q = 0; q < NSW; ++q) {
-            const int64_t p = (wv + SG_WAVES * q) * SG_SLICE + lane;
-            if (p < k) {
-                float* dst = slab + pm[p] * R;
+            for (int q = 0; q < (NSW + 1) / 2; ++q) asm volatile("" : "+v"(pmv[q]));
+            const bool has0 = tid < NPL * nl8;
+            const int pl0 = NPL > 1 && tid >= nl8 ? 1 : 0;
+            const int64_t l00 = (int64_t)(tid - pl0 * nl8) * 8;
+            const int64_t i0 = (blk0 + n) * R;
+            if (n > 0) __syncthreads();   // the output block of the block before has been read
+            // the first item comes from the registers; the others (L > 4096) are loaded here
+            for (int it = tid; it < NPL * nl8; it += SG_THREADS) {
+                asm volatile("" : "+v"(tid));   // (as above: nothing of commit's hoisted out of here)
+                const int pl = NPL > 1 && it >= nl8 ? 1 : 0;
+                const int64_t l0 = (int64_t)(it - pl * nl8) * 8;
+                if (it >= SG_THREADS) issue(i0, pl, l0, g);
+                commit(i0, pl, l0, 0, g);
+            }
+            __syncthreads();
+            if (n + 1 < nbk && has0) issue(i0 + R, pl0, l00, g);
+            float acc[NSW][R];
 #pragma unroll
-                for (int pl = 0; pl < R / PL; ++pl) {
-                    if constexpr (PL == 4)
-                        *reinterpret_cast<float4*>(dst + 4 * pl) = make_float4(acc[q][4 * pl], acc[q][4 * pl + 1],
-                                                                              acc[q][4 * pl + 2], acc[q][4 * pl + 3]);
-                    else *reinterpret_cast<float2*>(dst) = make_float2(acc[q][0], acc[q][1]);
+            for (int q = 0; q < NSW; ++q)
+                if (wid[q] >= 0) sg_slice<R>(slab, L, eb + eoff[q] + lane, wid[q], acc[q]);
+            __syncthreads();  // every wave is done with the slab: it becomes the k x R output block
+            // the next block's loads have landed under the sweep: waiting for them here, and not
+            // where they are used, keeps that wait from covering the output stores below
+#pragma unroll
+            for (int r = 0; r < PL; ++r)
+                asm volatile("" : "+v"(g.raw[r].x), "+v"(g.raw[r].y), "+v"(g.raw[r].z), "+v"(g.raw[r].w), "+v"(g.two[r]));
+            // (j-major, one 16- or 8-byte store per PL rows: few LDS writes for the scattered j)
+#pragma unroll
+            for (int q = 0; q < NSW; ++q) {
+                const uint32_t j = (pmv[q / 2] >> (16 * (q & 1))) & 0xffffu;
+                if (j != 0xffffu) {
+                    float* dst = slab + j * R;
+#pragma unroll
+                    for (int pl = 0; pl < NPL; ++pl) {
+                        if constexpr (PL == 4)
+                            *reinterpret_cast<float4*>(dst + 4 * pl) = make_float4(acc[q][4 * pl], acc[q][4 * pl + 1],
+                                                                                  acc[q][4 * pl + 2], acc[q][4 * pl + 3]);
+                        else *reinterpret_cast<float2*>(dst) = make_float2(acc[q][0], acc[q][1]);
+                    }
                 }
             }
-        }
-        __syncthreads();
-        // one j per thread: its R values (contiguous in LDS) to the R rows of P, coalesced over j
-        for (int64_t j = threadIdx.x; j < k; j += SG_THREADS) {
-            float v[R];
+            __syncthreads();
+            // one j per thread: its R values (contiguous in LDS) to the R rows of P, coalesced over j
+            for (int64_t j = tid; j < k; j += SG_THREADS) {
+                float v[R];
 #pragma unroll
-            for (int pl = 0; pl < R / PL; ++pl) {
-                if constexpr (PL == 4) {
-                    const float4 x = *reinterpret_cast<const float4*>(slab + j * R + 4 * pl);
-                    v[4 * pl] = x.x; v[4 * pl + 1] = x.y; v[4 * pl + 2] = x.z; v[4 * pl + 3] = x.w;
-                } else {
-                    const float2 x = *reinterpret_cast<const float2*>(slab + j * R);
-                    v[0] = x.x; v[1] = x.y;
+                for (int pl = 0; pl < NPL; ++pl) {
+                    if constexpr (PL == 4) {
+                        const float4 x = *reinterpret_cast<const float4*>(slab + j * R + 4 * pl);
+                        v[4 * pl] = x.x; v[4 * pl + 1] = x.y; v[4 * pl + 2] = x.z; v[4 * pl + 3] = x.w;
+                    } else {
+                        const float2 x = *reinterpret_cast<const float2*>(slab + j * R);
+                        v[0] = x.x; v[1] = x.y;
+                    }
                 }
-            }
 #pragma unroll
-            for (int r = 0; r < R; ++r)
-                if (i0 + r < k) Pb[(i0 + r) * k + j] = v[r];
+                for (int r = 0; r < R; ++r)
+                    if (i0 + r < k) Pb[(i0 + r) * k + j] = v[r];
+            }
         }
     } else if constexpr (NSW < 0) {
         // output block of its own after the slab (k x R, j-major): each slice's results go to
@@ -580,11 +669,16 @@ __global__ __launch_bounds__(1024) void sgram_spmm_kernel(const _Float16* __rest
         // the slab of l in [0, Lh), then the slab is restaged with l in [Lh, L) and the second
         // parts are added: every workgroup still reads the ELL once, but half as many do it
         // as with R = 2 rows over the whole contraction
+        const int64_t i0 = (int64_t)blockIdx.x * R;
+        stage(i0, 0, Ls, 0);
+        __syncthreads();
         float* outb = slab + (int64_t)R * Ls;
         const int32_t* w1 = SPLIT ? slice_w1 + b * ns : nullptr;
-        for (int64_t s = wv; s < ns; s += SG_WAVES) {
+        for (int q = 0; SG_WAVES * q < ns; ++q) {
+            const int64_t s = sg_wave_slice(wv, q);
+            if (s >= ns) continue;
             float acc[R];
-            sg_slice<R>(slab, Ls, eb + so[s] * SG_SLICE, SPLIT ? w1[s] : so[s + 1] - so[s], acc);
+            sg_slice<R>(slab, Ls, eb + so[s] * SG_SLICE + lane, SPLIT ? w1[s] : so[s + 1] - so[s], acc);
             const int64_t p = s * SG_SLICE + lane;
             if (p < k) {
 #pragma unroll
@@ -593,11 +687,13 @@ __global__ __launch_bounds__(1024) void sgram_spmm_kernel(const _Float16* __rest
         }
         if constexpr (SPLIT) {
             __syncthreads();   // every wave is done with the first part's slab
-            stage(Lh, L);
+            stage(i0, Lh, L, 0);
             __syncthreads();
-            for (int64_t s = wv; s < ns; s += SG_WAVES) {
+            for (int q = 0; SG_WAVES * q < ns; ++q) {
+                const int64_t s = sg_wave_slice(wv, q);
+                if (s >= ns) continue;
                 float acc[R];
-                sg_slice<R>(slab, Ls, eb + (so[s] + w1[s]) * SG_SLICE, so[s + 1] - so[s] - w1[s], acc, Lh);
+                sg_slice<R>(slab, Ls, eb + (so[s] + w1[s]) * SG_SLICE + lane, so[s + 1] - so[s] - w1[s], acc, Lh);
                 const int64_t p = s * SG_SLICE + lane;
                 if (p < k) {
 #pragma unroll
@@ -612,9 +708,14 @@ __global__ __launch_bounds__(1024) void sgram_spmm_kernel(const _Float16* __rest
                 if (i0 + r < k) Pb[(i0 + r) * k + j] = outb[j * R + r];
         }
     } else {
-        for (int64_t s = wv; s < ns; s += SG_WAVES) {
+        const int64_t i0 = (int64_t)blockIdx.x * R;
+        stage(i0, 0, L, 0);
+        __syncthreads();
+        for (int q = 0; SG_WAVES * q < ns; ++q) {
+            const int64_t s = sg_wave_slice(wv, q);
+            if (s >= ns) continue;
             float acc[R];
-            sg_slice<R>(slab, L, eb + so[s] * SG_SLICE, so[s + 1] - so[s], acc);
+            sg_slice<R>(slab, L, eb + so[s] * SG_SLICE + lane, so[s + 1] - so[s], acc);
             const int64_t p = s * SG_SLICE + lane;
             if (p < k) {
                 const int64_t j = pm[p];
@@ -1099,13 +1200,13 @@ int cq_sgram_spmm(int dtype, const void* W, const uint8_t* packed, const float* 
         CQ_REQUIRE(Lh == cq_sgram_split(k, L) && slice_w1, "cq_sgram_spmm: Lh must be cq_sgram_split(k, L)");
         const size_t lds = ((size_t)Lh * 4 + (size_t)k * 4) * sizeof(float);
         sgram_spmm_kernel<4, -1, true><<<dim3((unsigned)ceil_div(k, 4), (unsigned)batch), SG_THREADS, lds, s>>>(
-            Wh, packed, qscale, wcol, k, L, ell, perm, slice_off, slice_w1, Lh, stride_ell, P, wcol_stride);
+            Wh, packed, qscale, wcol, k, L, ell, perm, slice_off, slice_w1, Lh, stride_ell, P, wcol_stride, 1);
         return check_launch("cq_sgram_spmm");
     }
     const int R = cq_sgram_rows(L);
     CQ_REQUIRE(R > 0, "cq_sgram_spmm: rows of %lld values do not fit the LDS", (long long)L);
     size_t lds = (size_t)L * R * sizeof(float);
-    const dim3 grid((unsigned)ceil_div(k, R), (unsigned)batch);
+    dim3 grid((unsigned)ceil_div(k, R), (unsigned)batch);
     const int64_t nsw = ceil_div(ceil_div(k, SG_SLICE), SG_WAVES);  // slices per wave
     // the register-held form needs k <= L (the output block reuses the slab's LDS) and fits the
     // 128-VGPR budget of 16 waves per CU only at R = 8 (4 slices per wave): at R = 4 / 2 its 8 /
@@ -1114,9 +1215,15 @@ int cq_sgram_spmm(int dtype, const void* W, const uint8_t* packed, const float* 
     // R = 4 / 2: results through an LDS output block of their own where slab + block fit
     const bool ldsout = !held && R < 8 && lds + (size_t)k * R * sizeof(float) <= 150 * 1024;
     if (ldsout) lds += (size_t)k * R * sizeof(float);
+    // row blocks per workgroup (the register-held form only): as many as leave two workgroups
+    // per CU, at most SG_NB_MAX -- a function of the shapes alone; a grid that has no more than
+    // two workgroups per CU to begin with (one matrix of 4096 rows) stays as it is
+    const int64_t nblk = ceil_div(k, R);
+    const int nb = held ? (int)std::max<int64_t>(1, std::min<int64_t>({SG_NB_MAX, nblk * batch / (2 * kCUs), nblk})) : 1;
+    grid.x = (unsigned)ceil_div(nblk, nb);
 #define CQ_SP(RR, NN) sgram_spmm_kernel<RR, NN><<<grid, SG_THREADS, lds, s>>>(Wh, packed, qscale, wcol, k, L, ell, \
                                                                              perm, slice_off, nullptr, L, stride_ell, P, \
-                                                                             wcol_stride)
+                                                                             wcol_stride, nb)
     if (R == 8) {
         if (held) CQ_SP(8, 4); else CQ_SP(8, 0);
     } else if (R == 4) {

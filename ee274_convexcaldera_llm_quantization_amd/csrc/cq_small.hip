@@ -107,7 +107,7 @@ template <bool TK>
 __global__ __launch_bounds__(kGramThreads) void gram_f64_mfma_kernel(
     int64_t M, int64_t N, int64_t K, int64_t kchunk, int splits, const float* __restrict__ A,
     int64_t lda, int64_t sa, const float* __restrict__ B, int64_t ldb, int64_t sb, int sym,
-    double* __restrict__ part) {
+    double* __restrict__ part, double* __restrict__ C) {
     // row pitch: GT + 16 floats puts the fragment reads' four K rows (lane >> 4) 16 banks apart
     // (conflict-free; GT + 4 overlapped them: 3.2 conflict cycles per LDS instruction in PMC);
     // the TK stash writes columns and keeps GT + 4
@@ -208,7 +208,10 @@ __global__ __launch_bounds__(kGramThreads) void gram_f64_mfma_kernel(
         if (sl + 1 < nsl) stash(1 - cur);
         __syncthreads();
     }
-    double* P = part + ((int64_t)b * splits + split) * M * N;
+    // K not split (C given): the tile goes straight to C, as 0.0 + acc like the reduction's
+    // sum of one partial (-0.0 becomes +0.0), and a sym tile off the diagonal also to its mirror
+    double* P = C ? C + (int64_t)b * M * N : part + ((int64_t)b * splits + split) * M * N;
+    const bool mirror = C && sym && blockIdx.x != blockIdx.y;
     // C/D map of the f64 16x16x4 form: col = lane & 15, row = (lane >> 4) + 4 * reg
 #pragma unroll
     for (int u = 0; u < 2; ++u)
@@ -218,7 +221,11 @@ __global__ __launch_bounds__(kGramThreads) void gram_f64_mfma_kernel(
             for (int r = 0; r < 4; ++r) {
                 const int64_t i = i0 + 32 * wi + 16 * u + lk + 4 * r;
                 const int64_t j = j0 + 32 * wj + 16 * v + li;
-                if (i < M && j < N) P[i * N + j] = acc[u][v][r];
+                if (i < M && j < N) {
+                    const double x = C ? 0.0 + acc[u][v][r] : acc[u][v][r];
+                    P[i * N + j] = x;
+                    if (mirror) P[j * N + i] = x;
+                }
             }
 }
 
@@ -1042,12 +1049,16 @@ int cq_gram_f64(int64_t M, int64_t N, int64_t K, int64_t batch, const float* A, 
                      reinterpret_cast<uintptr_t>(A) % 16 == 0 && reinterpret_cast<uintptr_t>(B) % 16 == 0;
     if (al4 && trans_a == trans_b) {
         const int sym = (A == B && lda == ldb && stride_a == stride_b && M == N) ? 1 : 0;
+        double* direct = splits == 1 ? C : nullptr;   // one partial: no copy pass
         if (trans_a)
             gram_f64_mfma_kernel<true><<<grid, kGramThreads, 0, s>>>(M, N, K, kchunk, splits, A, lda, stride_a, B,
-                                                                     ldb, stride_b, sym, reinterpret_cast<double*>(ws));
+                                                                     ldb, stride_b, sym, reinterpret_cast<double*>(ws),
+                                                                     direct);
         else
             gram_f64_mfma_kernel<false><<<grid, kGramThreads, 0, s>>>(M, N, K, kchunk, splits, A, lda, stride_a, B,
-                                                                      ldb, stride_b, sym, reinterpret_cast<double*>(ws));
+                                                                      ldb, stride_b, sym, reinterpret_cast<double*>(ws),
+                                                                      direct);
+        if (direct) return check_launch("cq_gram_f64");
         if (sym)
             gram_reduce_sym_kernel<<<rgrid, 256, 0, s>>>(reinterpret_cast<double*>(ws), M, splits, batch, C);
         else
