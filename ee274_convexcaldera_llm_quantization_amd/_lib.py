@@ -80,6 +80,20 @@ class X3Args(ctypes.Structure):
     ]
 
 
+class LinearArgs(ctypes.Structure):
+    _fields_ = [
+        ("x", c_vp), ("ldx", c_i64),
+        ("tokens", c_i64), ("m", c_i64), ("n", c_i64), ("r", c_i64),
+        ("bits", c_int),
+        ("codes", c_vp), ("code_stride", c_i64),
+        ("qscale", c_float), ("gscale", c_float),
+        ("L", c_vp), ("ldl", c_i64),
+        ("R", c_vp), ("ldr", c_i64),
+        ("bias", c_vp),
+        ("y", c_vp), ("y_dtype", c_int), ("ldy", c_i64),
+    ]
+
+
 _SIGS = {
     "cq_abi_version": (c_int, []),
     "cq_last_error": (ctypes.c_char_p, []),
@@ -158,6 +172,8 @@ _SIGS = {
     "cq_act_sqsum_workspace": (c_size, [c_i64, c_i64]),
     "cq_act_sqsum_cols": (c_int, [c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_double, c_vp, c_size, c_vp]),
     "cq_act_sqsum_rows": (c_int, [c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_double, c_vp]),
+    "cq_linear_workspace": (c_size, [ctypes.POINTER(LinearArgs)]),
+    "cq_linear_forward": (c_int, [ctypes.POINTER(LinearArgs), c_vp, c_size, c_vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 5  # include/caldera_hip.h CQ_ABI_VERSION
@@ -1112,3 +1128,61 @@ def act_sqsum_rows(x: torch.Tensor, out: torch.Tensor, *, accumulate: bool = Tru
                                     _p(out), int(bool(accumulate)), float(post), _stream(x.device)),
            "cq_act_sqsum_rows")
     return out
+
+
+# ---------------------------------------------------------------------------- packed linear layer
+LINEAR_DECODE_MAX_TOKENS = 16  # include/caldera_hip.h CQ_LINEAR_DECODE_MAX_TOKENS
+LINEAR_MAX_RANK = 1024         # CQ_LINEAR_MAX_RANK
+
+
+def linear_args(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits) -> LinearArgs:
+    """cq_linear_args for x (T, n) fp16, inference-layout codes (m, row bytes) uint8, L (m, r) /
+    R (r, n) fp16 (None or r = 0: codes only), bias (m,) fp32 or None and y (T, m) fp32 / fp16;
+    x, L, R and y may be views with a row stride (unit column stride)."""
+    a = LinearArgs()
+    r = 0 if L is None else L.shape[1]
+
+    def need(cond, what):
+        if not cond:
+            raise ValueError(f"cq_linear: {what}")
+
+    for name, t in (("x", x), ("codes", codes), ("y", y)) + ((("L", L), ("R", R)) if r else ()):
+        need(t.dim() == 2 and t.stride(1) == 1, f"{name} must be a matrix with unit column stride")
+    need(x.dtype == torch.float16, f"x must be fp16, got {x.dtype}")
+    need(codes.dtype == torch.uint8 and codes.shape[0] == m, "codes must be uint8 with one row per output")
+    need(x.shape[1] == n and tuple(y.shape) == (x.shape[0], m), f"x {tuple(x.shape)} / y {tuple(y.shape)} do not fit "
+         f"(tokens, {n}) / (tokens, {m})")
+    need(y.dtype in (torch.float32, torch.float16), f"y must be fp32 or fp16, got {y.dtype}")
+    if r:
+        need(L.dtype == R.dtype == torch.float16, f"L and R must be fp16, got {L.dtype}, {R.dtype}")
+        need(tuple(L.shape) == (m, r) and tuple(R.shape) == (r, n), f"L {tuple(L.shape)} / R {tuple(R.shape)} do not "
+             f"fit {(m, r)} / {(r, n)}")
+    if bias is not None:
+        need(bias.dtype == torch.float32 and tuple(bias.shape) == (m,) and bias.is_contiguous(),
+             f"bias must be a contiguous fp32 ({m},) vector, got {bias.dtype} {tuple(bias.shape)}")
+    a.x, a.ldx = x.data_ptr(), x.stride(0)
+    a.tokens, a.m, a.n, a.r = x.shape[0], m, n, r
+    a.bits = bits
+    a.codes, a.code_stride = codes.data_ptr(), codes.stride(0)
+    a.qscale, a.gscale = float(qscale), float(gscale)
+    if r:
+        a.L, a.ldl = L.data_ptr(), L.stride(0)
+        a.R, a.ldr = R.data_ptr(), R.stride(0)
+    if bias is not None:
+        a.bias = bias.data_ptr()
+    a.y, a.ldy = y.data_ptr(), y.stride(0)
+    a.y_dtype = {torch.float32: CQ_F32, torch.float16: CQ_F16}[y.dtype]
+    return a
+
+
+def linear_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, ws=None):
+    """y = x (gs (Q + L R))^T (+ bias) from the packed codes (cq_linear_forward); ws: a uint8
+    workspace of at least cq_linear_workspace bytes (allocated here when None).  No host
+    synchronisation."""
+    _require_hip(x, codes, L, R, bias, y)
+    a = linear_args(x, codes, qscale, gscale, L, R, bias, y, m=m, n=n, bits=bits)
+    lib = load()
+    if ws is None:
+        ws = workspace(lib.cq_linear_workspace(ctypes.byref(a)), x.device)
+    _check(lib.cq_linear_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)), "cq_linear_forward")
+    return y

@@ -1,0 +1,448 @@
+// Packed linear layer (cq_linear_forward): y = x (gs (Q + L R))^T straight from the 2/4-bit
+// codes and the fp16 factors, never forming the dense weight.
+//
+//   y[t, i] = gs * ((s / k) * sum_j x[t, j] c[i, j] + sum_q z[t, q] L[i, q]) (+ bias[i])
+//   z[t, q] = sum_j x[t, j] R[q, j]
+//
+// Every product is v_mfma_f32_16x16x32_f16 with the tokens as the A rows and 16 weight rows
+// as the B columns: a lane's B fragment is 8 consecutive elements of one weight row, which is
+// 2 (2-bit) or 4 (4-bit) bytes of its packed row or 16 bytes of an fp16 row.  Weights go from
+// memory straight to VGPRs in 16-byte loads (a lane's load holds the B fragments of 8 / 4 / 1
+// MFMAs) and are expanded in registers; x, the small operand every wave shares, comes through
+// L2.  Codes are exact in fp16 and the MFMA accumulates in fp32, so the code sum is exact
+// until it is scaled by s / k once per output.  z crosses between the two launches as split
+// fp16 halves (hi = f16(z), lo = f16(z - hi)).
+//
+// Two shapes of the same kernel (kDecodeMax = CQ_LINEAR_DECODE_MAX_TOKENS):
+//   decode  (T <= 16): one workgroup per 16 weight rows, its 8 waves split K in interleaved
+//     chunks and add their partial tiles in wave order through LDS (fixed order, no atomics);
+//     the next chunk's codes and x fragments are in flight while this one is expanded.  R has
+//     only r / 16 row groups, so the z product also splits K over kDecodeSplitZ workgroups per
+//     group; their fp32 partial z are added in workgroup order, and split into halves, by the
+//     waves of the code kernel that multiply them with L.
+//   prefill (T > 16):  a wave owns 64 weight rows x 64 tokens, so an expanded B fragment
+//     feeds four MFMAs and an x fragment four more; weights are loaded a chunk ahead and x a
+//     k step ahead; the code sum is scaled by s / k in the accumulator and the L product
+//     continues on it.
+#include "cq_common.h"
+
+namespace cq {
+namespace {
+
+using h8 = __attribute__((ext_vector_type(8))) _Float16;
+using h2 = __attribute__((ext_vector_type(2))) _Float16;
+using f4 = __attribute__((ext_vector_type(4))) float;
+using u4 = __attribute__((ext_vector_type(4))) uint32_t;
+
+constexpr int kDecodeMax = CQ_LINEAR_DECODE_MAX_TOKENS;
+constexpr int kDecodeWaves = 8;    // K split of a decode workgroup (chunks interleaved over its waves)
+constexpr int kDecodeWavesZ = 2;   // the z product: waves per workgroup (64 bytes of R per lane and chunk) ...
+constexpr int kDecodeSplitZ = 16;  // ... and workgroups per 16 rows of R: r / 16 workgroups alone would
+                                   // stream R through r / 16 CUs; their partial z are added in order by
+                                   // the code kernel
+constexpr int kPrefillTiles = 4;   // 16-token tiles per wave
+constexpr int kPrefillGroups = 4;  // 16-row groups per wave (codes)
+
+struct LinP {
+    const _Float16* x; int64_t ldx; int x_al;
+    int64_t T, rows, n;        // rows: weight rows (m; r for the z product), n: contraction
+    const uint8_t* w; int64_t wstride; int w_al;  // codes: bytes per row; fp16: elements per row
+    int64_t r, r32;            // rank, rounded up to the MFMA's K (the z buffers' row length)
+    const _Float16* L; int64_t ldl; int l_al;
+    const _Float16* zh; const _Float16* zl;       // [token rows][r32] halves (read)
+    float sk, gs;
+    const float* bias;
+    void* y; int y_f16; int64_t ldy;
+    _Float16* oh; _Float16* ol;                   // z product: halves (written)
+    const float* zp; float* ozp;                  // decode: [kDecodeSplitZ][16][r32] fp32 partial z (read / written)
+};
+
+// elements k .. k + 7 of a row, zero at and beyond lim (lim = 0: nothing is read)
+__device__ __forceinline__ h8 ld8(const _Float16* row, int64_t k, int64_t lim, bool al) {
+    if (al && k + 8 <= lim) return *reinterpret_cast<const h8*>(row + k);
+    h8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (k < lim) {  // a ragged end or an unaligned row: element by element
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (k + j < lim) v[j] = row[k + j];
+    }
+    return v;
+}
+
+// fp16 magic numbers: 0x6400 | f is 1024 + f for a 10-bit field f, so a code field left where
+// it sits in the word (f = code << sh) becomes 1024 + (code << sh); one multiply by 2^-sh and
+// one subtraction of (1024 >> sh) + k, both exact in fp16, give code - k.
+__device__ __forceinline__ uint32_t pair(uint32_t uu, uint32_t mask) { return (uu & mask) | 0x64006400u; }
+__device__ __forceinline__ uint32_t scale_off(uint32_t p, h2 sc, h2 off) {
+    const h2 v = __builtin_bit_cast(h2, p) * sc + off;
+    return __builtin_bit_cast(uint32_t, v);
+}
+
+// B fragment jj of a lane's 16 bytes of codes (offset-binary, MSB-first): 8 consecutive codes
+template <int BITS>
+__device__ __forceinline__ h8 expand(const u4 q, int jj) {
+    u4 o;
+    if constexpr (BITS == 2) {
+        const uint32_t word = q[jj >> 1];
+        // both halves hold the fragment's two bytes
+        uint32_t uu = (jj & 1) ? ((word >> 16) | (word & 0xffff0000u)) : ((word & 0xffffu) | (word << 16));
+        const h2 sa = {(_Float16)(1.0f / 64), (_Float16)(1.0f / 16)}, oa = {(_Float16)-17.0f, (_Float16)-65.0f};
+        const h2 sb = {(_Float16)0.25f, (_Float16)1.0f}, ob = {(_Float16)-257.0f, (_Float16)-1025.0f};
+        o[0] = scale_off(pair(uu, 0x003000C0u), sa, oa);
+        o[1] = scale_off(pair(uu, 0x0003000Cu), sb, ob);
+        uu >>= 8;
+        o[2] = scale_off(pair(uu, 0x003000C0u), sa, oa);
+        o[3] = scale_off(pair(uu, 0x0003000Cu), sb, ob);
+    } else {
+        const uint32_t word = q[jj];
+        const uint32_t u0 = (word & 0xffffu) | (word << 16), u1 = (word >> 16) | (word & 0xffff0000u);
+        const h2 sa = {(_Float16)(1.0f / 16), (_Float16)1.0f}, oa = {(_Float16)-71.0f, (_Float16)-1031.0f};
+        o[0] = scale_off(pair(u0, 0x000F00F0u), sa, oa);
+        o[1] = scale_off(pair(u0 >> 8, 0x000F00F0u), sa, oa);
+        o[2] = scale_off(pair(u1, 0x000F00F0u), sa, oa);
+        o[3] = scale_off(pair(u1 >> 8, 0x000F00F0u), sa, oa);
+    }
+    return __builtin_bit_cast(h8, o);
+}
+
+// WT: 2 / 4 = packed codes (+ the L product and the output epilogue), 16 = fp16 weight rows
+// (the z product: writes split halves).  A wave owns RG groups of 16 weight rows x TT tiles of
+// 16 tokens.  NW: waves per workgroup; KSPLIT: they split K over one 16-row group (else each
+// owns its own rows).
+template <int WT, int TT, int RG, int NW, bool KSPLIT>
+__global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
+    constexpr bool CODES = WT != 16;
+    constexpr int WV = CODES ? 1 : 4;                   // 16-byte weight loads per lane and chunk
+    constexpr int CK = CODES ? 16 * 8 / WT * 4 : 128;   // k per chunk: 4 lane groups x WV loads
+    constexpr int NM = CK / 32;                         // MFMA k steps per chunk
+    constexpr int GK = CK / 4;                          // k per lane group
+    static_assert(!KSPLIT || (TT == 1 && RG == 1), "the K split reduces one tile");
+    struct WR { u4 v[WV]; };
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, g = lane >> 4;
+    const int64_t row0 = (KSPLIT ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * NW + wave) * (16 * RG);
+    // blockIdx.y: the token tile; under the K split (one tile) the workgroup's share of K
+    const int64_t tok0 = KSPLIT ? 0 : (int64_t)blockIdx.y * (TT * 16);
+    const int64_t rows_out = CODES ? p.rows : p.r32;
+    if (!KSPLIT && row0 >= rows_out) return;
+
+    int64_t rowc[RG], wlim[RG];
+#pragma unroll
+    for (int rg = 0; rg < RG; ++rg) {
+        const int64_t row = row0 + rg * 16 + li;
+        rowc[rg] = row < p.rows ? row : p.rows - 1;
+        wlim[rg] = row < p.rows ? p.n : 0;              // fp16 rows past the end read as zero
+    }
+    const _Float16* xrow[TT];
+    int64_t xlim[TT];
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+        const int64_t t = tok0 + tt * 16 + li;
+        xrow[tt] = p.x + (t < p.T ? t : 0) * p.ldx;
+        xlim[tt] = t < p.T ? p.n : 0;
+    }
+
+    f4 acc[RG][TT], accl[RG][TT];
+#pragma unroll
+    for (int rg = 0; rg < RG; ++rg)
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt) acc[rg][tt] = accl[rg][tt] = f4{0.f, 0.f, 0.f, 0.f};
+
+    const int64_t nchunks = (p.n + CK - 1) / CK;
+    const int64_t c0 = KSPLIT ? (int64_t)blockIdx.y * NW + wave : 0, cstep = KSPLIT ? (int64_t)NW * gridDim.y : 1;
+
+    auto load_w = [&](int64_t c, int rg) -> WR {
+        const int64_t kg = c * CK + g * GK;
+        WR w;
+        if constexpr (CODES) {
+            const uint8_t* wrow = p.w + rowc[rg] * p.wstride;
+            // a piece that starts inside n lies inside the 16-byte padded row
+            w.v[0] = kg < p.n ? *reinterpret_cast<const u4*>(wrow + kg * WT / 8) : u4{0u, 0u, 0u, 0u};
+        } else {
+            const _Float16* wrow = reinterpret_cast<const _Float16*>(p.w) + rowc[rg] * p.wstride;
+#pragma unroll
+            for (int jj = 0; jj < WV; ++jj) w.v[jj] = __builtin_bit_cast(u4, ld8(wrow, kg + jj * 8, wlim[rg], p.w_al));
+        }
+        return w;
+    };
+    auto frag = [&](const WR& w, int jj) -> h8 {
+        if constexpr (CODES) return expand<WT>(w.v[0], jj);
+        else return __builtin_bit_cast(h8, w.v[jj]);
+    };
+    auto load_x = [&](int64_t c, int jj, int tt) -> h8 {
+        return ld8(xrow[tt], c * CK + g * GK + jj * 8, xlim[tt], p.x_al);
+    };
+
+    WR q[RG], qn[RG];
+    if constexpr (TT == 1) {
+        // decode: the next chunk's weights and all its x fragments are in flight during this one
+        h8 a[NM], an[NM];
+        if (c0 < nchunks) {
+#pragma unroll
+            for (int rg = 0; rg < RG; ++rg) q[rg] = load_w(c0, rg);
+#pragma unroll
+            for (int jj = 0; jj < NM; ++jj) a[jj] = load_x(c0, jj, 0);
+        }
+        for (int64_t c = c0; c < nchunks; c += cstep) {
+            if (c + cstep < nchunks) {
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg) qn[rg] = load_w(c + cstep, rg);
+#pragma unroll
+                for (int jj = 0; jj < NM; ++jj) an[jj] = load_x(c + cstep, jj, 0);
+            }
+#pragma unroll
+            for (int jj = 0; jj < NM; ++jj) {
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg)
+                    acc[rg][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[jj], frag(q[rg], jj), acc[rg][0], 0, 0, 0);
+            }
+#pragma unroll
+            for (int rg = 0; rg < RG; ++rg) q[rg] = qn[rg];
+#pragma unroll
+            for (int jj = 0; jj < NM; ++jj) a[jj] = an[jj];
+        }
+    } else {
+        // prefill: weights one chunk ahead, x fragments one k step ahead; an expanded B fragment
+        // feeds TT MFMAs and an x fragment RG of them
+        h8 a[TT], an[TT];
+        if (c0 < nchunks) {
+#pragma unroll
+            for (int rg = 0; rg < RG; ++rg) q[rg] = load_w(c0, rg);
+#pragma unroll
+            for (int tt = 0; tt < TT; ++tt) a[tt] = load_x(c0, 0, tt);
+        }
+        for (int64_t c = c0; c < nchunks; c += cstep) {
+            const bool more = c + cstep < nchunks;
+            if (more) {
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg) qn[rg] = load_w(c + cstep, rg);
+            }
+#pragma unroll
+            for (int jj = 0; jj < NM; ++jj) {
+                if (jj + 1 < NM) {
+#pragma unroll
+                    for (int tt = 0; tt < TT; ++tt) an[tt] = load_x(c, jj + 1, tt);
+                } else if (more) {
+#pragma unroll
+                    for (int tt = 0; tt < TT; ++tt) an[tt] = load_x(c + cstep, 0, tt);
+                }
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg) {
+                    const h8 b = frag(q[rg], jj);
+#pragma unroll
+                    for (int tt = 0; tt < TT; ++tt)
+                        acc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[tt], b, acc[rg][tt], 0, 0, 0);
+                }
+#pragma unroll
+                for (int tt = 0; tt < TT; ++tt) a[tt] = an[tt];
+            }
+#pragma unroll
+            for (int rg = 0; rg < RG; ++rg) q[rg] = qn[rg];
+        }
+    }
+
+    // the L product: onto its own tile under the K split, else onto the scaled code sum
+    auto& lacc = *(KSPLIT ? &accl : &acc);
+    if constexpr (CODES) {
+        if constexpr (!KSPLIT) {  // s / k once per output
+#pragma unroll
+            for (int rg = 0; rg < RG; ++rg)
+#pragma unroll
+                for (int tt = 0; tt < TT; ++tt) acc[rg][tt] = acc[rg][tt] * p.sk;
+        }
+        const int64_t lchunks = p.r32 / 32;
+        for (int64_t c = c0; c < lchunks; c += cstep) {
+            const int64_t qq = c * 32 + g * 8;
+            h8 b[RG];
+#pragma unroll
+            for (int rg = 0; rg < RG; ++rg) b[rg] = ld8(p.L + rowc[rg] * p.ldl, qq, p.r, p.l_al);
+#pragma unroll
+            for (int tt = 0; tt < TT; ++tt) {
+                const int64_t zo = (tok0 + tt * 16 + li) * p.r32 + qq;
+                h8 zl, zh;
+                if constexpr (KSPLIT) {  // the partial z of the z kernel's workgroups, added in order
+                    float zs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                    if (li < p.T) {      // rows past T are zero
+                        for (int ks = 0; ks < kDecodeSplitZ; ++ks) {
+                            const f4* pp = reinterpret_cast<const f4*>(p.zp + (int64_t)ks * 16 * p.r32 + zo);
+                            const f4 u = pp[0], v = pp[1];
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) zs[j] += u[j], zs[4 + j] += v[j];
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        zh[j] = (_Float16)zs[j];
+                        zl[j] = (_Float16)(zs[j] - (float)zh[j]);
+                    }
+                } else {
+                    zl = *reinterpret_cast<const h8*>(p.zl + zo);
+                    zh = *reinterpret_cast<const h8*>(p.zh + zo);
+                }
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg) {
+                    lacc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zl, b[rg], lacc[rg][tt], 0, 0, 0);
+                    lacc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zh, b[rg], lacc[rg][tt], 0, 0, 0);
+                }
+            }
+        }
+    }
+
+    if constexpr (KSPLIT) {  // partial tiles summed in wave order
+        constexpr int NA = CODES ? 2 : 1;
+        __shared__ f4 red[NW][NA][64];
+        red[wave][0][lane] = acc[0][0];
+        if constexpr (CODES) red[wave][1][lane] = accl[0][0];
+        __syncthreads();
+        if (wave != 0) return;
+        f4 s0 = red[0][0][lane], s1 = f4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (CODES) s1 = red[0][1][lane];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) {
+            s0 += red[w][0][lane];
+            if constexpr (CODES) s1 += red[w][1][lane];
+        }
+        if constexpr (CODES) accl[0][0] = s0 * p.sk + s1;
+        else acc[0][0] = s0;
+    }
+
+    // D tile: column (weight row) = lane & 15, row (token) = 4 (lane >> 4) + register
+#pragma unroll
+    for (int rg = 0; rg < RG; ++rg) {
+        const int64_t row = row0 + rg * 16 + li;
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t t = tok0 + tt * 16 + g * 4 + e;
+                if constexpr (CODES) {
+                    if (row < p.rows && t < p.T) {
+                        float v = p.gs * lacc[rg][tt][e];
+                        if (p.bias) v += p.bias[row];
+                        if (p.y_f16) reinterpret_cast<_Float16*>(p.y)[t * p.ldy + row] = (_Float16)v;
+                        else reinterpret_cast<float*>(p.y)[t * p.ldy + row] = v;
+                    }
+                } else if constexpr (KSPLIT) {  // this workgroup's partial z, every element written
+                    p.ozp[((int64_t)blockIdx.y * 16 + t) * p.r32 + row] = acc[rg][tt][e];
+                } else if (row < rows_out) {  // the whole [token rows][r32] buffers (zeros past T, r)
+                    const float v = acc[rg][tt][e];
+                    const _Float16 hi = (_Float16)v;
+                    p.oh[t * p.r32 + row] = hi;
+                    p.ol[t * p.r32 + row] = (_Float16)(v - (float)hi);
+                }
+            }
+        }
+    }
+}
+
+inline int64_t token_rows(int64_t T) {
+    return T <= kDecodeMax ? 16 : ceil_div(T, kPrefillTiles * 16) * (kPrefillTiles * 16);
+}
+inline int64_t r32_of(int64_t r) { return ceil_div(r, 32) * 32; }
+inline bool al16(const void* ptr, int64_t ld_elems) {
+    return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld_elems % 8 == 0;
+}
+
+template <int WT>
+void launch(const LinP& p, hipStream_t s) {
+    constexpr bool CODES = WT != 16;
+    const int64_t groups = ceil_div(CODES ? p.rows : p.r32, 16);
+    if (p.T <= kDecodeMax) {
+        constexpr int NW = CODES ? kDecodeWaves : kDecodeWavesZ;
+        const dim3 grid((unsigned)groups, CODES ? 1 : kDecodeSplitZ);
+        hipLaunchKernelGGL((linear_kernel<WT, 1, 1, NW, true>), grid, dim3(NW * 64), 0, s, p);
+    } else {
+        constexpr int NW = CODES ? 4 : 1, RG = CODES ? kPrefillGroups : 1;
+        const dim3 grid((unsigned)ceil_div(groups, NW * RG), (unsigned)ceil_div(p.T, kPrefillTiles * 16));
+        hipLaunchKernelGGL((linear_kernel<WT, kPrefillTiles, RG, NW, false>), grid, dim3(NW * 64), 0, s, p);
+    }
+}
+
+int validate(const cq_linear_args* a) {
+    CQ_REQUIRE(a != nullptr, "cq_linear: null args");
+    CQ_REQUIRE(a->bits == 2 || a->bits == 4, "cq_linear: bits %d not in {2, 4}", a->bits);
+    CQ_REQUIRE(a->tokens >= 0 && a->m > 0 && a->n > 0 && a->r >= 0, "cq_linear: bad shape tokens=%lld m=%lld n=%lld r=%lld",
+               (long long)a->tokens, (long long)a->m, (long long)a->n, (long long)a->r);
+    CQ_REQUIRE(a->r <= CQ_LINEAR_MAX_RANK, "cq_linear: rank %lld > %d", (long long)a->r, CQ_LINEAR_MAX_RANK);
+    CQ_REQUIRE(a->tokens <= (int64_t)65535 * 64 && a->m <= ((int64_t)1 << 31), "cq_linear: shape too large");
+    CQ_REQUIRE(a->y_dtype == CQ_F32 || a->y_dtype == CQ_F16, "cq_linear: y dtype %d not fp32 / fp16", a->y_dtype);
+    CQ_REQUIRE(a->x && a->codes && a->y, "cq_linear: null x / codes / y");
+    CQ_REQUIRE(a->r == 0 || (a->L && a->R), "cq_linear: null L / R with r = %lld", (long long)a->r);
+    CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->codes) & 15) == 0 && a->code_stride % 16 == 0,
+               "cq_linear: codes and their row stride must be 16-byte aligned (inference layout)");
+    CQ_REQUIRE(a->code_stride >= (a->n * a->bits + 7) / 8, "cq_linear: code row stride %lld < %lld bytes",
+               (long long)a->code_stride, (long long)((a->n * a->bits + 7) / 8));
+    CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->x) & 1) == 0 && (reinterpret_cast<uintptr_t>(a->L) & 1) == 0 &&
+                   (reinterpret_cast<uintptr_t>(a->R) & 1) == 0,
+               "cq_linear: misaligned fp16 pointer");
+    CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->y) & (a->y_dtype == CQ_F16 ? 1 : 3)) == 0 &&
+                   (reinterpret_cast<uintptr_t>(a->bias) & 3) == 0,
+               "cq_linear: misaligned y / bias pointer");
+    CQ_REQUIRE(a->ldx >= a->n && a->ldy >= a->m && (a->r == 0 || (a->ldl >= a->r && a->ldr >= a->n)),
+               "cq_linear: leading dimension smaller than the row");
+    return CQ_OK;
+}
+
+}  // namespace
+}  // namespace cq
+
+using namespace cq;
+
+extern "C" size_t cq_linear_workspace(const cq_linear_args* a) {
+    if (a == nullptr || a->r <= 0 || a->tokens <= 0) return 0;
+    if (a->tokens <= kDecodeMax) return (size_t)(kDecodeSplitZ * 16 * r32_of(a->r)) * sizeof(float);
+    return (size_t)(2 * token_rows(a->tokens) * r32_of(a->r)) * sizeof(uint16_t);
+}
+
+extern "C" int cq_linear_forward(const cq_linear_args* a, void* ws, size_t ws_bytes, void* stream) {
+    if (int st = validate(a)) return st;
+    if (a->tokens == 0) return CQ_OK;
+    const size_t need = cq_linear_workspace(a);
+    if (need) {
+        CQ_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
+                   "cq_linear_forward: workspace must be 16-byte aligned");
+        if (ws_bytes < need) return set_error(CQ_EWORKSPACE, "cq_linear_forward: workspace %zu < %zu", ws_bytes, need);
+    }
+    hipStream_t s = as_stream(stream);
+    LinP p{};
+    p.x = reinterpret_cast<const _Float16*>(a->x);
+    p.ldx = a->ldx;
+    p.x_al = al16(a->x, a->ldx);
+    p.T = a->tokens;
+    p.n = a->n;
+    p.r = a->r;
+    p.r32 = r32_of(a->r);
+    _Float16* zh = reinterpret_cast<_Float16*>(ws);
+    _Float16* zl = zh ? zh + token_rows(a->tokens) * p.r32 : nullptr;
+    if (a->r > 0) {  // z = x R^T as split halves
+        LinP z = p;
+        z.rows = a->r;
+        z.w = reinterpret_cast<const uint8_t*>(a->R);
+        z.wstride = a->ldr;
+        z.w_al = al16(a->R, a->ldr);
+        z.ozp = reinterpret_cast<float*>(ws);
+        z.oh = zh;
+        z.ol = zl;
+        launch<16>(z, s);
+        if (int st = check_launch("cq_linear_forward (z)")) return st;
+    }
+    p.rows = a->m;
+    p.w = a->codes;
+    p.wstride = a->code_stride;
+    p.L = reinterpret_cast<const _Float16*>(a->L);
+    p.ldl = a->ldl;
+    p.l_al = a->r > 0 && al16(a->L, a->ldl);
+    p.zp = reinterpret_cast<const float*>(ws);
+    p.zh = zh;
+    p.zl = zl;
+    const float k = (float)((1 << (a->bits - 1)) - 1);
+    p.sk = a->qscale / k;
+    p.gs = a->gscale;
+    p.bias = a->bias;
+    p.y = a->y;
+    p.y_f16 = a->y_dtype == CQ_F16;
+    p.ldy = a->ldy;
+    if (a->bits == 2) launch<2>(p, s);
+    else launch<4>(p, s);
+    return check_launch("cq_linear_forward");
+}

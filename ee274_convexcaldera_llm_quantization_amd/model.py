@@ -184,7 +184,8 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                                selection: LayerSelection | None = None, error_threshold: float = 0.99,
                                scale_W: bool = False, hadamard: bool = False, device="cuda",
                                max_batch: int = 64, keep_dtype: bool = True, decompose: Callable | None = None,
-                               log: Callable | None = None, hadamard_gate: bool = False) -> QuantizationReport:
+                               log: Callable | None = None, hadamard_gate: bool = False,
+                               packed: bool = False) -> QuantizationReport:
     """main.py:135-251 on the MI355X engine.
 
     hessians: {module name: diagonal (n,) or dense (n, n)} — `Hall` (a missing name raises
@@ -198,8 +199,21 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
     decompose(quant_params, Ws, H) -> list of CalderaDecomposition: the engine unless given
       (tests pass a stand-in).  The engine runs every shape batch at once
       (`api.caldera_groups`: all batches interleaved on HIP streams).
+    packed: a layer that passes the error gate is replaced by a `linear.CalderaLinear` built
+      from its decomposition (2/4-bit codes + fp16 factors, applied by cq_linear_forward)
+      instead of receiving the dense `out`; the gate and the counters are unchanged.  Needs
+      uniform 2- or 4-bit Q; not with `hadamard` (the layer would need the transforms around
+      it) and not with `scale_W=True`: like main.py, the gate and the dense write-back use
+      Q + L R of the scaled W without its global scale, while a packed layer applies
+      gs (Q + L R), so the two would be different models and the gate would judge a weight
+      the layer does not apply.  Either combination raises ValueError.
     Returns the QuantizationReport (counters + per-layer outcomes)."""
     qp = quant_params if quant_params is not None else driver_params()
+    if packed and hadamard:
+        raise ValueError("apply_caldera_quantization: packed=True cannot be combined with hadamard=True")
+    if packed and scale_W:
+        raise ValueError("apply_caldera_quantization: packed=True cannot be combined with scale_W=True (the gate "
+                         "and the write-back use Q + L R without the global scale; the packed layer applies it)")
     say = log or (lambda *a: None)
     jobs, rep = select_layers(model, hessians, selection, say)
     # batches: same shape; every layer keeps its own Hessian (a list of per-matrix H, or one
@@ -248,7 +262,13 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                     outcomes[name] = LayerOutcome(name, tuple(W.shape), err, True, dict(dec.errors))
                     continue
                 ok = err <= error_threshold
-                if ok:
+                if ok and packed:
+                    from .linear import CalderaLinear
+                    lin = CalderaLinear.from_decomposition(dec, qp.Q_bits, bias=getattr(module, "bias", None))
+                    _set_module(model, name, lin.to(W.device))
+                    rep.quantized_param_count += W.numel()
+                    say(f"Applied CALDERA (packed) to {name}.weight, shape: {tuple(W.shape)}")
+                elif ok:
                     module.weight.data = (out.to(W.dtype) if keep_dtype else out).to(W.device)
                     rep.quantized_param_count += W.numel()
                     say(f"Applied CALDERA to {name}.weight, shape: {tuple(W.shape)}")
@@ -258,3 +278,32 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                 outcomes[name] = LayerOutcome(name, tuple(W.shape), err, ok, dict(dec.errors))
     rep.layers = [outcomes[j[0]] for j in jobs]
     return rep
+
+
+def _set_module(model: torch.nn.Module, name: str, new: torch.nn.Module):
+    """Replace the submodule `name` (dotted, as named_modules gives it) of `model`."""
+    parent_name, _, leaf = name.rpartition(".")
+    parent = model.get_submodule(parent_name) if parent_name else model
+    setattr(parent, leaf, new)
+
+
+def apply_packed_results(model: torch.nn.Module, results, device=None) -> list:
+    """Replace each `nn.Linear` named by a `sharding.MatrixResult` (e.g. from `load_results`) by
+    a `linear.CalderaLinear` holding that result (the module's bias is kept).  device: where
+    the new layers live (default: each replaced module's own device).  KeyError for a result
+    whose module the model does not have; returns the replaced names."""
+    from .linear import CalderaLinear
+    modules = dict(model.named_modules())
+    done = []
+    for res in results:
+        if res.name not in modules or not res.name:
+            raise KeyError(f"apply_packed_results: the model has no module {res.name!r}")
+        mod = modules[res.name]
+        w = getattr(mod, "weight", None)
+        if w is None or tuple(w.shape) != (res.m, res.n):
+            raise ValueError(f"apply_packed_results: {res.name}: weight {None if w is None else tuple(w.shape)} "
+                             f"!= result {(res.m, res.n)}")
+        lin = CalderaLinear.from_result(res, bias=getattr(mod, "bias", None))
+        _set_module(model, res.name, lin.to(w.device if device is None else device))
+        done.append(res.name)
+    return done

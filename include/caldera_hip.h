@@ -541,6 +541,61 @@ int cq_act_sqsum_cols(int dtype, const void* x, int64_t rows, int64_t cols, int6
 int cq_act_sqsum_rows(int dtype, const void* x, int64_t rows, int64_t len, int64_t ld, double* out,
                       int accumulate, double post, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Packed linear layer: apply one compressed m x n layer W ~ gs (Q + L R) to activations
+ * without forming the dense weight (the consumer of what main.py:198-202 writes back as
+ * `Q + L @ R`; the reference has no packed forward).  For x (tokens x n fp16, row stride ldx):
+ *
+ *   y[t, i] = gs * ((s / k) * sum_j x[t, j] c[i, j] + sum_q z[t, q] L[i, q]) (+ bias[i])
+ *   z[t, q] = sum_j x[t, j] R[q, j]                          k = 2^(bits-1) - 1, bits 2 | 4
+ *
+ * Contract:
+ *   - the code sum is accumulated unscaled (codes c = u - k are exact in fp16) and s / k, one
+ *     fp32 division of the two fp32 values qscale and k, is applied once per output;
+ *   - every sum accumulates in fp32; z crosses between the two products as split fp16
+ *     halves hi = f16(z), lo = f16(z - hi) (the f16x3 idiom: ~2^-22 relative, never a single
+ *     fp16 rounding), so |z| must stay below 65504 as x itself must;
+ *   - y (fp32 | fp16, row stride ldy) is the fp32 result, for fp16 rounded once;
+ *   - L (m x r, row stride ldl) and R (r x n, row stride ldr) are fp16; r = 0: codes only
+ *     (L, R may be NULL); bias (m fp32) may be NULL;
+ *   - no float atomics and a fixed summation order: the same input gives the same bits, and
+ *     row t of y depends on row t of x alone (within one dispatch branch);
+ *   - stream-ordered, no allocation, no host synchronisation (graph-capturable).
+ *
+ * Inference layout of the codes: offset-binary (u = c + k), MSB-first, 4 resp. 2 codes per
+ * byte as everywhere above, but row i starts at codes + i * code_stride bytes with
+ * code_stride a multiple of 16 (>= ceil(n bits / 8)) and codes 16-byte aligned, so every
+ * row takes aligned 16-byte loads (the storage layout's rows are n_padded bits / 8 bytes:
+ * 225 for n = 898).  The row's tail holds code 0 (u = k: bytes 0x55 at 2-bit, 0x77 at
+ * 4-bit).  Columns >= n contribute nothing whatever the codes' tail or x's buffer beyond n
+ * hold: x is not read there.
+ *
+ * Dispatch: tokens <= CQ_LINEAR_DECODE_MAX_TOKENS takes the weight-streaming decode kernels
+ * (one workgroup per 16 rows, K split over its waves, partials added in wave order), more
+ * tokens the prefill kernels (64 rows x 64 tokens per wave).  Two launches: z (skipped for
+ * r = 0), then codes + L + epilogue.  Workspace (cq_linear_workspace bytes, 16-byte aligned):
+ * the z halves (prefill), or the fp32 partial z of the z kernel's K split, which the second
+ * kernel adds in a fixed order before it splits them (decode).
+ * CQ_EINVAL: bits not 2 / 4, r > CQ_LINEAR_MAX_RANK, codes or code_stride not 16-byte
+ * aligned, an fp16 / fp32 pointer not aligned to its element, a row stride below the row. */
+#define CQ_LINEAR_DECODE_MAX_TOKENS 16
+#define CQ_LINEAR_MAX_RANK 1024
+
+typedef struct cq_linear_args {
+    const uint16_t* x; int64_t ldx;
+    int64_t tokens, m, n, r;
+    int bits;
+    const uint8_t* codes; int64_t code_stride;
+    float qscale, gscale;
+    const uint16_t* L; int64_t ldl;
+    const uint16_t* R; int64_t ldr;
+    const float* bias;
+    void* y; int y_dtype; int64_t ldy;
+} cq_linear_args;
+
+size_t cq_linear_workspace(const cq_linear_args* a);
+int cq_linear_forward(const cq_linear_args* a, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
