@@ -94,6 +94,15 @@ class LinearArgs(ctypes.Structure):
     ]
 
 
+class LinearPackedArgs(ctypes.Structure):
+    _fields_ = LinearArgs._fields_ + [
+        ("l_bits", c_int), ("r_bits", c_int),
+        ("L_codes", c_vp), ("l_code_stride", c_i64),
+        ("R_codes", c_vp), ("r_code_stride", c_i64),
+        ("lscale", c_float), ("rscale", c_float),
+    ]
+
+
 _SIGS = {
     "cq_abi_version": (c_int, []),
     "cq_last_error": (ctypes.c_char_p, []),
@@ -174,6 +183,8 @@ _SIGS = {
     "cq_act_sqsum_rows": (c_int, [c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_double, c_vp]),
     "cq_linear_workspace": (c_size, [ctypes.POINTER(LinearArgs)]),
     "cq_linear_forward": (c_int, [ctypes.POINTER(LinearArgs), c_vp, c_size, c_vp]),
+    "cq_linear_packed_workspace": (c_size, [ctypes.POINTER(LinearPackedArgs)]),
+    "cq_linear_packed_forward": (c_int, [ctypes.POINTER(LinearPackedArgs), c_vp, c_size, c_vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 5  # include/caldera_hip.h CQ_ABI_VERSION
@@ -1139,24 +1150,32 @@ def linear_args(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits) -> Linea
     """cq_linear_args for x (T, n) fp16, inference-layout codes (m, row bytes) uint8, L (m, r) /
     R (r, n) fp16 (None or r = 0: codes only), bias (m,) fp32 or None and y (T, m) fp32 / fp16;
     x, L, R and y may be views with a row stride (unit column stride)."""
-    a = LinearArgs()
-    r = 0 if L is None else L.shape[1]
+    return _fill_linear_args(LinearArgs(), x, codes, qscale, gscale, L, R, bias, y, m=m, n=n, bits=bits,
+                             r=0 if L is None else L.shape[1])
 
-    def need(cond, what):
-        if not cond:
-            raise ValueError(f"cq_linear: {what}")
 
-    for name, t in (("x", x), ("codes", codes), ("y", y)) + ((("L", L), ("R", R)) if r else ()):
+def _linear_need(cond, what):
+    if not cond:
+        raise ValueError(f"cq_linear: {what}")
+
+
+def _fill_linear_args(a, x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, r, L_coded=False, R_coded=False):
+    """The fields cq_linear_args and cq_linear_packed_args share; a coded factor's fp16 operand
+    is not looked at."""
+    need = _linear_need
+    fp16 = ((("L", L),) if r and not L_coded else ()) + ((("R", R),) if r and not R_coded else ())
+    for name, t in (("x", x), ("codes", codes), ("y", y)) + fp16:
         need(t.dim() == 2 and t.stride(1) == 1, f"{name} must be a matrix with unit column stride")
     need(x.dtype == torch.float16, f"x must be fp16, got {x.dtype}")
     need(codes.dtype == torch.uint8 and codes.shape[0] == m, "codes must be uint8 with one row per output")
     need(x.shape[1] == n and tuple(y.shape) == (x.shape[0], m), f"x {tuple(x.shape)} / y {tuple(y.shape)} do not fit "
          f"(tokens, {n}) / (tokens, {m})")
     need(y.dtype in (torch.float32, torch.float16), f"y must be fp32 or fp16, got {y.dtype}")
-    if r:
-        need(L.dtype == R.dtype == torch.float16, f"L and R must be fp16, got {L.dtype}, {R.dtype}")
-        need(tuple(L.shape) == (m, r) and tuple(R.shape) == (r, n), f"L {tuple(L.shape)} / R {tuple(R.shape)} do not "
-             f"fit {(m, r)} / {(r, n)}")
+    if fp16:
+        need(all(t.dtype == torch.float16 for _, t in fp16),
+             "L and R must be fp16, got " + ", ".join(str(t.dtype) for _, t in fp16))
+        need(all(tuple(t.shape) == ((m, r) if name == "L" else (r, n)) for name, t in fp16),
+             " / ".join(f"{name} {tuple(t.shape)}" for name, t in fp16) + f" do not fit {(m, r)} / {(r, n)}")
     if bias is not None:
         need(bias.dtype == torch.float32 and tuple(bias.shape) == (m,) and bias.is_contiguous(),
              f"bias must be a contiguous fp32 ({m},) vector, got {bias.dtype} {tuple(bias.shape)}")
@@ -1165,14 +1184,62 @@ def linear_args(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits) -> Linea
     a.bits = bits
     a.codes, a.code_stride = codes.data_ptr(), codes.stride(0)
     a.qscale, a.gscale = float(qscale), float(gscale)
-    if r:
-        a.L, a.ldl = L.data_ptr(), L.stride(0)
-        a.R, a.ldr = R.data_ptr(), R.stride(0)
+    for name, t in fp16:
+        setattr(a, name, t.data_ptr())
+        setattr(a, "ld" + name.lower(), t.stride(0))
     if bias is not None:
         a.bias = bias.data_ptr()
     a.y, a.ldy = y.data_ptr(), y.stride(0)
     a.y_dtype = {torch.float32: CQ_F32, torch.float16: CQ_F16}[y.dtype]
     return a
+
+
+def linear_packed_args(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, r=None, L_codes=None,
+                       R_codes=None) -> LinearPackedArgs:
+    """cq_linear_packed_args: `linear_args` with either factor given by its codes instead of fp16.
+    L_codes / R_codes: (uint8 inference-layout codes with one row per m resp. r, scale, bits in
+    {2, 4}); the fp16 L / R of a coded factor is None.  r: the rank, needed when both factors are
+    coded (else taken from the fp16 one)."""
+    need = _linear_need
+    if r is None:
+        need(L is not None or R is not None or (L_codes is None and R_codes is None),
+             "r is needed when both factors are coded")
+        r = L.shape[1] if L is not None else R.shape[0] if R is not None else 0
+    r = int(r)
+    if r:
+        need((L is None) != (L_codes is None), "give exactly one of L and L_codes")
+        need((R is None) != (R_codes is None), "give exactly one of R and R_codes")
+    a = _fill_linear_args(LinearPackedArgs(), x, codes, qscale, gscale, L, R, bias, y, m=m, n=n, bits=bits, r=r,
+                          L_coded=L_codes is not None, R_coded=R_codes is not None)
+    a.l_bits = a.r_bits = 16
+    for what, spec, rows in (("L", L_codes, m), ("R", R_codes, r)):
+        if spec is None or not r:
+            continue
+        t, scale, fbits = spec
+        need(t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.uint8 and t.shape[0] == rows,
+             f"{what}_codes must be a uint8 matrix with {rows} rows and unit column stride")
+        setattr(a, what.lower() + "_bits", int(fbits))
+        setattr(a, what + "_codes", t.data_ptr())
+        setattr(a, what.lower() + "_code_stride", t.stride(0))
+        setattr(a, what.lower() + "scale", float(scale))
+    return a
+
+
+def linear_packed_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, r=None, L_codes=None,
+                          R_codes=None, ws=None):
+    """y = x (gs (Q + L R))^T (+ bias) with either factor applied from its packed 2/4-bit codes
+    (cq_linear_packed_forward); operands as `linear_packed_args`, ws as `linear_forward`.  No
+    host synchronisation."""
+    _require_hip(x, codes, L, R, bias, y, None if L_codes is None else L_codes[0],
+                 None if R_codes is None else R_codes[0])
+    a = linear_packed_args(x, codes, qscale, gscale, L, R, bias, y, m=m, n=n, bits=bits, r=r, L_codes=L_codes,
+                           R_codes=R_codes)
+    lib = load()
+    if ws is None:
+        ws = workspace(lib.cq_linear_packed_workspace(ctypes.byref(a)), x.device)
+    _check(lib.cq_linear_packed_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)),
+           "cq_linear_packed_forward")
+    return y
 
 
 def linear_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, ws=None):

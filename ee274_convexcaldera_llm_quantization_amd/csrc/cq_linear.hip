@@ -24,6 +24,17 @@
 //     feeds four MFMAs and an x fragment four more; weights are loaded a chunk ahead and x a
 //     k step ahead; the code sum is scaled by s / k in the accumulator and the L product
 //     continues on it.
+//
+// Factor codes (cq_linear_packed_forward): L and / or R as packed 2/4-bit codes with one scale
+// each, in the layout of the layer's own codes.  z~ = zscale * sum_j x rho with rho the integer R
+// codes (the K loop and `expand` of the code kernel, writing z) and zscale the product of the
+// coded factors' scale / k, applied once to the complete fp32 z sum before it is split into halves
+// (the z kernel's epilogue in prefill; after the ordered add of the partial z in decode); the L
+// product then multiplies the halves with the integer L codes, a lane's 16-byte load holding its B
+// fragments of 4 / 8 k steps.  cq_linear_forward is this path with fp16 factors and zscale = 1.
+#include <cmath>
+#include <cstdio>
+
 #include "cq_common.h"
 
 namespace cq {
@@ -55,6 +66,8 @@ struct LinP {
     void* y; int y_f16; int64_t ldy;
     _Float16* oh; _Float16* ol;                   // z product: halves (written)
     const float* zp; float* ozp;                  // decode: [kDecodeSplitZ][16][r32] fp32 partial z (read / written)
+    const uint8_t* lc; int64_t lcstride;          // packed L codes (m rows of r codes): bytes per row
+    float zscale;                                 // on the complete z sum, before it is split (1 without factor codes)
 };
 
 // elements k .. k + 7 of a row, zero at and beyond lim (lim = 0: nothing is read)
@@ -105,13 +118,16 @@ __device__ __forceinline__ h8 expand(const u4 q, int jj) {
     return __builtin_bit_cast(h8, o);
 }
 
-// WT: 2 / 4 = packed codes (+ the L product and the output epilogue), 16 = fp16 weight rows
-// (the z product: writes split halves).  A wave owns RG groups of 16 weight rows x TT tiles of
-// 16 tokens.  NW: waves per workgroup; KSPLIT: they split K over one 16-row group (else each
-// owns its own rows).
-template <int WT, int TT, int RG, int NW, bool KSPLIT>
+// WT: the weight rows of the K loop, 2 / 4 = packed codes, 16 = fp16.  ZP: the z product (the
+// weight rows are R's, fp16 or codes; writes partial z or split halves), else the layer's codes
+// (+ the L product and the output epilogue) with LB: L as fp16 rows (16) or packed 2 / 4-bit
+// codes.  A wave owns RG groups of 16 weight rows x TT tiles of 16 tokens.  NW: waves per
+// workgroup; KSPLIT: they split K over one 16-row group (else each owns its own rows).
+template <int WT, int LB, bool ZP, int TT, int RG, int NW, bool KSPLIT>
 __global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
     constexpr bool CODES = WT != 16;
+    static_assert(!ZP || LB == 16, "the z product has no L");
+    static_assert(ZP || CODES, "the layer's own weight is always codes");
     constexpr int WV = CODES ? 1 : 4;                   // 16-byte weight loads per lane and chunk
     constexpr int CK = CODES ? 16 * 8 / WT * 4 : 128;   // k per chunk: 4 lane groups x WV loads
     constexpr int NM = CK / 32;                         // MFMA k steps per chunk
@@ -123,7 +139,7 @@ __global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
     const int64_t row0 = (KSPLIT ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * NW + wave) * (16 * RG);
     // blockIdx.y: the token tile; under the K split (one tile) the workgroup's share of K
     const int64_t tok0 = KSPLIT ? 0 : (int64_t)blockIdx.y * (TT * 16);
-    const int64_t rows_out = CODES ? p.rows : p.r32;
+    const int64_t rows_out = ZP ? p.r32 : p.rows;
     if (!KSPLIT && row0 >= rows_out) return;
 
     int64_t rowc[RG], wlim[RG];
@@ -172,6 +188,24 @@ __global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
     auto load_x = [&](int64_t c, int jj, int tt) -> h8 {
         return ld8(xrow[tt], c * CK + g * GK + jj * 8, xlim[tt], p.x_al);
     };
+
+    // L codes: a lane's 16 bytes hold its B fragments of LNM k steps, so a chunk is LCK columns of
+    // z and lane group g owns columns c LCK + g LGK ... of it.  A piece that starts inside r lies
+    // inside the 16-byte padded row; past r nothing is read, and the z columns there (r .. r32:
+    // written as zeros; beyond: not read) are zero, so whatever the codes' tail holds contributes
+    // nothing.
+    constexpr int LCK = LB == 16 ? 32 : 16 * 8 / LB * 4, LNM = LCK / 32, LGK = LCK / 4;
+    auto load_l = [&](int64_t c, int rg) -> u4 {
+        const int64_t q0 = c * LCK + g * LGK;
+        return q0 < p.r ? *reinterpret_cast<const u4*>(p.lc + rowc[rg] * p.lcstride + q0 * LB / 8)
+                        : u4{0u, 0u, 0u, 0u};
+    };
+    // decode: the codes of the wave's first L unit are fetched before the K loop (their address
+    // depends on nothing computed here), so the L product does not wait on memory
+    u4 lfirst = u4{0u, 0u, 0u, 0u};
+    if constexpr (!ZP && LB != 16 && KSPLIT) {
+        if (c0 < (p.r + LCK - 1) / LCK * LNM) lfirst = load_l(c0 / LNM, 0);
+    }
 
     WR q[RG], qn[RG];
     if constexpr (TT == 1) {
@@ -243,66 +277,116 @@ __global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
 
     // the L product: onto its own tile under the K split, else onto the scaled code sum
     auto& lacc = *(KSPLIT ? &accl : &acc);
-    if constexpr (CODES) {
+    if constexpr (!ZP) {
         if constexpr (!KSPLIT) {  // s / k once per output
 #pragma unroll
             for (int rg = 0; rg < RG; ++rg)
 #pragma unroll
                 for (int tt = 0; tt < TT; ++tt) acc[rg][tt] = acc[rg][tt] * p.sk;
         }
-        const int64_t lchunks = p.r32 / 32;
-        for (int64_t c = c0; c < lchunks; c += cstep) {
-            const int64_t qq = c * 32 + g * 8;
-            h8 b[RG];
+        // the z fragment of token tile tt at columns qq .. qq + 7 as split halves; zero where an
+        // L chunk of codes reaches past the z buffers' row (qq >= r32)
+        auto load_z = [&](int tt, int64_t qq, h8& zh, h8& zl) {
+            const int64_t zo = (tok0 + tt * 16 + li) * p.r32 + qq;
+            const bool in = LB == 16 || qq < p.r32;
+            if constexpr (KSPLIT) {  // the partial z of the z kernel's workgroups, added in order
+                float zs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                if (li < p.T && in) {  // rows past T are zero
+                    for (int ks = 0; ks < kDecodeSplitZ; ++ks) {
+                        const f4* pp = reinterpret_cast<const f4*>(p.zp + (int64_t)ks * 16 * p.r32 + zo);
+                        const f4 u = pp[0], v = pp[1];
 #pragma unroll
-            for (int rg = 0; rg < RG; ++rg) b[rg] = ld8(p.L + rowc[rg] * p.ldl, qq, p.r, p.l_al);
-#pragma unroll
-            for (int tt = 0; tt < TT; ++tt) {
-                const int64_t zo = (tok0 + tt * 16 + li) * p.r32 + qq;
-                h8 zl, zh;
-                if constexpr (KSPLIT) {  // the partial z of the z kernel's workgroups, added in order
-                    float zs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                    if (li < p.T) {      // rows past T are zero
-                        for (int ks = 0; ks < kDecodeSplitZ; ++ks) {
-                            const f4* pp = reinterpret_cast<const f4*>(p.zp + (int64_t)ks * 16 * p.r32 + zo);
-                            const f4 u = pp[0], v = pp[1];
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) zs[j] += u[j], zs[4 + j] += v[j];
-                        }
+                        for (int j = 0; j < 4; ++j) zs[j] += u[j], zs[4 + j] += v[j];
                     }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        zh[j] = (_Float16)zs[j];
-                        zl[j] = (_Float16)(zs[j] - (float)zh[j]);
-                    }
-                } else {
-                    zl = *reinterpret_cast<const h8*>(p.zl + zo);
-                    zh = *reinterpret_cast<const h8*>(p.zh + zo);
                 }
 #pragma unroll
-                for (int rg = 0; rg < RG; ++rg) {
-                    lacc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zl, b[rg], lacc[rg][tt], 0, 0, 0);
-                    lacc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zh, b[rg], lacc[rg][tt], 0, 0, 0);
+                for (int j = 0; j < 8; ++j) {
+                    const float zv = zs[j] * p.zscale;  // once, on the complete sum
+                    zh[j] = (_Float16)zv;
+                    zl[j] = (_Float16)(zv - (float)zh[j]);
+                }
+            } else if (in) {
+                zl = *reinterpret_cast<const h8*>(p.zl + zo);
+                zh = *reinterpret_cast<const h8*>(p.zh + zo);
+            } else {
+                zl = zh = h8{0, 0, 0, 0, 0, 0, 0, 0};
+            }
+        };
+        if constexpr (LB == 16) {
+            const int64_t lchunks = p.r32 / 32;
+            for (int64_t c = c0; c < lchunks; c += cstep) {
+                const int64_t qq = c * 32 + g * 8;
+                h8 b[RG];
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg) b[rg] = ld8(p.L + rowc[rg] * p.ldl, qq, p.r, p.l_al);
+#pragma unroll
+                for (int tt = 0; tt < TT; ++tt) {
+                    h8 zl, zh;
+                    load_z(tt, qq, zh, zl);
+#pragma unroll
+                    for (int rg = 0; rg < RG; ++rg) {
+                        lacc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zl, b[rg], lacc[rg][tt], 0, 0, 0);
+                        lacc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zh, b[rg], lacc[rg][tt], 0, 0, 0);
+                    }
+                }
+            }
+        } else {
+            const int64_t lchunks = (p.r + LCK - 1) / LCK;
+            if constexpr (KSPLIT) {
+                // decode: the unit of work is one k step of one chunk, interleaved over the waves
+                // (r = 256 at 4 bits is 2 chunks but 8 k steps: one per wave, as with fp16 L)
+                for (int64_t u = c0; u < lchunks * LNM; u += cstep) {
+                    const int64_t c = u / LNM;
+                    const int jj = (int)(u % LNM);
+                    if (c * LCK + jj * 8 >= p.r32) continue;  // no lane has z columns here
+                    const h8 b = expand<LB>(u == c0 ? lfirst : load_l(c, 0), jj);
+                    h8 zl, zh;
+                    load_z(0, c * LCK + g * LGK + jj * 8, zh, zl);
+                    lacc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zl, b, lacc[0][0], 0, 0, 0);
+                    lacc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zh, b, lacc[0][0], 0, 0, 0);
+                }
+            } else {
+                for (int64_t c = 0; c < lchunks; ++c) {
+                    u4 lw[RG];
+#pragma unroll
+                    for (int rg = 0; rg < RG; ++rg) lw[rg] = load_l(c, rg);
+#pragma unroll
+                    for (int jj = 0; jj < LNM; ++jj) {
+                        if (c * LCK + jj * 8 >= p.r32) break;
+                        h8 b[RG];
+#pragma unroll
+                        for (int rg = 0; rg < RG; ++rg) b[rg] = expand<LB>(lw[rg], jj);
+#pragma unroll
+                        for (int tt = 0; tt < TT; ++tt) {
+                            h8 zl, zh;
+                            load_z(tt, c * LCK + g * LGK + jj * 8, zh, zl);
+#pragma unroll
+                            for (int rg = 0; rg < RG; ++rg) {
+                                lacc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zl, b[rg], lacc[rg][tt], 0, 0, 0);
+                                lacc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zh, b[rg], lacc[rg][tt], 0, 0, 0);
+                            }
+                        }
+                    }
                 }
             }
         }
     }
 
     if constexpr (KSPLIT) {  // partial tiles summed in wave order
-        constexpr int NA = CODES ? 2 : 1;
+        constexpr int NA = ZP ? 1 : 2;
         __shared__ f4 red[NW][NA][64];
         red[wave][0][lane] = acc[0][0];
-        if constexpr (CODES) red[wave][1][lane] = accl[0][0];
+        if constexpr (!ZP) red[wave][1][lane] = accl[0][0];
         __syncthreads();
         if (wave != 0) return;
         f4 s0 = red[0][0][lane], s1 = f4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (CODES) s1 = red[0][1][lane];
+        if constexpr (!ZP) s1 = red[0][1][lane];
 #pragma unroll
         for (int w = 1; w < NW; ++w) {
             s0 += red[w][0][lane];
-            if constexpr (CODES) s1 += red[w][1][lane];
+            if constexpr (!ZP) s1 += red[w][1][lane];
         }
-        if constexpr (CODES) accl[0][0] = s0 * p.sk + s1;
+        if constexpr (!ZP) accl[0][0] = s0 * p.sk + s1;
         else acc[0][0] = s0;
     }
 
@@ -315,7 +399,7 @@ __global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int64_t t = tok0 + tt * 16 + g * 4 + e;
-                if constexpr (CODES) {
+                if constexpr (!ZP) {
                     if (row < p.rows && t < p.T) {
                         float v = p.gs * lacc[rg][tt][e];
                         if (p.bias) v += p.bias[row];
@@ -323,9 +407,10 @@ __global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
                         else reinterpret_cast<float*>(p.y)[t * p.ldy + row] = v;
                     }
                 } else if constexpr (KSPLIT) {  // this workgroup's partial z, every element written
-                    p.ozp[((int64_t)blockIdx.y * 16 + t) * p.r32 + row] = acc[rg][tt][e];
+                    // (code rows r .. r32 are clamped to row r - 1, not zero as fp16 rows are there)
+                    p.ozp[((int64_t)blockIdx.y * 16 + t) * p.r32 + row] = CODES && row >= p.rows ? 0.f : acc[rg][tt][e];
                 } else if (row < rows_out) {  // the whole [token rows][r32] buffers (zeros past T, r)
-                    const float v = acc[rg][tt][e];
+                    const float v = CODES && row >= p.rows ? 0.f : acc[rg][tt][e] * p.zscale;  // once, before the split
                     const _Float16 hi = (_Float16)v;
                     p.oh[t * p.r32 + row] = hi;
                     p.ol[t * p.r32 + row] = (_Float16)(v - (float)hi);
@@ -343,31 +428,59 @@ inline bool al16(const void* ptr, int64_t ld_elems) {
     return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld_elems % 8 == 0;
 }
 
-template <int WT>
+template <int WT, int LB, bool ZP>
 void launch(const LinP& p, hipStream_t s) {
-    constexpr bool CODES = WT != 16;
-    const int64_t groups = ceil_div(CODES ? p.rows : p.r32, 16);
+    const int64_t groups = ceil_div(ZP ? p.r32 : p.rows, 16);
     if (p.T <= kDecodeMax) {
-        constexpr int NW = CODES ? kDecodeWaves : kDecodeWavesZ;
-        const dim3 grid((unsigned)groups, CODES ? 1 : kDecodeSplitZ);
-        hipLaunchKernelGGL((linear_kernel<WT, 1, 1, NW, true>), grid, dim3(NW * 64), 0, s, p);
+        constexpr int NW = ZP ? kDecodeWavesZ : kDecodeWaves;
+        const dim3 grid((unsigned)groups, ZP ? kDecodeSplitZ : 1);
+        hipLaunchKernelGGL((linear_kernel<WT, LB, ZP, 1, 1, NW, true>), grid, dim3(NW * 64), 0, s, p);
     } else {
-        constexpr int NW = CODES ? 4 : 1, RG = CODES ? kPrefillGroups : 1;
+        constexpr int NW = ZP ? 1 : 4, RG = ZP ? 1 : kPrefillGroups;
         const dim3 grid((unsigned)ceil_div(groups, NW * RG), (unsigned)ceil_div(p.T, kPrefillTiles * 16));
-        hipLaunchKernelGGL((linear_kernel<WT, kPrefillTiles, RG, NW, false>), grid, dim3(NW * 64), 0, s, p);
+        hipLaunchKernelGGL((linear_kernel<WT, LB, ZP, kPrefillTiles, RG, NW, false>), grid, dim3(NW * 64), 0, s, p);
     }
 }
 
-int validate(const cq_linear_args* a) {
+template <int WT>
+void launch_layer(const LinP& p, int l_bits, hipStream_t s) {
+    if (l_bits == 2) launch<WT, 2, false>(p, s);
+    else if (l_bits == 4) launch<WT, 4, false>(p, s);
+    else launch<WT, 16, false>(p, s);
+}
+
+inline bool coded(int bits) { return bits == 2 || bits == 4; }
+inline float kmax(int bits) { return (float)((1 << (bits - 1)) - 1); }
+
+// one factor's codes: rows of `cols` codes in the inference layout, one finite scale >= 0
+int validate_factor(const char* name, int bits, const uint8_t* codes, int64_t stride, int64_t cols, float scale) {
+    CQ_REQUIRE(codes != nullptr, "cq_linear: null %s codes with %s bits = %d", name, name, bits);
+    CQ_REQUIRE((reinterpret_cast<uintptr_t>(codes) & 15) == 0 && stride % 16 == 0,
+               "cq_linear: %s codes and their row stride must be 16-byte aligned (inference layout)", name);
+    CQ_REQUIRE(stride >= (cols * bits + 7) / 8, "cq_linear: %s code row stride %lld < %lld bytes", name,
+               (long long)stride, (long long)((cols * bits + 7) / 8));
+    CQ_REQUIRE(std::isfinite(scale) && scale >= 0.f, "cq_linear: %s scale %g is not finite and >= 0", name, (double)scale);
+    return CQ_OK;
+}
+
+int validate(const cq_linear_packed_args* a) {
     CQ_REQUIRE(a != nullptr, "cq_linear: null args");
     CQ_REQUIRE(a->bits == 2 || a->bits == 4, "cq_linear: bits %d not in {2, 4}", a->bits);
+    CQ_REQUIRE((coded(a->l_bits) || a->l_bits == 16) && (coded(a->r_bits) || a->r_bits == 16),
+               "cq_linear: factor bits L %d / R %d not in {2, 4, 16}", a->l_bits, a->r_bits);
+    const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
     CQ_REQUIRE(a->tokens >= 0 && a->m > 0 && a->n > 0 && a->r >= 0, "cq_linear: bad shape tokens=%lld m=%lld n=%lld r=%lld",
                (long long)a->tokens, (long long)a->m, (long long)a->n, (long long)a->r);
     CQ_REQUIRE(a->r <= CQ_LINEAR_MAX_RANK, "cq_linear: rank %lld > %d", (long long)a->r, CQ_LINEAR_MAX_RANK);
     CQ_REQUIRE(a->tokens <= (int64_t)65535 * 64 && a->m <= ((int64_t)1 << 31), "cq_linear: shape too large");
     CQ_REQUIRE(a->y_dtype == CQ_F32 || a->y_dtype == CQ_F16, "cq_linear: y dtype %d not fp32 / fp16", a->y_dtype);
     CQ_REQUIRE(a->x && a->codes && a->y, "cq_linear: null x / codes / y");
-    CQ_REQUIRE(a->r == 0 || (a->L && a->R), "cq_linear: null L / R with r = %lld", (long long)a->r);
+    CQ_REQUIRE(a->r == 0 || ((lcoded || a->L) && (rcoded || a->R)), "cq_linear: null L / R with r = %lld",
+               (long long)a->r);
+    if (lcoded)
+        if (int st = validate_factor("L", a->l_bits, a->L_codes, a->l_code_stride, a->r, a->lscale)) return st;
+    if (rcoded)
+        if (int st = validate_factor("R", a->r_bits, a->R_codes, a->r_code_stride, a->n, a->rscale)) return st;
     CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->codes) & 15) == 0 && a->code_stride % 16 == 0,
                "cq_linear: codes and their row stride must be 16-byte aligned (inference layout)");
     CQ_REQUIRE(a->code_stride >= (a->n * a->bits + 7) / 8, "cq_linear: code row stride %lld < %lld bytes",
@@ -378,31 +491,44 @@ int validate(const cq_linear_args* a) {
     CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->y) & (a->y_dtype == CQ_F16 ? 1 : 3)) == 0 &&
                    (reinterpret_cast<uintptr_t>(a->bias) & 3) == 0,
                "cq_linear: misaligned y / bias pointer");
-    CQ_REQUIRE(a->ldx >= a->n && a->ldy >= a->m && (a->r == 0 || (a->ldl >= a->r && a->ldr >= a->n)),
+    CQ_REQUIRE(a->ldx >= a->n && a->ldy >= a->m &&
+                   (a->r == 0 || ((lcoded || a->ldl >= a->r) && (rcoded || a->ldr >= a->n))),
                "cq_linear: leading dimension smaller than the row");
     return CQ_OK;
 }
 
-}  // namespace
-}  // namespace cq
-
-using namespace cq;
-
-extern "C" size_t cq_linear_workspace(const cq_linear_args* a) {
-    if (a == nullptr || a->r <= 0 || a->tokens <= 0) return 0;
-    if (a->tokens <= kDecodeMax) return (size_t)(kDecodeSplitZ * 16 * r32_of(a->r)) * sizeof(float);
-    return (size_t)(2 * token_rows(a->tokens) * r32_of(a->r)) * sizeof(uint16_t);
+size_t workspace_bytes(int64_t tokens, int64_t r) {
+    if (r <= 0 || tokens <= 0) return 0;
+    if (tokens <= kDecodeMax) return (size_t)(kDecodeSplitZ * 16 * r32_of(r)) * sizeof(float);
+    return (size_t)(2 * token_rows(tokens) * r32_of(r)) * sizeof(uint16_t);
 }
 
-extern "C" int cq_linear_forward(const cq_linear_args* a, void* ws, size_t ws_bytes, void* stream) {
+// cq_linear_args is the leading part of cq_linear_packed_args: the same layer with fp16 factors
+cq_linear_packed_args with_fp16_factors(const cq_linear_args* a) {
+    cq_linear_packed_args b{};
+    b.x = a->x, b.ldx = a->ldx;
+    b.tokens = a->tokens, b.m = a->m, b.n = a->n, b.r = a->r;
+    b.bits = a->bits;
+    b.codes = a->codes, b.code_stride = a->code_stride;
+    b.qscale = a->qscale, b.gscale = a->gscale;
+    b.L = a->L, b.ldl = a->ldl;
+    b.R = a->R, b.ldr = a->ldr;
+    b.bias = a->bias;
+    b.y = a->y, b.y_dtype = a->y_dtype, b.ldy = a->ldy;
+    b.l_bits = b.r_bits = 16;
+    return b;
+}
+
+int forward(const cq_linear_packed_args* a, void* ws, size_t ws_bytes, void* stream, const char* who) {
     if (int st = validate(a)) return st;
     if (a->tokens == 0) return CQ_OK;
-    const size_t need = cq_linear_workspace(a);
+    const size_t need = workspace_bytes(a->tokens, a->r);
     if (need) {
         CQ_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
-                   "cq_linear_forward: workspace must be 16-byte aligned");
-        if (ws_bytes < need) return set_error(CQ_EWORKSPACE, "cq_linear_forward: workspace %zu < %zu", ws_bytes, need);
+                   "%s: workspace must be 16-byte aligned", who);
+        if (ws_bytes < need) return set_error(CQ_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
     }
+    const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
     hipStream_t s = as_stream(stream);
     LinP p{};
     p.x = reinterpret_cast<const _Float16*>(a->x);
@@ -414,35 +540,76 @@ extern "C" int cq_linear_forward(const cq_linear_args* a, void* ws, size_t ws_by
     p.r32 = r32_of(a->r);
     _Float16* zh = reinterpret_cast<_Float16*>(ws);
     _Float16* zl = zh ? zh + token_rows(a->tokens) * p.r32 : nullptr;
+    // the coded factors' scale / k (one fp32 division each), multiplied in fp32
+    p.zscale = 1.0f;
+    if (lcoded) p.zscale = a->lscale / kmax(a->l_bits);
+    if (rcoded) p.zscale = lcoded ? p.zscale * (a->rscale / kmax(a->r_bits)) : a->rscale / kmax(a->r_bits);
     if (a->r > 0) {  // z = x R^T as split halves
         LinP z = p;
         z.rows = a->r;
-        z.w = reinterpret_cast<const uint8_t*>(a->R);
-        z.wstride = a->ldr;
-        z.w_al = al16(a->R, a->ldr);
         z.ozp = reinterpret_cast<float*>(ws);
         z.oh = zh;
         z.ol = zl;
-        launch<16>(z, s);
-        if (int st = check_launch("cq_linear_forward (z)")) return st;
+        if (rcoded) {
+            z.w = a->R_codes;
+            z.wstride = a->r_code_stride;
+            if (a->r_bits == 2) launch<2, 16, true>(z, s);
+            else launch<4, 16, true>(z, s);
+        } else {
+            z.w = reinterpret_cast<const uint8_t*>(a->R);
+            z.wstride = a->ldr;
+            z.w_al = al16(a->R, a->ldr);
+            launch<16, 16, true>(z, s);
+        }
+        char what[64];
+        snprintf(what, sizeof what, "%s (z)", who);
+        if (int st = check_launch(what)) return st;
     }
     p.rows = a->m;
     p.w = a->codes;
     p.wstride = a->code_stride;
-    p.L = reinterpret_cast<const _Float16*>(a->L);
-    p.ldl = a->ldl;
-    p.l_al = a->r > 0 && al16(a->L, a->ldl);
+    if (lcoded) {
+        p.lc = a->L_codes;
+        p.lcstride = a->l_code_stride;
+    } else {
+        p.L = reinterpret_cast<const _Float16*>(a->L);
+        p.ldl = a->ldl;
+        p.l_al = a->r > 0 && al16(a->L, a->ldl);
+    }
     p.zp = reinterpret_cast<const float*>(ws);
     p.zh = zh;
     p.zl = zl;
-    const float k = (float)((1 << (a->bits - 1)) - 1);
-    p.sk = a->qscale / k;
+    p.sk = a->qscale / kmax(a->bits);
     p.gs = a->gscale;
     p.bias = a->bias;
     p.y = a->y;
     p.y_f16 = a->y_dtype == CQ_F16;
     p.ldy = a->ldy;
-    if (a->bits == 2) launch<2>(p, s);
-    else launch<4>(p, s);
-    return check_launch("cq_linear_forward");
+    const int l_bits = lcoded ? a->l_bits : 16;
+    if (a->bits == 2) launch_layer<2>(p, l_bits, s);
+    else launch_layer<4>(p, l_bits, s);
+    return check_launch(who);
+}
+
+}  // namespace
+}  // namespace cq
+
+using namespace cq;
+
+extern "C" size_t cq_linear_workspace(const cq_linear_args* a) {
+    return a == nullptr ? 0 : workspace_bytes(a->tokens, a->r);
+}
+
+extern "C" size_t cq_linear_packed_workspace(const cq_linear_packed_args* a) {
+    return a == nullptr ? 0 : workspace_bytes(a->tokens, a->r);
+}
+
+extern "C" int cq_linear_forward(const cq_linear_args* a, void* ws, size_t ws_bytes, void* stream) {
+    CQ_REQUIRE(a != nullptr, "cq_linear: null args");
+    const cq_linear_packed_args b = with_fp16_factors(a);
+    return forward(&b, ws, ws_bytes, stream, "cq_linear_forward");
+}
+
+extern "C" int cq_linear_packed_forward(const cq_linear_packed_args* a, void* ws, size_t ws_bytes, void* stream) {
+    return forward(a, ws, ws_bytes, stream, "cq_linear_packed_forward");
 }

@@ -1201,6 +1201,8 @@ class CalderaEngine:
             out = [self._cut_columns(d, m, n, n_true) for d in out]
             for lp in self.last_packed:  # packed codes stay in the padded (m, n + pad) grid
                 lp["R"] = lp["R"][:, :n_true]
+                if "R_codes" in lp:
+                    lp["R_codes"] = lp["R_codes"][:, :n_true]
                 lp["n_padded"] = n
         return out
 
@@ -1278,6 +1280,16 @@ class CalderaEngine:
         self.last_packed = [dict(codes=best.Qc[b], Q_scale=qs[b], L=best.L[b], R=best.R[b], global_scale=gsl[b],
                                  errors={k: v[b] for k, v in errors.items()})
                             for b in range(B)]
+        if torch.is_tensor(best.L_idxs):
+            # uniform L, R with a kept iterate: the factors' integer codes, (m, r) and (r, n), and
+            # their scales -- L = (L_codes / k_L) L_scale exactly, so a consumer need not store
+            # the factors dense (views of the kept codes: L_idxs is in L^T order)
+            r = best.L.shape[2]
+            ls, rs = best.L_scale.tolist(), best.R_scale.tolist()
+            for b, lp in enumerate(self.last_packed):
+                if best.flag_LR[b]:
+                    lp.update(L_codes=best.L_idxs[b].view(r, m).t(), R_codes=best.R_idxs[b].view(r, n),
+                              L_scale=ls[b], R_scale=rs[b])
         codes_all = Qall = None
         if not best.dense_q and any(best.flag_Q):
             work, res = spare

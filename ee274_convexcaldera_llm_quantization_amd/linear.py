@@ -7,6 +7,12 @@ weight `model.apply_caldera_quantization` writes back by default holds 32 MB.
 The codes are kept in the inference layout of include/caldera_hip.h (rows padded to 16
 bytes with code 0); the storage layout of `engine.last_packed` / `sharding.MatrixResult` is
 converted once at construction with torch ops (not on the hot path).
+
+CALDERA's own configurations quantise L and R too (2/4-bit uniform, one scale each).  Such a
+factor is kept as its packed codes in the same inference layout (`L_codes`: out_features rows
+of rank codes, `R_codes`: rank rows of in_features codes) with `lscale` / `rscale`, has no
+fp16 buffer, and is applied by cq_linear_packed_forward: a quarter (4-bit) or an eighth
+(2-bit) of the fp16 factor's bytes, and no second rounding of (c / k) s to fp16.
 """
 from __future__ import annotations
 
@@ -24,6 +30,11 @@ def _k(bits: int) -> int:
 def _check_bits(bits):
     if bits not in SUPPORTED_BITS:
         raise ValueError(f"CalderaLinear: Q bits {bits} not in {SUPPORTED_BITS} (no packed codes)")
+
+
+def _check_factor_bits(bits, what):
+    if bits not in SUPPORTED_BITS:
+        raise ValueError(f"CalderaLinear: {what} bits {bits} not in {SUPPORTED_BITS} (no packed factor codes)")
 
 
 def row_bytes(n: int, bits: int) -> int:
@@ -57,33 +68,65 @@ def unpack_bytes(b: torch.Tensor, bits: int) -> torch.Tensor:
 class CalderaLinear(torch.nn.Module):
     """One compressed layer.  Buffers (so `state_dict()` carries them): `codes` (out_features,
     row_bytes) uint8 inference layout, `L` (out_features, rank) and `R` (rank, in_features) fp16,
-    `bias` (out_features,) fp32 or None.  Plain attributes: qscale, gscale, bits, in_features,
-    out_features, rank (also carried as the state dict's extra state).
+    `bias` (out_features,) fp32 or None.  A factor given by its codes has `L_codes`
+    (out_features, row_bytes(rank, L_bits)) resp. `R_codes` (rank, row_bytes(in_features, R_bits))
+    uint8 instead, with `lscale` / `rscale`, and its fp16 buffer is None.  Plain attributes:
+    qscale, gscale, bits, in_features, out_features, rank, lscale, rscale, L_bits, R_bits (16 =
+    fp16 factor), also carried as the state dict's extra state.
 
     forward(x): any leading dimensions, last = in_features, on a HIP device (there is no CPU
     path).  x is cast to fp16 and the result returned in x's dtype: bf16 activations beyond
     fp16's range (|x| > 65504) would overflow, as would |x R^T|."""
 
-    def __init__(self, codes, L, R, bias=None, *, qscale, gscale, bits, in_features, out_features):
+    def __init__(self, codes, L, R, bias=None, *, qscale, gscale, bits, in_features, out_features, L_codes=None,
+                 R_codes=None):
+        """L_codes / R_codes: (uint8 inference-layout codes, scale, bits) of a coded factor,
+        whose fp16 L / R is then None."""
         super().__init__()
         _check_bits(bits)
         m, n = int(out_features), int(in_features)
         if codes.dtype != torch.uint8 or tuple(codes.shape) != (m, row_bytes(n, bits)):
             raise ValueError(f"CalderaLinear: codes must be uint8 {(m, row_bytes(n, bits))} (inference layout), "
                              f"got {codes.dtype} {tuple(codes.shape)}")
-        r = 0 if L is None else int(L.shape[1])
+        if (L_codes is not None and L is not None) or (R_codes is not None and R is not None):
+            raise ValueError("CalderaLinear: a factor is given by its codes or as fp16, not both")
+        if (L is None and L_codes is None) != (R is None and R_codes is None):
+            raise ValueError("CalderaLinear: one factor without the other")
+        r = int(R_codes[0].shape[0]) if R_codes is not None else 0 if R is None else int(R.shape[0])
         if r > K.LINEAR_MAX_RANK:
             raise ValueError(f"CalderaLinear: rank {r} > {K.LINEAR_MAX_RANK}")
         dev = codes.device
         if r == 0:
-            L, R = torch.zeros((m, 0), device=dev), torch.zeros((0, n), device=dev)
-        if tuple(L.shape) != (m, r) or tuple(R.shape) != (r, n):
-            raise ValueError(f"CalderaLinear: L {tuple(L.shape)} / R {tuple(R.shape)} do not fit {(m, r)} / {(r, n)}")
+            L, R, L_codes, R_codes = torch.zeros((m, 0), device=dev), torch.zeros((0, n), device=dev), None, None
         self.in_features, self.out_features, self.rank, self.bits = n, m, r, int(bits)
         self.qscale, self.gscale = float(qscale), float(gscale)
+        self.lscale = self.rscale = 1.0
+        self.L_bits = self.R_bits = 16
+        packed = {}
+        for what, spec, fp, shape in (("L", L_codes, L, (m, r)), ("R", R_codes, R, (r, n))):
+            if spec is None:
+                if tuple(fp.shape) != shape:
+                    raise ValueError(f"CalderaLinear: {what} {tuple(fp.shape)} does not fit {shape} (L {(m, r)} / "
+                                     f"R {(r, n)})")
+                packed[what] = None
+                continue
+            t, scale, fbits = spec
+            _check_factor_bits(fbits, what)
+            want = (shape[0], row_bytes(shape[1], fbits))
+            if t.dtype != torch.uint8 or tuple(t.shape) != want:
+                raise ValueError(f"CalderaLinear: {what}_codes must be uint8 {want} (inference layout), got "
+                                 f"{t.dtype} {tuple(t.shape)}")
+            scale = float(scale)
+            if not (scale >= 0.0 and scale != float("inf")):
+                raise ValueError(f"CalderaLinear: {what} scale {scale} is not finite and >= 0")
+            setattr(self, what.lower() + "scale", scale)
+            setattr(self, what + "_bits", int(fbits))
+            packed[what] = t.detach().contiguous()
         self.register_buffer("codes", codes.contiguous())
-        self.register_buffer("L", L.detach().to(torch.float16).contiguous())
-        self.register_buffer("R", R.detach().to(torch.float16).contiguous())
+        self.register_buffer("L", None if packed["L"] is not None else L.detach().to(torch.float16).contiguous())
+        self.register_buffer("R", None if packed["R"] is not None else R.detach().to(torch.float16).contiguous())
+        self.register_buffer("L_codes", packed["L"])
+        self.register_buffer("R_codes", packed["R"])
         self.register_buffer("bias", None if bias is None else bias.detach().to(torch.float32).contiguous())
 
     def _apply(self, fn, *args, **kwargs):
@@ -97,12 +140,25 @@ class CalderaLinear(torch.nn.Module):
 
     # ------------------------------------------------------------------ constructors
     @classmethod
-    def from_codes(cls, c, L, R, bias=None, *, qscale, gscale, bits):
-        """From (m, n) integer codes in [-k, k]."""
+    def from_codes(cls, c, L, R, bias=None, *, qscale, gscale, bits, L_codes=None, R_codes=None):
+        """From (m, n) integer codes in [-k, k].  L_codes = (cL, sL, bits) / R_codes = (cR, sR,
+        bits): a factor as (m, r) resp. (r, n) integer codes in [-k, k] with its scale, i.e.
+        L = (cL / k) sL; its fp16 L / R is then None."""
         _check_bits(bits)
         m, n = c.shape
+
+        def packed(spec, what):
+            if spec is None:
+                return None
+            cf, scale, fbits = spec
+            _check_factor_bits(fbits, what)
+            if cf.dim() != 2 or cf.dtype.is_floating_point or int(cf.abs().max() if cf.numel() else 0) > _k(fbits):
+                raise ValueError(f"CalderaLinear.from_codes: {what} codes must be an integer matrix in "
+                                 f"[-{_k(fbits)}, {_k(fbits)}]")
+            return pack_rows(cf, fbits), scale, fbits
+
         return cls(pack_rows(c, bits), L, R, bias, qscale=qscale, gscale=gscale, bits=bits, in_features=n,
-                   out_features=m)
+                   out_features=m, L_codes=packed(L_codes, "L"), R_codes=packed(R_codes, "R"))
 
     @classmethod
     def from_result(cls, res, bias=None):
@@ -116,14 +172,26 @@ class CalderaLinear(torch.nn.Module):
         if flat.dtype != torch.uint8 or flat.numel() != nbytes or (m * npad * res.Q_bits) % 8:
             raise ValueError(f"CalderaLinear.from_result: {res.name}: codes are not {nbytes} packed bytes")
         c = unpack_bytes(flat, res.Q_bits).view(m, npad)[:, :n]
-        return cls.from_codes(c, res.L, res.R[:, :n], bias, qscale=res.Q_scale, gscale=res.global_scale,
-                              bits=res.Q_bits)
+        # a coded factor travels in the inference layout already (its fp32 array has zero rows)
+        Lc = getattr(res, "L_codes", None)
+        Rc = getattr(res, "R_codes", None)
+        return cls(pack_rows(c, res.Q_bits), None if Lc is not None else res.L,
+                   None if Rc is not None else res.R[:, :n], bias, qscale=res.Q_scale, gscale=res.global_scale,
+                   bits=res.Q_bits, in_features=n, out_features=m,
+                   L_codes=None if Lc is None else (Lc, res.L_scale, res.L_bits),
+                   R_codes=None if Rc is None else (Rc, res.R_scale, res.R_bits))
 
     @classmethod
-    def from_decomposition(cls, dec, Q_bits, bias=None):
+    def from_decomposition(cls, dec, Q_bits, bias=None, *, L_bits=None, R_bits=None):
         """From a CalderaDecomposition with uniform Q: packs `Q_idxs` (the reference's int codes,
-        (1, m n)) with `Q_scale`; L, R are rounded to fp16."""
+        (1, m n)) with `Q_scale`; L, R are rounded to fp16.  L_bits / R_bits (2 | 4; None: fp16):
+        that factor was quantised uniformly at those bits and is kept as its codes instead --
+        `L_idxs` ((1, r m), in L^T order) with `L_scale`, `R_idxs` ((1, r n)) with `R_scale`,
+        each one scale."""
         _check_bits(Q_bits)
+        for what, fbits in (("L", L_bits), ("R", R_bits)):
+            if fbits is not None:
+                _check_factor_bits(fbits, what)
         if dec.Q_idxs is None or dec.Q is None:
             raise ValueError("CalderaLinear.from_decomposition: the decomposition has no Q")
         qs = dec.Q_scale
@@ -135,44 +203,83 @@ class CalderaLinear(torch.nn.Module):
         if dec.Q_idxs.numel() != m * n:
             raise ValueError("CalderaLinear.from_decomposition: Q_idxs does not hold m x n codes")
         qscale = float(qs.reshape(-1)[0]) if torch.is_tensor(qs) else float(qs)
-        return cls.from_codes(dec.Q_idxs.reshape(m, n), dec.L, dec.R, bias, qscale=qscale,
-                              gscale=float(dec.global_scale), bits=Q_bits)
+        r = dec.R.shape[0]
+
+        def factor(what, fbits, rows, cols, transposed):
+            if fbits is None:
+                return None
+            idxs, scale = getattr(dec, what + "_idxs", None), getattr(dec, what + "_scale", None)
+            if (not torch.is_tensor(idxs) or idxs.dtype != torch.int8 or isinstance(scale, (tuple, list, dict))
+                    or (torch.is_tensor(scale) and scale.numel() != 1)):
+                raise ValueError(f"CalderaLinear.from_decomposition: {what} is not uniformly quantised with one "
+                                 "scale (nf / bbint codebooks have no packed codes)")
+            if idxs.numel() != rows * cols:
+                raise ValueError(f"CalderaLinear.from_decomposition: {what}_idxs does not hold {rows} x {cols} codes")
+            cf = idxs.reshape(cols, rows).t() if transposed else idxs.reshape(rows, cols)
+            return cf, (float(scale.reshape(-1)[0]) if torch.is_tensor(scale) else float(scale)), fbits
+
+        Lc = factor("L", L_bits, m, r, True)
+        Rc = factor("R", R_bits, r, n, False)
+        return cls.from_codes(dec.Q_idxs.reshape(m, n), None if Lc else dec.L, None if Rc else dec.R, bias,
+                              qscale=qscale, gscale=float(dec.global_scale), bits=Q_bits, L_codes=Lc, R_codes=Rc)
 
     def to_result(self, name: str):
         """The layer as a `sharding.MatrixResult` (storage layout: codes on the (m, n padded to
-        4) grid, fp32 factors), e.g. for `sharding.save_results`; `from_result` inverts it."""
+        4) grid, fp32 factors; a coded factor as its codes, its fp32 array with zero rows), e.g.
+        for `sharding.save_results`; `from_result` inverts it."""
         from .sharding import MatrixResult
         m, n, per = self.out_features, self.in_features, 8 // self.bits
         npad = n + (-n) % 4
         codes = self.codes[:, :npad // per].contiguous().reshape(-1)
         extra = {"n_padded": npad} if npad != n else {}
-        return MatrixResult(name, m, n, self.rank, self.bits, codes, self.qscale, self.L.float(), self.R.float(),
-                            self.gscale, {}, extra)
+        dev = self.codes.device
+        # a coded factor: its codes as they are (inference layout) and an fp32 array of zero rows
+        L = self.L.float() if self.L_codes is None else torch.zeros((0, self.rank), device=dev)
+        R = self.R.float() if self.R_codes is None else torch.zeros((0, n), device=dev)
+        return MatrixResult(name, m, n, self.rank, self.bits, codes, self.qscale, L, R, self.gscale, {}, extra,
+                            L_codes=self.L_codes, R_codes=self.R_codes, L_scale=self.lscale, R_scale=self.rscale,
+                            L_bits=self.L_bits, R_bits=self.R_bits)
 
     # ------------------------------------------------------------------ state
     def get_extra_state(self):
         return {"qscale": self.qscale, "gscale": self.gscale, "bits": self.bits, "in_features": self.in_features,
-                "out_features": self.out_features, "rank": self.rank}
+                "out_features": self.out_features, "rank": self.rank, "lscale": self.lscale, "rscale": self.rscale,
+                "L_bits": self.L_bits, "R_bits": self.R_bits}
 
     def set_extra_state(self, state):
+        """A state saved before factor codes existed has no lscale / rscale / L_bits / R_bits: the
+        layer keeps its own (an fp16-factor layer's defaults)."""
         for key, v in state.items():
             setattr(self, key, v)
 
     def extra_repr(self):
+        fac = "" if self.L_bits == self.R_bits == 16 else f", L_bits={self.L_bits}, R_bits={self.R_bits}"
         return (f"in_features={self.in_features}, out_features={self.out_features}, bits={self.bits}, "
-                f"rank={self.rank}, bias={self.bias is not None}")
+                f"rank={self.rank}{fac}, bias={self.bias is not None}")
 
     def packed_bytes(self) -> int:
-        """Bytes a forward streams for the weights: codes + L + R (+ bias)."""
-        return sum(t.numel() * t.element_size() for t in (self.codes, self.L, self.R, self.bias) if t is not None)
+        """Bytes a forward streams for the weights: codes + L + R (fp16 or codes) (+ bias)."""
+        return sum(t.numel() * t.element_size()
+                   for t in (self.codes, self.L, self.R, self.L_codes, self.R_codes, self.bias) if t is not None)
+
+    def factors(self):
+        """(L, R) as fp32 (out_features, rank) / (rank, in_features): an fp16 factor as stored, a
+        coded one as c (scale / k) with the fp32 division the kernel makes."""
+        def deq(codes, scale, bits, cols):
+            c = unpack_bytes(codes, bits)[:, :cols].float()
+            return c * (torch.tensor(scale, dtype=torch.float32) / torch.tensor(float(_k(bits)), dtype=torch.float32))
+        L = self.L.float() if self.L_codes is None else deq(self.L_codes, self.lscale, self.L_bits, self.rank)
+        R = self.R.float() if self.R_codes is None else deq(self.R_codes, self.rscale, self.R_bits, self.in_features)
+        return L, R
 
     def dense_weight(self) -> torch.Tensor:
         """gs (Q + L R) as a dense fp32 (out_features, in_features) tensor, by torch ops (checks
-        and baselines only): Q = c (s / k)."""
+        and baselines only): Q = c (s / k), a coded factor likewise."""
         k = _k(self.bits)
         c = unpack_bytes(self.codes, self.bits)[:, :self.in_features].float()
         sk = (torch.tensor(self.qscale, dtype=torch.float32) / torch.tensor(float(k), dtype=torch.float32)).item()
-        return self.gscale * (c * sk + self.L.float() @ self.R.float())
+        L, R = self.factors()
+        return self.gscale * (c * sk + L @ R)
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -185,7 +292,14 @@ class CalderaLinear(torch.nn.Module):
             x2 = x2.contiguous()
         ydt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
         y = torch.empty((x2.shape[0], self.out_features), dtype=ydt, device=x.device)
-        K.linear_forward(x2, self.codes, self.qscale, self.gscale, self.L if self.rank else None,
-                         self.R if self.rank else None, self.bias, y, m=self.out_features, n=self.in_features,
-                         bits=self.bits)
+        if self.rank and (self.L_codes is not None or self.R_codes is not None):
+            K.linear_packed_forward(
+                x2, self.codes, self.qscale, self.gscale, self.L, self.R, self.bias, y, m=self.out_features,
+                n=self.in_features, bits=self.bits, r=self.rank,
+                L_codes=None if self.L_codes is None else (self.L_codes, self.lscale, self.L_bits),
+                R_codes=None if self.R_codes is None else (self.R_codes, self.rscale, self.R_bits))
+        else:
+            K.linear_forward(x2, self.codes, self.qscale, self.gscale, self.L if self.rank else None,
+                             self.R if self.rank else None, self.bias, y, m=self.out_features, n=self.in_features,
+                             bits=self.bits)
         return y.to(x.dtype).reshape(*x.shape[:-1], self.out_features)

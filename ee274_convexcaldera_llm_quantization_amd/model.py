@@ -185,7 +185,7 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                                scale_W: bool = False, hadamard: bool = False, device="cuda",
                                max_batch: int = 64, keep_dtype: bool = True, decompose: Callable | None = None,
                                log: Callable | None = None, hadamard_gate: bool = False,
-                               packed: bool = False) -> QuantizationReport:
+                               packed: bool = False, packed_factors: bool = False) -> QuantizationReport:
     """main.py:135-251 on the MI355X engine.
 
     hessians: {module name: diagonal (n,) or dense (n, n)} — `Hall` (a missing name raises
@@ -207,6 +207,11 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
       Q + L R of the scaled W without its global scale, while a packed layer applies
       gs (Q + L R), so the two would be different models and the gate would judge a weight
       the layer does not apply.  Either combination raises ValueError.
+    packed_factors: with packed=True, keep L and R as their packed 2/4-bit codes too (applied
+      by cq_linear_packed_forward) instead of fp16: a quarter or an eighth of the factors'
+      bytes and no second rounding.  Needs packed=True, the uniform LR quantiser
+      (`quant_factory_LR.method`) and L_bits, R_bits in {2, 4}; anything else raises ValueError.
+      The default keeps fp16 factors.
     Returns the QuantizationReport (counters + per-layer outcomes)."""
     qp = quant_params if quant_params is not None else driver_params()
     if packed and hadamard:
@@ -214,6 +219,16 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
     if packed and scale_W:
         raise ValueError("apply_caldera_quantization: packed=True cannot be combined with scale_W=True (the gate "
                          "and the write-back use Q + L R without the global scale; the packed layer applies it)")
+    if packed_factors:
+        if not packed:
+            raise ValueError("apply_caldera_quantization: packed_factors=True needs packed=True")
+        method = str(getattr(getattr(qp, "quant_factory_LR", None), "method", "uniform")).lower()
+        if method != "uniform":
+            raise ValueError(f"apply_caldera_quantization: packed_factors=True needs the uniform LR quantiser, got "
+                             f"{method!r}: codebook factors have no packed codes")
+        if getattr(qp, "L_bits", None) not in (2, 4) or getattr(qp, "R_bits", None) not in (2, 4):
+            raise ValueError(f"apply_caldera_quantization: packed_factors=True needs L_bits / R_bits in (2, 4), got "
+                             f"{getattr(qp, 'L_bits', None)} / {getattr(qp, 'R_bits', None)}")
     say = log or (lambda *a: None)
     jobs, rep = select_layers(model, hessians, selection, say)
     # batches: same shape; every layer keeps its own Hessian (a list of per-matrix H, or one
@@ -264,7 +279,8 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                 ok = err <= error_threshold
                 if ok and packed:
                     from .linear import CalderaLinear
-                    lin = CalderaLinear.from_decomposition(dec, qp.Q_bits, bias=getattr(module, "bias", None))
+                    fbits = dict(L_bits=qp.L_bits, R_bits=qp.R_bits) if packed_factors else {}
+                    lin = CalderaLinear.from_decomposition(dec, qp.Q_bits, bias=getattr(module, "bias", None), **fbits)
                     _set_module(model, name, lin.to(W.device))
                     rep.quantized_param_count += W.numel()
                     say(f"Applied CALDERA (packed) to {name}.weight, shape: {tuple(W.shape)}")

@@ -71,6 +71,15 @@ class MatrixResult:
     global_scale: float
     errors: dict = field(default_factory=dict)
     extra: dict = field(default_factory=dict)  # e.g. n_padded: codes on an (m, n_padded) grid
+    # a 2/4-bit uniform factor kept as its codes (linear.CalderaLinear applies them as they are):
+    # uint8 inference layout of include/caldera_hip.h, (m, row bytes of r codes) / (r, row bytes
+    # of n codes), with one scale each; the factor's fp32 array (L / R) then has zero rows
+    L_codes: torch.Tensor | None = None
+    R_codes: torch.Tensor | None = None
+    L_scale: float = 1.0
+    R_scale: float = 1.0
+    L_bits: int = 16
+    R_bits: int = 16
 
 
 def _pad(nbytes: int) -> int:
@@ -91,7 +100,13 @@ def pack_results(results: list[MatrixResult], device=None) -> torch.Tensor:
         entry = {"name": r.name, "m": r.m, "n": r.n, "rank": r.rank, "Q_bits": r.Q_bits,
                  "Q_scale": float(r.Q_scale), "global_scale": float(r.global_scale),
                  "errors": r.errors, "extra": r.extra, "arrays": {}}
-        for key, t in (("codes", r.codes), ("L", r.L), ("R", r.R)):
+        arrays = [("codes", r.codes), ("L", r.L), ("R", r.R)]
+        # factor codes: optional arrays and meta keys (a payload without them reads as before)
+        for key, t, scale, bits in (("L", r.L_codes, r.L_scale, r.L_bits), ("R", r.R_codes, r.R_scale, r.R_bits)):
+            if t is not None:
+                arrays.append((key + "_codes", t))
+                entry[key + "_scale"], entry[key + "_bits"] = float(scale), int(bits)
+        for key, t in arrays:
             b = _as_bytes(t, dev)
             entry["arrays"][key] = {"offset": off, "nbytes": b.numel(), "dtype": str(t.dtype).split(".")[-1],
                                     "shape": list(t.shape)}
@@ -129,7 +144,9 @@ def unpack_results(buf: torch.Tensor) -> list[MatrixResult]:
             arrs[key] = buf[s:s + d["nbytes"]].view(getattr(torch, d["dtype"])).view(d["shape"])
         out.append(MatrixResult(e["name"], e["m"], e["n"], e["rank"], e["Q_bits"], arrs["codes"],
                                 e["Q_scale"], arrs["L"], arrs["R"], e["global_scale"], e["errors"],
-                                e.get("extra", {})))
+                                e.get("extra", {}), arrs.get("L_codes"), arrs.get("R_codes"),
+                                e.get("L_scale", 1.0), e.get("R_scale", 1.0), e.get("L_bits", 16),
+                                e.get("R_bits", 16)))
     return out
 
 
@@ -225,7 +242,13 @@ def _blob(results, dev):
         entry = {"name": r.name, "m": r.m, "n": r.n, "rank": r.rank, "Q_bits": r.Q_bits,
                  "Q_scale": float(r.Q_scale), "global_scale": float(r.global_scale),
                  "errors": r.errors, "extra": r.extra, "arrays": {}}
-        for key, t in (("codes", r.codes), ("L", r.L), ("R", r.R)):
+        arrays = [("codes", r.codes), ("L", r.L), ("R", r.R)]
+        # factor codes: optional arrays and meta keys (a payload without them reads as before)
+        for key, t, scale, bits in (("L", r.L_codes, r.L_scale, r.L_bits), ("R", r.R_codes, r.R_scale, r.R_bits)):
+            if t is not None:
+                arrays.append((key + "_codes", t))
+                entry[key + "_scale"], entry[key + "_bits"] = float(scale), int(bits)
+        for key, t in arrays:
             b = _as_bytes(t, dev)
             entry["arrays"][key] = {"offset": off, "nbytes": b.numel(), "dtype": str(t.dtype).split(".")[-1],
                                     "shape": list(t.shape)}

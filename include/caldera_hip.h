@@ -596,6 +596,54 @@ typedef struct cq_linear_args {
 size_t cq_linear_workspace(const cq_linear_args* a);
 int cq_linear_forward(const cq_linear_args* a, void* ws, size_t ws_bytes, void* stream);
 
+/* The same layer with low-bit factors (CALDERA's W ~ Q + L R with 2/4-bit uniform L, R, each
+ * with one scale): the factors are applied from their packed codes, never stored as fp16.
+ *
+ *   y[t, i]  = gs * ((s / k) * sum_j x[t, j] c[i, j] + sum_q z~[t, q] l[i, q]) (+ bias[i])
+ *   z~[t, q] = zscale * sum_j x[t, j] rho[q, j]
+ *
+ * l is the L codes (l_bits 2 | 4: integers in [-k_L, k_L], exact in fp16) or the fp16 L
+ * (l_bits 16), rho the R codes or the fp16 R (r_bits).  zscale is the fp32 product of the
+ * coded factors' scale / k -- lscale / k_L and rscale / k_R, each one fp32 division as s / k
+ * is -- and 1.0f when neither factor is coded.
+ *
+ * Contract, beside everything cq_linear_forward's holds to:
+ *   - both code sums accumulate unscaled in fp32; zscale is applied once, to the complete fp32
+ *     z sum (in decode: after the ordered add of the partial z), before it is split into fp16
+ *     halves, so the halves must stay in fp16 range while the unscaled sum need not
+ *     (n k_R |x| passes 65504 at n = 4096);
+ *   - the L product on integer codes continues on the scaled code accumulator;
+ *   - factor codes use the inference layout above: L_codes is m rows of r codes (row stride
+ *     l_code_stride bytes), R_codes r rows of n codes (r_code_stride), offset-binary,
+ *     MSB-first, 16-byte aligned rows, stride a multiple of 16, tail = code 0.  Pad columns
+ *     of the L codes (q >= r) and of the R codes (j >= n) contribute nothing whatever the
+ *     tails hold;
+ *   - a coded factor's fp16 pointer and leading dimension are ignored (may be NULL / 0), an
+ *     fp16 factor's code pointer, stride and scale likewise; with l_bits = r_bits = 16 the
+ *     result has the bits of cq_linear_forward, which is this entry with those values.
+ * Workspace: cq_linear_packed_workspace bytes (the same amount as cq_linear_workspace).
+ * CQ_EINVAL, beside cq_linear_forward's: l_bits / r_bits not in {2, 4, 16}; for a coded factor
+ * a NULL or not 16-byte aligned code pointer, a stride that is not a multiple of 16 or is
+ * below ceil(row codes * bits / 8), a scale that is not finite or is negative. */
+typedef struct cq_linear_packed_args {
+    const uint16_t* x; int64_t ldx;
+    int64_t tokens, m, n, r;
+    int bits;
+    const uint8_t* codes; int64_t code_stride;
+    float qscale, gscale;
+    const uint16_t* L; int64_t ldl;
+    const uint16_t* R; int64_t ldr;
+    const float* bias;
+    void* y; int y_dtype; int64_t ldy;
+    int l_bits, r_bits;
+    const uint8_t* L_codes; int64_t l_code_stride;
+    const uint8_t* R_codes; int64_t r_code_stride;
+    float lscale, rscale;
+} cq_linear_packed_args;
+
+size_t cq_linear_packed_workspace(const cq_linear_packed_args* a);
+int cq_linear_packed_forward(const cq_linear_packed_args* a, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
