@@ -185,6 +185,24 @@ _SIGS = {
     "cq_linear_forward": (c_int, [ctypes.POINTER(LinearArgs), c_vp, c_size, c_vp]),
     "cq_linear_packed_workspace": (c_size, [ctypes.POINTER(LinearPackedArgs)]),
     "cq_linear_packed_forward": (c_int, [ctypes.POINTER(LinearPackedArgs), c_vp, c_size, c_vp]),
+    # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
+    "cq_gemm_x3_skip": (c_int, [ctypes.POINTER(X3Args), c_vp]),
+    "cq_gram_f64_masked": (c_int, [c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_i64,
+                                   c_i64, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "cq_spd_whiten_masked": (c_int, [c_vp, c_i64, c_i64, c_double, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "cq_jacobi_eigh_masked": (c_int, [c_vp, c_i64, c_i64, c_int, c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_size, c_vp]),
+    "cq_jacobi_eigh_staged_masked": (c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_double, c_int, c_vp, c_vp, c_vp,
+                                             c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
+    "cq_extreme_eigs_masked": (c_int, [c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp]),
+    "cq_ritz_residual_masked": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_size,
+                                        c_vp]),
+    "cq_ritz_product_error_masked": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp,
+                                             c_size, c_vp]),
+    "cq_gemm_f32_masked": (c_int, [ctypes.POINTER(GemmArgs), c_vp, c_vp, c_size, c_vp]),
+    "cq_gemm_triu_split_masked": (c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_float, c_vp, c_vp]),
+    "cq_transpose_split_masked": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_float, c_vp, c_int, c_vp,
+                                          c_vp]),
 }
 EXPORTS = tuple(_SIGS)
 ABI_VERSION = 5  # include/caldera_hip.h CQ_ABI_VERSION
@@ -251,6 +269,15 @@ def _check(st: int, what: str):
 
 def _p(t: torch.Tensor | None):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _act(active: torch.Tensor | None, B: int):
+    """Pointer of a per-matrix mask (B,) int32 on the device (1 = live, 0 = left out), or NULL."""
+    if active is None:
+        return None
+    assert active.is_cuda and active.dtype == torch.int32 and active.is_contiguous() and active.numel() == B, \
+        "active must be a contiguous int32 device tensor of one entry per matrix"
+    return ctypes.c_void_p(active.data_ptr())
 
 
 def _stream(dev: torch.device):
@@ -481,9 +508,11 @@ def _mat(t: torch.Tensor):
 
 def gemm(A, B, *, ta=False, tb=False, C=None, alpha=1.0, beta=0.0, D=None, gamma=0.0,
          epi=EPI_LINEAR, absmax=None, w=None, err_out=None, alpha_v=None, beta_v=None,
-         gamma_v=None, batch=None, syrk=False, b_triu=False):
+         gamma_v=None, batch=None, syrk=False, b_triu=False, active=None):
     """Batched C = alpha op(A) op(B) + beta C + gamma D (or RESID / WERR epilogues).
-    b_triu: B (not transposed) is upper triangular -- its zero K slices are skipped."""
+    b_triu: B (not transposed) is upper triangular -- its zero K slices are skipped.
+    active (batch,) int32 (LINEAR epilogue, no syrk): matrices with active[b] == 0 are left out
+    (C[b] not written); None = all."""
     _require_hip(A, B, C, D, w)
     A_, lda, sa = _mat(A)
     B_, ldb, sb = _mat(B)
@@ -525,13 +554,18 @@ def gemm(A, B, *, ta=False, tb=False, C=None, alpha=1.0, beta=0.0, D=None, gamma
     dev = A.device
     nws = lib.cq_gemm_workspace(ctypes.byref(g))
     ws = workspace(nws, dev) if nws else None
+    if active is not None:
+        _check(lib.cq_gemm_f32_masked(ctypes.byref(g), _act(active, batch), _p(ws), 0 if ws is None else ws.numel(),
+                                      _stream(dev)), "cq_gemm_f32_masked")
+        return C
     _check(lib.cq_gemm_f32(ctypes.byref(g), _p(ws), 0 if ws is None else ws.numel(), _stream(dev)),
            "cq_gemm_f32")
     return C
 
 
-def gram_f64(A, B, *, ta=False, tb=False, out=None):
-    """C = op(A)^T op(B) style Gram: A is K x M (or M x K if ta), B is K x N (or N x K if tb)."""
+def gram_f64(A, B, *, ta=False, tb=False, out=None, active=None):
+    """C = op(A)^T op(B) style Gram: A is K x M (or M x K if ta), B is K x N (or N x K if tb).
+    active (batch,) int32: matrices with active[b] == 0 are left out (out[b] not written)."""
     _require_hip(A, B)
     A_, lda, sa = _mat(A)
     B_, ldb, sb = _mat(B)
@@ -543,12 +577,16 @@ def gram_f64(A, B, *, ta=False, tb=False, out=None):
         out = torch.empty((batch, M, N), dtype=torch.float64, device=A.device)
     lib = load()
     ws = workspace(lib.cq_gram_f64_workspace(M, N, K, batch), A.device)
+    if active is not None:
+        _check(lib.cq_gram_f64_masked(M, N, K, batch, _p(A_), int(ta), lda, sa, _p(B_), int(tb), ldb, sb, _p(out),
+                                      _act(active, batch), _p(ws), ws.numel(), _stream(A.device)), "cq_gram_f64_masked")
+        return out
     _check(lib.cq_gram_f64(M, N, K, batch, _p(A_), int(ta), lda, sa, _p(B_), int(tb), ldb, sb, _p(out),
                            _p(ws), ws.numel(), _stream(A.device)), "cq_gram_f64")
     return out
 
 
-def spd_whiten(S: torch.Tensor, rcond2: float = 1e-30):
+def spd_whiten(S: torch.Tensor, rcond2: float = 1e-30, active=None):
     """S (B, p, p) fp64 SPD (overwritten) -> (Wt32, Wt64, info) with Wt^T S Wt = I on the
     independent columns; pivots <= rcond2 * max diag are dropped (info = their count).
     Wt64 is S itself: the kernel leaves the fp64 Wt there (its Wt64 argument is scratch)."""
@@ -557,12 +595,17 @@ def spd_whiten(S: torch.Tensor, rcond2: float = 1e-30):
     Wt32 = torch.empty((B, p, p), dtype=torch.float32, device=S.device)
     scr = torch.empty((B, p, p), dtype=torch.float64, device=S.device)
     info = torch.empty(B, dtype=torch.int32, device=S.device)
+    if active is not None:  # masked-out matrices: S, Wt32 and info are left as they are
+        _check(load().cq_spd_whiten_masked(_p(S), p, B, float(rcond2), _p(Wt32), _p(scr), _p(info), _act(active, B),
+                                           _stream(S.device)), "cq_spd_whiten_masked")
+        return Wt32, S, info
     _check(load().cq_spd_whiten_rcond(_p(S), p, B, float(rcond2), _p(Wt32), _p(scr), _p(info),
                                       _stream(S.device)), "cq_spd_whiten_rcond")
     return Wt32, S, info
 
 
-def jacobi_eigh(A: torch.Tensor, max_sweeps: int = 30, tol: float = 1e-13, want64=False, want_vectors=True):
+def jacobi_eigh(A: torch.Tensor, max_sweeps: int = 30, tol: float = 1e-13, want64=False, want_vectors=True,
+                active=None):
     """A (B, p, p) fp64 symmetric (overwritten) -> (evals desc (B,p) fp64, V32, V64, sweeps);
     want_vectors=False: eigenvalues only (V32 = V64 = None; the p <= 192 register kernel then
     skips its eigenvector rotations)."""
@@ -575,18 +618,27 @@ def jacobi_eigh(A: torch.Tensor, max_sweeps: int = 30, tol: float = 1e-13, want6
     sw = torch.empty(B, dtype=torch.int32, device=A.device)
     lib = load()
     ws = workspace(lib.cq_jacobi_workspace(p, B), A.device)
+    if active is not None:  # masked-out matrices: no values, no vectors, sweeps 0
+        _check(lib.cq_jacobi_eigh_masked(_p(A), p, B, max_sweeps, tol, _p(ev), _p(V32), _p(V64), _p(sw),
+                                         _act(active, B), _p(ws), ws.numel(), _stream(A.device)),
+               "cq_jacobi_eigh_masked")
+        return ev, V32, V64, sw
     _check(lib.cq_jacobi_eigh(_p(A), p, B, max_sweeps, tol, _p(ev), _p(V32), _p(V64), _p(sw), _p(ws),
                               ws.numel(), _stream(A.device)), "cq_jacobi_eigh")
     return ev, V32, V64, sw
 
 
-def extreme_eigs(T: torch.Tensor, steps: int = 40) -> torch.Tensor:
+def extreme_eigs(T: torch.Tensor, steps: int = 40, active=None) -> torch.Tensor:
     """T (B, p, p) fp64 symmetric, p <= 512 (not overwritten) -> (B, 2) fp64 [largest,
     smallest eigenvalue] by Lanczos + bisection (cq_extreme_eigs): the filter bounds of the
     solver's cheap outer iterations without a values-only eigensolve."""
     _require_hip(T)
     B, p, _ = T.shape
     ends = torch.empty((B, 2), dtype=torch.float64, device=T.device)
+    if active is not None:
+        _check(load().cq_extreme_eigs_masked(_p(T), p, B, int(steps), _p(ends), _act(active, B), _stream(T.device)),
+               "cq_extreme_eigs_masked")
+        return ends
     _check(load().cq_extreme_eigs(_p(T), p, B, int(steps), _p(ends), _stream(T.device)), "cq_extreme_eigs")
     return ends
 
@@ -596,15 +648,24 @@ class BlockJacobi:
     only while the device count of unconverged matrices (read back by the caller) is nonzero."""
     BEGIN, SWEEPS, END = 1, 2, 4
 
-    def __init__(self, A: torch.Tensor, tol: float, want_vectors: bool = True):
+    def __init__(self, A: torch.Tensor, tol: float, want_vectors: bool = True, active=None):
         _require_hip(A)
         self.A, self.tol, self.want = A, tol, bool(want_vectors)
         self.B, self.p, _ = A.shape
+        # masked-out matrices are done from the begin stage on (never pending) and finish() leaves
+        # their values and vectors alone; the mask must hold its value until finish()
+        self.active = active
         self.ws = workspace(load().cq_jacobi_staged_workspace(self.p, self.B), A.device)
         self.pending = torch.zeros(1, dtype=torch.int32, device=A.device)
         self.swept = 0
 
     def _call(self, phase, nsweeps=0, ev=None, V32=None, sw=None):
+        if self.active is not None:
+            _check(load().cq_jacobi_eigh_staged_masked(_p(self.A), self.p, self.B, phase, nsweeps, self.tol,
+                                                       int(self.want), _p(ev), _p(V32), None, _p(sw), _p(self.pending),
+                                                       _act(self.active, self.B), _p(self.ws), self.ws.numel(),
+                                                       _stream(self.A.device)), "cq_jacobi_eigh_staged_masked")
+            return
         _check(load().cq_jacobi_eigh_staged(_p(self.A), self.p, self.B, phase, nsweeps, self.tol, int(self.want),
                                             _p(ev), _p(V32), None, _p(sw), _p(self.pending), _p(self.ws),
                                             self.ws.numel(), _stream(self.A.device)), "cq_jacobi_eigh_staged")
@@ -632,24 +693,32 @@ class BlockJacobi:
         return ev, V32, None, sw
 
 
-def ritz_residual(X, Z, theta, r):
+def ritz_residual(X, Z, theta, r, active=None):
     _require_hip(X, Z, theta)
     B, k, p = X.shape
     out = torch.empty(B, dtype=torch.float32, device=X.device)
     lib = load()
     ws = workspace(lib.cq_ritz_workspace(k, r, B), X.device)
+    if active is not None:
+        _check(lib.cq_ritz_residual_masked(_p(X), _p(Z), _p(theta), k, p, r, B, _p(out), _act(active, B), _p(ws),
+                                           ws.numel(), _stream(X.device)), "cq_ritz_residual_masked")
+        return out
     _check(lib.cq_ritz_residual(_p(X), _p(Z), _p(theta), k, p, r, B, _p(out), _p(ws), ws.numel(),
                                 _stream(X.device)), "cq_ritz_residual")
     return out
 
 
-def ritz_product_error(X, Z, theta, r, ysq):
+def ritz_product_error(X, Z, theta, r, ysq, active=None):
     """Per-matrix estimate of the relative error of the rank-r projection (cq_ritz_product_error)."""
     _require_hip(X, Z, theta, ysq)
     B, k, p = X.shape
     out = torch.empty(B, dtype=torch.float32, device=X.device)
     lib = load()
     ws = workspace(lib.cq_ritz_workspace(k, r, B), X.device)
+    if active is not None:
+        _check(lib.cq_ritz_product_error_masked(_p(X), _p(Z), _p(theta), k, p, r, B, _p(ysq), _p(out), _act(active, B),
+                                                _p(ws), ws.numel(), _stream(X.device)), "cq_ritz_product_error_masked")
+        return out
     _check(lib.cq_ritz_product_error(_p(X), _p(Z), _p(theta), k, p, r, B, _p(ysq), _p(out), _p(ws), ws.numel(),
                                      _stream(X.device)), "cq_ritz_product_error")
     return out
@@ -696,7 +765,7 @@ def sym_split_f16(G: torch.Tensor, x_scale: float, *, hi=None, lo=None, scale=No
 
 
 def transpose_split(X: torch.Tensor, *, out=None, hi=None, lo=None, scale: float | torch.Tensor = 1.0,
-                    blocked: bool = False):
+                    blocked: bool = False, active=None):
     """X (B, r, c) fp32 contiguous -> X^T (B, c, r) fp32 (out) and/or its fp16 split (hi, lo)
     scaled by `scale` (a float, or a (B,) fp32 tensor of per-matrix scales); hi without lo: the
     hi half alone (the operand of a single product)."""
@@ -705,6 +774,10 @@ def transpose_split(X: torch.Tensor, *, out=None, hi=None, lo=None, scale: float
     B, r, c = X.shape
     sv = scale if torch.is_tensor(scale) else None
     sf = 1.0 if sv is not None else float(scale)
+    if active is not None:  # masked-out matrices: out and the halves left as they are
+        _check(load().cq_transpose_split_masked(_p(X), r, c, B, _p(out), _p(hi), _p(lo), sf, _p(sv), int(bool(blocked)),
+                                                _act(active, B), _stream(X.device)), "cq_transpose_split_masked")
+        return out, hi, lo
     _check(load().cq_transpose_split(_p(X), r, c, B, _p(out), _p(hi), _p(lo), sf, _p(sv), int(bool(blocked)),
                                      _stream(X.device)),
            "cq_transpose_split")
@@ -720,7 +793,7 @@ def triu_split_ok(M: int, p: int) -> bool:
 
 
 def gemm_triu_split(X: torch.Tensor, Wt: torch.Tensor, C: torch.Tensor, hi: torch.Tensor, lo: torch.Tensor,
-                    scale: float):
+                    scale: float, active=None):
     """C = X Wt (Wt upper triangular) and hi/lo = the K-blocked split of C^T at `scale`: the
     same bits as gemm(X, Wt, b_triu=True) followed by transpose_split(C, blocked=True)."""
     _require_hip(X)
@@ -728,6 +801,10 @@ def gemm_triu_split(X: torch.Tensor, Wt: torch.Tensor, C: torch.Tensor, hi: torc
     assert X.dtype == Wt.dtype == C.dtype == torch.float32 and hi.dtype == lo.dtype == torch.float16
     assert X.is_contiguous() and Wt.is_contiguous() and C.is_contiguous() and hi.is_contiguous() and lo.is_contiguous()
     assert Wt.shape == (B, p, p) and C.shape == X.shape and hi.shape == (B, p, M) and lo.shape == hi.shape
+    if active is not None:
+        _check(load().cq_gemm_triu_split_masked(_p(X), _p(Wt), M, p, B, _p(C), _p(hi), _p(lo), float(scale),
+                                                _act(active, B), _stream(X.device)), "cq_gemm_triu_split_masked")
+        return
     _check(load().cq_gemm_triu_split(_p(X), _p(Wt), M, p, B, _p(C), _p(hi), _p(lo), float(scale),
                                      _stream(X.device)), "cq_gemm_triu_split")
     return C
@@ -800,7 +877,7 @@ def auto_split_k() -> bool:
 def gemm_x3(Ah, Al, Bh, Bl, inv_scale, C, *, P=None, D=None, alpha_v=None, beta_v=None, gamma_v=None,
             out_h=None, out_l=None, out_scale=1.0, overflow=None, tri=False, b_blocked=False, active=None,
             a_blocked=False, o_blocked=False, sym_bound=None, scale_out=None, inv_out=None, lda=None, M=None,
-            single=False, ksplit=None, b_exact=False, colw=None, absmax_out=None, Ct=None):
+            single=False, ksplit=None, b_exact=False, colw=None, absmax_out=None, Ct=None, skip=False):
     """C (B, M, N) = alpha * A B^T * inv_scale + beta P + gamma D with A = Ah + Al (B, M, K) and
     B = Bh + Bl (B, N, K) fp16 halves (b_blocked: in the K-blocked layout of sym_split_f16,
     same storage size); optional fp16 split of C into out_h/out_l.
@@ -813,7 +890,10 @@ def gemm_x3(Ah, Al, Bh, Bl, inv_scale, C, *, P=None, D=None, alpha_v=None, beta_
     (plain products): zeroed here, receives the bits of max|C[b]| (pow2_from_absmax turns them
     into the next split's scale without a pass over C).  Ct (B, N, M) fp32: C^T as well (not
     with tri / sym_out); C may then be None (only C^T is written).  out_l may be None with
-    out_h given (hi halves only, for a single product that follows; not with sym_bound)."""
+    out_h given (hi halves only, for a single product that follows; not with sym_bound).
+    active (B,) int32: a matrix with active[b] == 0 skips the product and gets C = D and its split
+    (D required) -- or, in the skip form (D None, or skip=True), is left out: nothing of it is
+    written (C, Ct, halves, overflow flag)."""
     assert Bl is not None or b_exact or single
     _require_hip(Ah, Al, Bh, Bl, C)
     Bt, MA, Kd = Ah.shape
@@ -883,6 +963,9 @@ def gemm_x3(Ah, Al, Bh, Bl, inv_scale, C, *, P=None, D=None, alpha_v=None, beta_
         g.out_bound, g.scale_out, g.inv_out = sym_bound.data_ptr(), scale_out.data_ptr(), inv_out.data_ptr()
         g.out_h, g.out_l, g.ldo, g.stride_o = out_h.data_ptr(), out_l.data_ptr(), N, M * N
         g.out_scale = out_scale
+    if skip and active is not None:
+        _check(load().cq_gemm_x3_skip(ctypes.byref(g), _stream(Ah.device)), "cq_gemm_x3_skip")
+        return C
     _check(load().cq_gemm_x3(ctypes.byref(g), _stream(Ah.device)), "cq_gemm_x3")
     return C
 

@@ -81,8 +81,15 @@ __device__ __forceinline__ void rot_params(double aii, double ajj, double aij, d
 template <int NT>
 __global__ __launch_bounds__(NT) void bj_init_kernel(double* __restrict__ A_all, int p, double* __restrict__ Vt_all,
                                                      int* __restrict__ done, int* __restrict__ sweeps,
-                                                     double tol) {
+                                                     double tol, const int* __restrict__ active) {
     const int64_t b = blockIdx.x;
+    if (active && !active[b]) {  // masked-out matrix: done from the start, so no sweep touches it
+        if (threadIdx.x == 0) {
+            done[b] = 1;
+            sweeps[b] = 0;
+        }
+        return;
+    }
     double* A = A_all + b * (int64_t)p * p;
     __shared__ double red[16];
     double off = 0.0, dg = 0.0;
@@ -379,9 +386,13 @@ __global__ __launch_bounds__(NT) void bj_finish_kernel(const double* __restrict_
                                                        const double* __restrict__ Vt_all, double* __restrict__ evals,
                                                        float* __restrict__ V32, double* __restrict__ V64,
                                                        const int* __restrict__ sweeps, int* __restrict__ sweeps_out,
-                                                       int* __restrict__ rank_ws) {
+                                                       int* __restrict__ rank_ws, const int* __restrict__ active) {
     extern __shared__ double fdg[];   // the diagonal (p values): the ranks read it p times
     const int64_t b = blockIdx.x;
+    if (active && !active[b]) {  // masked-out matrix: no values, no vectors, 0 sweeps
+        if (threadIdx.x == 0 && sweeps_out) sweeps_out[b] = 0;
+        return;
+    }
     const double* A = A_all + b * (int64_t)p * p;
     int* rk = rank_ws + b * (int64_t)p;
     for (int i = threadIdx.x; i < p; i += NT) fdg[i] = A[(int64_t)i * p + i];
@@ -432,15 +443,18 @@ __global__ void bj_pending_kernel(const int* __restrict__ done, int64_t batch, i
 }
 
 // Block-Jacobi eigensolver in stages, every stage stream-ordered (no host read-back inside):
-//   BJ_BEGIN   V = I, per-matrix done flags and sweep counts cleared;
+//   BJ_BEGIN   V = I, per-matrix done flags and sweep counts cleared (active given: a matrix with
+//              active[b] == 0 starts out done, so no sweep touches it and pending_out never counts it);
 //   BJ_SWEEPS  nsweeps sweeps; a matrix whose off-norm test passed (bj_check_kernel) has
 //              done[b] set and every later workgroup of it exits at entry; pending_out (device
 //              int, optional) = matrices still unconverged after these sweeps;
-//   BJ_END     eigenvalues (descending) and eigenvectors out, per-matrix sweep counts.
+//   BJ_END     eigenvalues (descending) and eigenvectors out, per-matrix sweep counts (a masked-out
+//              matrix's values and vectors are left alone, its sweep count reads 0).
 // The state (A in place, Vt, flags) lives in the caller's workspace between stages, so a
 // caller that reads pending_out can launch further sweeps only where they are needed.
 int bj_stage(double* A, int64_t p, int64_t batch, int phase, int nsweeps, double tol, bool want_v, double* evals,
-             float* V32, double* V64, int* sweeps_out, int* pending_out, void* ws, size_t ws_bytes, hipStream_t s) {
+             float* V32, double* V64, int* sweeps_out, int* pending_out, const int* active, void* ws, size_t ws_bytes,
+             hipStream_t s) {
     if (ws_bytes < bj_workspace(p, batch)) return set_error(CQ_EWORKSPACE, "cq_jacobi_eigh: workspace too small");
     const int nblk = (int)(ceil_div(p, NB) + (ceil_div(p, NB) & 1));
     const int npair = nblk / 2, noff = npair * (npair - 1), nslots = npair + noff;
@@ -459,9 +473,9 @@ int bj_stage(double* A, int64_t p, int64_t batch, int phase, int nsweeps, double
     if (phase & BJ_BEGIN)
     {
         if (batch < kCUs)
-            bj_init_kernel<1024><<<(unsigned)batch, 1024, 0, s>>>(A, (int)p, want_v ? Vt : nullptr, done, sweeps, tol);
+            bj_init_kernel<1024><<<(unsigned)batch, 1024, 0, s>>>(A, (int)p, want_v ? Vt : nullptr, done, sweeps, tol, active);
         else
-            bj_init_kernel<BT><<<(unsigned)batch, BT, 0, s>>>(A, (int)p, want_v ? Vt : nullptr, done, sweeps, tol);
+            bj_init_kernel<BT><<<(unsigned)batch, BT, 0, s>>>(A, (int)p, want_v ? Vt : nullptr, done, sweeps, tol, active);
     }
     if (phase & BJ_SWEEPS) {
         for (int sw = 0; sw < nsweeps; ++sw) {
@@ -486,18 +500,18 @@ int bj_stage(double* A, int64_t p, int64_t batch, int phase, int nsweeps, double
         const size_t fl = (size_t)p * sizeof(double);
         if (batch < kCUs)
             bj_finish_kernel<1024><<<(unsigned)batch, 1024, fl, s>>>(A, (int)p, want_v ? Vt : nullptr, evals, V32, V64,
-                                                                     sweeps, sweeps_out, ranks);
+                                                                     sweeps, sweeps_out, ranks, active);
         else
             bj_finish_kernel<BT><<<(unsigned)batch, BT, fl, s>>>(A, (int)p, want_v ? Vt : nullptr, evals, V32, V64,
-                                                                 sweeps, sweeps_out, ranks);
+                                                                 sweeps, sweeps_out, ranks, active);
     }
     return check_launch("cq_jacobi_eigh (block Jacobi)");
 }
 
 int bj_eigh(double* A, int64_t p, int64_t batch, int max_sweeps, double tol, double* evals, float* V32,
-            double* V64, int* sweeps_out, void* ws, size_t ws_bytes, hipStream_t s) {
+            double* V64, int* sweeps_out, const int* active, void* ws, size_t ws_bytes, hipStream_t s) {
     return bj_stage(A, p, batch, BJ_BEGIN | BJ_SWEEPS | BJ_END, max_sweeps, tol, V32 || V64, evals, V32, V64,
-                    sweeps_out, nullptr, ws, ws_bytes, s);
+                    sweeps_out, nullptr, active, ws, ws_bytes, s);
 }
 
 }  // namespace cq

@@ -42,6 +42,7 @@ struct KArgs {
     int b_triu;  // op(B) upper triangular (op(B)[k][n] = 0 for k > n): zero K slices skipped
     _Float16 *th, *tl;  // gemm_triu_kernel<., true>: K-blocked split halves of C^T
     float tscale;       // ... at this scale
+    const int* active;  // [batch] or NULL: workgroups of a matrix with active[b] == 0 return at entry
 };
 
 // Stage one BM x BK slice of op(A) into registers (4 floats x 2 per thread).
@@ -222,6 +223,7 @@ __global__ __launch_bounds__(kGemmThreads, 2) void gemm_f32_kernel(KArgs a) {
     float* Bs0 = smem + 2 * BK * LDA_S;
 
     const int64_t b = blockIdx.z;
+    if (a.active && !a.active[b]) return;  // masked-out matrix (cq_gemm_f32_masked): C untouched
     int64_t tm = blockIdx.y, tn = blockIdx.x;
     if (a.tri) {  // decode upper-triangular tile index (tm <= tn)
         const int64_t T = a.tri;
@@ -315,6 +317,7 @@ __global__ __launch_bounds__(kGemmThreads, 2) void gemm_triu_kernel(KArgs a) {
     float* As0 = smem;
     float* Bs0 = smem + 2 * BK * LDA_S;
     const int64_t b = blockIdx.z;
+    if (a.active && !a.active[b]) return;  // masked-out matrix: C (and the halves) untouched
     const int64_t m0 = (int64_t)blockIdx.y * BM;
     const float* A = a.A + b * a.sa;
     const float* B = a.B + b * a.sb;
@@ -583,7 +586,16 @@ size_t cq_gemm_workspace(const cq_gemm_args* a) {
 }
 
 int cq_gemm_f32(const cq_gemm_args* g, void* ws, size_t ws_bytes, void* stream) {
+    return cq_gemm_f32_masked(g, nullptr, ws, ws_bytes, stream);
+}
+
+// active ([batch] int32 or NULL = all): matrices with active[b] == 0 are left out -- their
+// workgroups return at entry and C[b] is not written.  LINEAR epilogue without syrk only (the
+// solver's X V, Z V and X Wt products); the live matrices' bits are those of cq_gemm_f32.
+int cq_gemm_f32_masked(const cq_gemm_args* g, const int* active, void* ws, size_t ws_bytes, void* stream) {
     CQ_REQUIRE(g, "cq_gemm_f32: null args");
+    CQ_REQUIRE(!active || (g->epi == CQ_EPI_LINEAR && !g->syrk),
+               "cq_gemm_f32_masked: a mask needs the LINEAR epilogue without syrk");
     CQ_REQUIRE(g->M > 0 && g->N > 0 && g->K >= 0 && g->batch > 0, "cq_gemm_f32: bad shape");
     CQ_REQUIRE((g->A && g->B) || g->K == 0, "cq_gemm_f32: null A/B");
     CQ_REQUIRE(g->epi >= CQ_EPI_LINEAR && g->epi <= CQ_EPI_WERR, "cq_gemm_f32: bad epi");
@@ -626,6 +638,7 @@ int cq_gemm_f32(const cq_gemm_args* g, void* ws, size_t ws_bytes, void* stream) 
     k.b_triu = g->b_triu;
     k.th = k.tl = nullptr;
     k.tscale = 1.f;
+    k.active = active;
     CQ_REQUIRE(!g->b_triu || (!g->trans_a && !g->trans_b && !g->syrk && g->epi == CQ_EPI_LINEAR),
                "cq_gemm_f32: b_triu needs a plain product (no transposes, LINEAR epilogue)");
     if (g->syrk) {
@@ -674,6 +687,11 @@ int cq_gemm_f32(const cq_gemm_args* g, void* ws, size_t ws_bytes, void* stream) 
 
 int cq_gemm_triu_split(const float* X, const float* Wt, int64_t M, int64_t p, int64_t batch, float* C,
                        uint16_t* hi, uint16_t* lo, float scale, void* stream) {
+    return cq_gemm_triu_split_masked(X, Wt, M, p, batch, C, hi, lo, scale, nullptr, stream);
+}
+
+int cq_gemm_triu_split_masked(const float* X, const float* Wt, int64_t M, int64_t p, int64_t batch, float* C,
+                              uint16_t* hi, uint16_t* lo, float scale, const int* active, void* stream) {
     CQ_REQUIRE(X && Wt && C && hi && lo, "cq_gemm_triu_split: null pointer");
     CQ_REQUIRE(p > 0 && p % 32 == 0 && p <= BN, "cq_gemm_triu_split: p must be a multiple of 32, <= 192");
     CQ_REQUIRE(M > 0 && M % 32 == 0 && batch > 0 && batch <= 65535 && ceil_div(M, BM) <= 65535,
@@ -691,6 +709,7 @@ int cq_gemm_triu_split(const float* X, const float* Wt, int64_t M, int64_t p, in
     k.th = reinterpret_cast<_Float16*>(hi);
     k.tl = reinterpret_cast<_Float16*>(lo);
     k.tscale = scale;
+    k.active = active;
     CQ_REQUIRE((reinterpret_cast<uintptr_t>(hi) & 7) == 0 && (reinterpret_cast<uintptr_t>(lo) & 7) == 0,
                "cq_gemm_triu_split: halves must be 8-byte aligned");
     const dim3 tg(1, (unsigned)ceil_div(M, BM), (unsigned)batch);

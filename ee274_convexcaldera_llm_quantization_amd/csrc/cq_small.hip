@@ -24,10 +24,11 @@ constexpr int kGramThreads = 256;
 __global__ __launch_bounds__(kGramThreads) void gram_f64_kernel(
     int64_t M, int64_t N, int64_t K, int64_t kchunk, int splits, const float* __restrict__ A,
     int ta, int64_t lda, int64_t sa, const float* __restrict__ B, int tb, int64_t ldb, int64_t sb,
-    double* __restrict__ part) {
+    double* __restrict__ part, const int* __restrict__ active) {
     __shared__ float As[GK][GT + 1];
     __shared__ float Bs[GK][GT + 1];
     const int64_t b = blockIdx.z / splits;
+    if (active && !active[b]) return;  // masked-out matrix: nothing read, nothing written
     const int split = blockIdx.z % splits;
     const int64_t i0 = (int64_t)blockIdx.y * GT, j0 = (int64_t)blockIdx.x * GT;
     const float* Ab = A + b * sa;
@@ -81,11 +82,12 @@ __global__ __launch_bounds__(kGramThreads) void gram_f64_kernel(
 }
 
 __global__ void gram_reduce_kernel(const double* __restrict__ part, int64_t MN, int splits,
-                                   int64_t batch, double* __restrict__ C) {
+                                   int64_t batch, double* __restrict__ C, const int* __restrict__ active) {
     const int64_t total = batch * MN;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
          e += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = e / MN, o = e % MN;
+        if (active && !active[b]) continue;
         double s = 0.0;
         for (int t = 0; t < splits; ++t) s += part[(b * splits + t) * MN + o];
         C[e] = s;
@@ -107,7 +109,7 @@ template <bool TK>
 __global__ __launch_bounds__(kGramThreads) void gram_f64_mfma_kernel(
     int64_t M, int64_t N, int64_t K, int64_t kchunk, int splits, const float* __restrict__ A,
     int64_t lda, int64_t sa, const float* __restrict__ B, int64_t ldb, int64_t sb, int sym,
-    double* __restrict__ part, double* __restrict__ C) {
+    double* __restrict__ part, double* __restrict__ C, const int* __restrict__ active) {
     // row pitch: GT + 16 floats puts the fragment reads' four K rows (lane >> 4) 16 banks apart
     // (conflict-free; GT + 4 overlapped them: 3.2 conflict cycles per LDS instruction in PMC);
     // the TK stash writes columns and keeps GT + 4
@@ -117,6 +119,7 @@ __global__ __launch_bounds__(kGramThreads) void gram_f64_mfma_kernel(
     const int64_t b = blockIdx.z / splits;
     const int split = blockIdx.z % splits;
     if (sym && blockIdx.x < blockIdx.y) return;
+    if (active && !active[b]) return;  // masked-out matrix: nothing read, nothing written
     const int64_t i0 = (int64_t)blockIdx.y * GT, j0 = (int64_t)blockIdx.x * GT;
     const float* Ab = A + b * sa;
     const float* Bb = B + b * sb;
@@ -230,11 +233,12 @@ __global__ __launch_bounds__(kGramThreads) void gram_f64_mfma_kernel(
 }
 
 __global__ void gram_reduce_sym_kernel(const double* __restrict__ part, int64_t M, int splits,
-                                       int64_t batch, double* __restrict__ C) {
+                                       int64_t batch, double* __restrict__ C, const int* __restrict__ active) {
     const int64_t MN = M * M, total = batch * MN;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
          e += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = e / MN, o = e % MN, i = o / M, j = o % M;
+        if (active && !active[b]) continue;
         const int64_t src = (i / GT > j / GT) ? j * M + i : o;  // lower tiles were skipped
         double s = 0.0;
         for (int t2 = 0; t2 < splits; ++t2) s += part[(b * splits + t2) * MN + src];
@@ -266,8 +270,13 @@ __global__ __launch_bounds__(NTH) void jacobi_reg_kernel(const double* __restric
                                                                     double* __restrict__ evals,
                                                                     float* __restrict__ V32,
                                                                     double* __restrict__ V64,
-                                                                    int* __restrict__ sweeps_out) {
+                                                                    int* __restrict__ sweeps_out,
+                                                                    const int* __restrict__ active) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    if (active && !active[blockIdx.x]) {  // masked-out matrix: no values, no vectors, 0 sweeps
+        if (threadIdx.x == 0 && sweeps_out) sweeps_out[blockIdx.x] = 0;
+        return;
+    }
     const int P = p + (p & 1);
     const int H = P / 2;
     double2* csn = reinterpret_cast<double2*>(smem_raw);  // H: (cos, sin) of pair k's rotation
@@ -586,8 +595,10 @@ constexpr int kWmWaves = kWmThreads / 64;
 template <bool LP>   // LP: the panel rows in LDS (p <= 512); else read in place from L2 (any p)
 __global__ __launch_bounds__(kWmThreads) void spd_whiten_mfma_kernel(double* __restrict__ S_all, int p, double rc2,
                                                                      double* __restrict__ E_all,
-                                                                     float* __restrict__ W32, int* __restrict__ info) {
+                                                                     float* __restrict__ W32, int* __restrict__ info,
+                                                                     const int* __restrict__ active) {
     extern __shared__ __attribute__((aligned(16))) double wm_smem[];
+    if (active && !active[blockIdx.x]) return;  // masked-out matrix: S, E, W32 and info untouched
     double* piv = wm_smem;          // p pivots (inf for dropped)
     double* Li = piv + p;           // 32 x 33: L11^{-1} of the current panel (row-major, padded)
     double* rp = Li + 32 * 33;      // 32: 1 / pivot (0 for dropped) of the current panel
@@ -791,7 +802,9 @@ __device__ __forceinline__ int lz_sturm(const double* al, const double* b2, int 
 // rounding) instead of an fp32 copy of S in LDS
 template <int Q, bool GT, int NT>
 __global__ __launch_bounds__(NT) void extreme_eigs_kernel(const double* __restrict__ T_all, int p, int steps,
-                                                         double* __restrict__ ends) {
+                                                         double* __restrict__ ends,
+                                                         const int* __restrict__ active) {
+    if (active && !active[blockIdx.x]) return;  // masked-out matrix: ends untouched
     extern __shared__ __attribute__((aligned(16))) float lz_t[];   // S, p x p fp32 (row j at j p), !GT
     __shared__ float vf[64 * Q];                                   // current Lanczos vector (fp32 copy)
     __shared__ float part[NT / 64][64 * Q];                        // per-wave partial products
@@ -958,8 +971,10 @@ __global__ __launch_bounds__(256) void ritz_partial_kernel(const float* __restri
                                                             const float* __restrict__ Z,
                                                             const double* __restrict__ theta,
                                                             int64_t k, int64_t p, int64_t r,
-                                                            int64_t rows_per, double* part) {
+                                                            int64_t rows_per, double* part,
+                                                            const int* __restrict__ active) {
     const int64_t b = blockIdx.y, chunk = blockIdx.x;
+    if (active && !active[b]) return;
     const int64_t r0 = chunk * rows_per, r1 = min(k, r0 + rows_per);
     for (int64_t c = threadIdx.x; c < r; c += blockDim.x) {
         const float th = (float)theta[b * p + c];
@@ -973,9 +988,10 @@ __global__ __launch_bounds__(256) void ritz_partial_kernel(const float* __restri
 }
 
 __global__ void ritz_final_kernel(const double* part, int nchunks, int64_t p, int64_t r,
-                                  const double* theta, float* out) {
+                                  const double* theta, float* out, const int* __restrict__ active) {
     __shared__ double red[16];
     const int64_t b = blockIdx.x;
+    if (active && !active[b]) return;
     double mx = 0.0;
     for (int64_t c = threadIdx.x; c < r; c += blockDim.x) {
         double s = 0.0;
@@ -999,9 +1015,11 @@ __global__ void ritz_final_kernel(const double* part, int nchunks, int64_t p, in
 // (gap_i = theta_i - theta_{p-1}, the block's smallest Ritz value bounding the unconverged
 // complement), which moves the projection of Y by that angle times sigma_i = sqrt(theta_i).
 __global__ void ritz_prod_final_kernel(const double* part, int nchunks, int64_t p, int64_t r,
-                                       const double* theta, const double* ysq, float* out) {
+                                       const double* theta, const double* ysq, float* out,
+                                       const int* __restrict__ active) {
     __shared__ double red[16];
     const int64_t b = blockIdx.x;
+    if (active && !active[b]) return;
     const double t0 = fabs(theta[b * p]), tp = theta[b * p + p - 1];
     double acc = 0.0;
     for (int64_t c = threadIdx.x; c < r; c += blockDim.x) {
@@ -1035,6 +1053,17 @@ size_t cq_gram_f64_workspace(int64_t M, int64_t N, int64_t K, int64_t batch) {
 int cq_gram_f64(int64_t M, int64_t N, int64_t K, int64_t batch, const float* A, int trans_a,
                 int64_t lda, int64_t stride_a, const float* B, int trans_b, int64_t ldb,
                 int64_t stride_b, double* C, void* ws, size_t ws_bytes, void* stream) {
+    return cq_gram_f64_masked(M, N, K, batch, A, trans_a, lda, stride_a, B, trans_b, ldb, stride_b, C, nullptr, ws,
+                              ws_bytes, stream);
+}
+
+// The masked entries (ABI 5, additive): `active` is [batch] int32 on the device or NULL (= all).
+// A workgroup of a matrix with active[b] == 0 returns at entry -- uniformly, before its first
+// barrier -- so that matrix's outputs are left as they were; the others run the same
+// instructions on the same data as the unmasked entry (which passes NULL).
+int cq_gram_f64_masked(int64_t M, int64_t N, int64_t K, int64_t batch, const float* A, int trans_a,
+                       int64_t lda, int64_t stride_a, const float* B, int trans_b, int64_t ldb,
+                       int64_t stride_b, double* C, const int* active, void* ws, size_t ws_bytes, void* stream) {
     CQ_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0 && batch > 0, "cq_gram_f64: bad args");
     const int splits = gram_splits(M, N, K, batch);
     if (!ws || ws_bytes < cq_gram_f64_workspace(M, N, K, batch))
@@ -1053,22 +1082,22 @@ int cq_gram_f64(int64_t M, int64_t N, int64_t K, int64_t batch, const float* A, 
         if (trans_a)
             gram_f64_mfma_kernel<true><<<grid, kGramThreads, 0, s>>>(M, N, K, kchunk, splits, A, lda, stride_a, B,
                                                                      ldb, stride_b, sym, reinterpret_cast<double*>(ws),
-                                                                     direct);
+                                                                     direct, active);
         else
             gram_f64_mfma_kernel<false><<<grid, kGramThreads, 0, s>>>(M, N, K, kchunk, splits, A, lda, stride_a, B,
                                                                       ldb, stride_b, sym, reinterpret_cast<double*>(ws),
-                                                                      direct);
+                                                                      direct, active);
         if (direct) return check_launch("cq_gram_f64");
         if (sym)
-            gram_reduce_sym_kernel<<<rgrid, 256, 0, s>>>(reinterpret_cast<double*>(ws), M, splits, batch, C);
+            gram_reduce_sym_kernel<<<rgrid, 256, 0, s>>>(reinterpret_cast<double*>(ws), M, splits, batch, C, active);
         else
-            gram_reduce_kernel<<<rgrid, 256, 0, s>>>(reinterpret_cast<double*>(ws), M * N, splits, batch, C);
+            gram_reduce_kernel<<<rgrid, 256, 0, s>>>(reinterpret_cast<double*>(ws), M * N, splits, batch, C, active);
         return check_launch("cq_gram_f64");
     }
     gram_f64_kernel<<<grid, kGramThreads, 0, s>>>(M, N, K, kchunk, splits, A, trans_a, lda,
                                                    stride_a, B, trans_b, ldb, stride_b,
-                                                   reinterpret_cast<double*>(ws));
-    gram_reduce_kernel<<<rgrid, 256, 0, s>>>(reinterpret_cast<double*>(ws), M * N, splits, batch, C);
+                                                   reinterpret_cast<double*>(ws), active);
+    gram_reduce_kernel<<<rgrid, 256, 0, s>>>(reinterpret_cast<double*>(ws), M * N, splits, batch, C, active);
     return check_launch("cq_gram_f64");
 }
 
@@ -1079,6 +1108,11 @@ int cq_spd_whiten(double* S, int64_t p, int64_t batch, float* Wt32, double* Wt64
 
 int cq_spd_whiten_rcond(double* S, int64_t p, int64_t batch, double rcond2, float* Wt32, double* Wt64, int* info,
                         void* stream) {
+    return cq_spd_whiten_masked(S, p, batch, rcond2, Wt32, Wt64, info, nullptr, stream);
+}
+
+int cq_spd_whiten_masked(double* S, int64_t p, int64_t batch, double rcond2, float* Wt32, double* Wt64, int* info,
+                         const int* active, void* stream) {
     CQ_REQUIRE(S && p > 0 && batch > 0 && info && Wt64, "cq_spd_whiten: bad args (Wt64 is required scratch)");
     CQ_REQUIRE(rcond2 >= 0.0, "cq_spd_whiten: rcond2 must be >= 0");
     hipStream_t s = as_stream(stream);
@@ -1088,9 +1122,9 @@ int cq_spd_whiten_rcond(double* S, int64_t p, int64_t batch, double rcond2, floa
     const size_t wlm = wsm + (size_t)32 * wm_pitch((int)p) * sizeof(double);
     CQ_REQUIRE(wsm <= 64 * 1024, "cq_spd_whiten: p too large");
     if (wlm <= 150 * 1024)
-        spd_whiten_mfma_kernel<true><<<(unsigned)batch, kWmThreads, wlm, s>>>(S, (int)p, rcond2, Wt64, Wt32, info);
+        spd_whiten_mfma_kernel<true><<<(unsigned)batch, kWmThreads, wlm, s>>>(S, (int)p, rcond2, Wt64, Wt32, info, active);
     else
-        spd_whiten_mfma_kernel<false><<<(unsigned)batch, kWmThreads, wsm, s>>>(S, (int)p, rcond2, Wt64, Wt32, info);
+        spd_whiten_mfma_kernel<false><<<(unsigned)batch, kWmThreads, wsm, s>>>(S, (int)p, rcond2, Wt64, Wt32, info, active);
     return check_launch("cq_spd_whiten");
 }
 
@@ -1102,22 +1136,29 @@ size_t cq_jacobi_workspace(int64_t p, int64_t batch) {
 int cq_jacobi_eigh(double* A, int64_t p, int64_t batch, int max_sweeps, double tol, double* evals,
                    float* V32, double* V64, int* sweeps_out, void* ws, size_t ws_bytes,
                    void* stream) {
+    return cq_jacobi_eigh_masked(A, p, batch, max_sweeps, tol, evals, V32, V64, sweeps_out, nullptr, ws, ws_bytes,
+                                 stream);
+}
+
+int cq_jacobi_eigh_masked(double* A, int64_t p, int64_t batch, int max_sweeps, double tol, double* evals,
+                          float* V32, double* V64, int* sweeps_out, const int* active, void* ws, size_t ws_bytes,
+                          void* stream) {
     CQ_REQUIRE(A && evals && p > 0 && batch > 0 && max_sweeps > 0, "cq_jacobi_eigh: bad args");
     CQ_REQUIRE(p <= 4096, "cq_jacobi_eigh: p too large");
     if (!ws || ws_bytes < cq_jacobi_workspace(p, batch))
         return set_error(CQ_EWORKSPACE, "cq_jacobi_eigh: workspace too small");
     hipStream_t s = as_stream(stream);
     if (p > kBlockJacobiMinP)  // A does not fit one CU's LDS: block Jacobi over many workgroups
-        return cq::bj_eigh(A, p, batch, max_sweeps, tol, evals, V32, V64, sweeps_out, ws, ws_bytes, s);
+        return cq::bj_eigh(A, p, batch, max_sweeps, tol, evals, V32, V64, sweeps_out, active, ws, ws_bytes, s);
     // p <= 192: fp64 A packed in LDS, V in registers (no per-round memory traffic for V)
     const size_t lreg = jacobi_reg_bytes((int)p);
     CQ_REQUIRE(lreg <= 160 * 1024, "cq_jacobi_eigh: LDS budget");
     if (p <= 64)
-        jacobi_reg_kernel<1, 2, 2, 1024><<<(unsigned)batch, 1024, lreg, s>>>(A, (int)p, max_sweeps, tol, evals, V32, V64, sweeps_out);
+        jacobi_reg_kernel<1, 2, 2, 1024><<<(unsigned)batch, 1024, lreg, s>>>(A, (int)p, max_sweeps, tol, evals, V32, V64, sweeps_out, active);
     else if (p <= 128)
-        jacobi_reg_kernel<2, 4, 2, 1024><<<(unsigned)batch, 1024, lreg, s>>>(A, (int)p, max_sweeps, tol, evals, V32, V64, sweeps_out);
+        jacobi_reg_kernel<2, 4, 2, 1024><<<(unsigned)batch, 1024, lreg, s>>>(A, (int)p, max_sweeps, tol, evals, V32, V64, sweeps_out, active);
     else
-        jacobi_reg_kernel<3, 6, 1, 1024><<<(unsigned)batch, 1024, lreg, s>>>(A, (int)p, max_sweeps, tol, evals, V32, V64, sweeps_out);
+        jacobi_reg_kernel<3, 6, 1, 1024><<<(unsigned)batch, 1024, lreg, s>>>(A, (int)p, max_sweeps, tol, evals, V32, V64, sweeps_out, active);
     return check_launch("cq_jacobi_eigh");
 }
 
@@ -1126,6 +1167,15 @@ size_t cq_jacobi_staged_workspace(int64_t p, int64_t batch) { return cq::bj_work
 int cq_jacobi_eigh_staged(double* A, int64_t p, int64_t batch, int phase, int nsweeps, double tol, int want_vectors,
                           double* evals, float* V32, double* V64, int* sweeps_out, int* pending_out, void* ws,
                           size_t ws_bytes, void* stream) {
+    return cq_jacobi_eigh_staged_masked(A, p, batch, phase, nsweeps, tol, want_vectors, evals, V32, V64, sweeps_out,
+                                        pending_out, nullptr, ws, ws_bytes, stream);
+}
+
+// active is read by the BJ_BEGIN stage (inactive matrices start out done: no sweep touches them
+// and pending_out never counts them) and by BJ_END (their outputs are left alone, sweeps_out 0)
+int cq_jacobi_eigh_staged_masked(double* A, int64_t p, int64_t batch, int phase, int nsweeps, double tol,
+                                 int want_vectors, double* evals, float* V32, double* V64, int* sweeps_out,
+                                 int* pending_out, const int* active, void* ws, size_t ws_bytes, void* stream) {
     CQ_REQUIRE(A && p >= 2 && p <= 4096 && batch > 0, "cq_jacobi_eigh_staged: bad args");
     CQ_REQUIRE(phase > 0 && phase <= (BJ_BEGIN | BJ_SWEEPS | BJ_END), "cq_jacobi_eigh_staged: bad phase");
     CQ_REQUIRE(!(phase & BJ_SWEEPS) || nsweeps > 0, "cq_jacobi_eigh_staged: nsweeps must be > 0");
@@ -1133,10 +1183,15 @@ int cq_jacobi_eigh_staged(double* A, int64_t p, int64_t batch, int phase, int ns
     if (!ws || ws_bytes < cq_jacobi_staged_workspace(p, batch))
         return set_error(CQ_EWORKSPACE, "cq_jacobi_eigh_staged: workspace too small");
     return cq::bj_stage(A, p, batch, phase, nsweeps, tol, want_vectors != 0, evals, V32, V64, sweeps_out, pending_out,
-                        ws, ws_bytes, as_stream(stream));
+                        active, ws, ws_bytes, as_stream(stream));
 }
 
 int cq_extreme_eigs(const double* T, int64_t p, int64_t batch, int steps, double* ends, void* stream) {
+    return cq_extreme_eigs_masked(T, p, batch, steps, ends, nullptr, stream);
+}
+
+int cq_extreme_eigs_masked(const double* T, int64_t p, int64_t batch, int steps, double* ends, const int* active,
+                           void* stream) {
     CQ_REQUIRE(T && ends && p >= 2 && batch > 0 && batch <= 2147483647, "cq_extreme_eigs: bad args");
     CQ_REQUIRE(p <= kLzMaxPG, "cq_extreme_eigs: p > %d", kLzMaxPG);
     CQ_REQUIRE(steps >= 1 && steps < kLzMaxSteps, "cq_extreme_eigs: steps must be in [1, %d)", kLzMaxSteps);
@@ -1146,13 +1201,13 @@ int cq_extreme_eigs(const double* T, int64_t p, int64_t batch, int steps, double
     // 64-row groups p needs
     if (p <= kLzMaxP)
         extreme_eigs_kernel<3, false, kLzThreads><<<(unsigned)batch, kLzThreads, (size_t)p * p * sizeof(float), s>>>(
-            T, (int)p, steps, ends);
+            T, (int)p, steps, ends, active);
     else if (p <= 320)
-        extreme_eigs_kernel<5, true, 1024><<<(unsigned)batch, 1024, 0, s>>>(T, (int)p, steps, ends);
+        extreme_eigs_kernel<5, true, 1024><<<(unsigned)batch, 1024, 0, s>>>(T, (int)p, steps, ends, active);
     else if (p <= 384)
-        extreme_eigs_kernel<6, true, 1024><<<(unsigned)batch, 1024, 0, s>>>(T, (int)p, steps, ends);
+        extreme_eigs_kernel<6, true, 1024><<<(unsigned)batch, 1024, 0, s>>>(T, (int)p, steps, ends, active);
     else
-        extreme_eigs_kernel<8, true, 1024><<<(unsigned)batch, 1024, 0, s>>>(T, (int)p, steps, ends);
+        extreme_eigs_kernel<8, true, 1024><<<(unsigned)batch, 1024, 0, s>>>(T, (int)p, steps, ends, active);
     return check_launch("cq_extreme_eigs");
 }
 
@@ -1164,6 +1219,12 @@ size_t cq_ritz_workspace(int64_t k, int64_t r, int64_t batch) {
 int cq_ritz_residual(const float* X, const float* Z, const double* theta, int64_t k, int64_t p,
                      int64_t r, int64_t batch, float* out, void* ws, size_t ws_bytes,
                      void* stream) {
+    return cq_ritz_residual_masked(X, Z, theta, k, p, r, batch, out, nullptr, ws, ws_bytes, stream);
+}
+
+int cq_ritz_residual_masked(const float* X, const float* Z, const double* theta, int64_t k, int64_t p,
+                            int64_t r, int64_t batch, float* out, const int* active, void* ws, size_t ws_bytes,
+                            void* stream) {
     CQ_REQUIRE(X && Z && theta && out && k > 0 && p > 0 && r > 0 && r <= p, "cq_ritz_residual: bad args");
     if (!ws || ws_bytes < cq_ritz_workspace(k, r, batch))
         return set_error(CQ_EWORKSPACE, "cq_ritz_residual: workspace too small");
@@ -1171,13 +1232,19 @@ int cq_ritz_residual(const float* X, const float* Z, const double* theta, int64_
     const int64_t nch = std::min<int64_t>(64, std::max<int64_t>(1, k / 64));
     const int64_t rows_per = ceil_div(k, nch);
     double* part = reinterpret_cast<double*>(ws);
-    ritz_partial_kernel<<<dim3((unsigned)nch, (unsigned)batch), 256, 0, s>>>(X, Z, theta, k, p, r, rows_per, part);
-    ritz_final_kernel<<<(unsigned)batch, 256, 0, s>>>(part, (int)nch, p, r, theta, out);
+    ritz_partial_kernel<<<dim3((unsigned)nch, (unsigned)batch), 256, 0, s>>>(X, Z, theta, k, p, r, rows_per, part, active);
+    ritz_final_kernel<<<(unsigned)batch, 256, 0, s>>>(part, (int)nch, p, r, theta, out, active);
     return check_launch("cq_ritz_residual");
 }
 
 int cq_ritz_product_error(const float* X, const float* Z, const double* theta, int64_t k, int64_t p, int64_t r,
                           int64_t batch, const double* ysq, float* out, void* ws, size_t ws_bytes, void* stream) {
+    return cq_ritz_product_error_masked(X, Z, theta, k, p, r, batch, ysq, out, nullptr, ws, ws_bytes, stream);
+}
+
+int cq_ritz_product_error_masked(const float* X, const float* Z, const double* theta, int64_t k, int64_t p, int64_t r,
+                                 int64_t batch, const double* ysq, float* out, const int* active, void* ws,
+                                 size_t ws_bytes, void* stream) {
     CQ_REQUIRE(X && Z && theta && ysq && out && k > 0 && p > 0 && r > 0 && r < p,
                "cq_ritz_product_error: bad args");
     if (!ws || ws_bytes < cq_ritz_workspace(k, r, batch))
@@ -1186,8 +1253,8 @@ int cq_ritz_product_error(const float* X, const float* Z, const double* theta, i
     const int64_t nch = std::min<int64_t>(64, std::max<int64_t>(1, k / 64));
     const int64_t rows_per = ceil_div(k, nch);
     double* part = reinterpret_cast<double*>(ws);
-    ritz_partial_kernel<<<dim3((unsigned)nch, (unsigned)batch), 256, 0, s>>>(X, Z, theta, k, p, r, rows_per, part);
-    ritz_prod_final_kernel<<<(unsigned)batch, 256, 0, s>>>(part, (int)nch, p, r, theta, ysq, out);
+    ritz_partial_kernel<<<dim3((unsigned)nch, (unsigned)batch), 256, 0, s>>>(X, Z, theta, k, p, r, rows_per, part, active);
+    ritz_prod_final_kernel<<<(unsigned)batch, 256, 0, s>>>(part, (int)nch, p, r, theta, ysq, out, active);
     return check_launch("cq_ritz_product_error");
 }
 

@@ -189,9 +189,11 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void transpose_split_kernel(const float* __restrict__ X, int64_t rows, int64_t cols,
                                                               float* __restrict__ Y, _Float16* __restrict__ hi,
                                                               _Float16* __restrict__ lo, float s_fixed,
-                                                              const float* __restrict__ s_v, int blocked) {
+                                                              const float* __restrict__ s_v, int blocked,
+                                                              const int* __restrict__ active) {
     __shared__ float tile[64][65];
     const int64_t b = blockIdx.z;
+    if (active && !active[b]) return;  // masked-out matrix: Y and the halves untouched
     const int64_t r0 = (int64_t)blockIdx.y * 64, c0 = (int64_t)blockIdx.x * 64;
     const float* Xb = X + b * rows * cols;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -333,6 +335,12 @@ int cq_split_f16(const float* X, int64_t n_per, int64_t batch, const float* scal
 
 int cq_transpose_split(const float* X, int64_t rows, int64_t cols, int64_t batch, float* Y, uint16_t* hi,
                        uint16_t* lo, float scale, const float* scale_v, int blocked, void* stream) {
+    return cq_transpose_split_masked(X, rows, cols, batch, Y, hi, lo, scale, scale_v, blocked, nullptr, stream);
+}
+
+int cq_transpose_split_masked(const float* X, int64_t rows, int64_t cols, int64_t batch, float* Y, uint16_t* hi,
+                              uint16_t* lo, float scale, const float* scale_v, int blocked, const int* active,
+                              void* stream) {
     CQ_REQUIRE(!blocked || rows % 32 == 0, "cq_transpose_split: blocked halves need rows % 32 == 0");
     CQ_REQUIRE(X && (Y || hi), "cq_transpose_split: null pointer");
     CQ_REQUIRE(hi || !lo, "cq_transpose_split: lo needs hi (hi alone: the operand of a single product)");
@@ -342,10 +350,10 @@ int cq_transpose_split(const float* X, int64_t rows, int64_t cols, int64_t batch
     const bool vec = rows % 8 == 0 && cols % 4 == 0 && al16(X) && (!Y || al16(Y)) && (!hi || al16(hi)) && (!lo || al16(lo));
     if (vec)
         transpose_split_kernel<true><<<grid, 256, 0, as_stream(stream)>>>(
-            X, rows, cols, Y, reinterpret_cast<_Float16*>(hi), reinterpret_cast<_Float16*>(lo), scale, scale_v, blocked);
+            X, rows, cols, Y, reinterpret_cast<_Float16*>(hi), reinterpret_cast<_Float16*>(lo), scale, scale_v, blocked, active);
     else
         transpose_split_kernel<false><<<grid, 256, 0, as_stream(stream)>>>(
-            X, rows, cols, Y, reinterpret_cast<_Float16*>(hi), reinterpret_cast<_Float16*>(lo), scale, scale_v, blocked);
+            X, rows, cols, Y, reinterpret_cast<_Float16*>(hi), reinterpret_cast<_Float16*>(lo), scale, scale_v, blocked, active);
     return check_launch("cq_transpose_split");
 }
 

@@ -39,6 +39,7 @@ struct X3K {
     int64_t scolw = 0;            // colw batch stride (0: one vector for every matrix)
     uint32_t* absmax_out = nullptr;  // [batch] (or NULL, plain products): atomic max of |C| bits
     float* Ct = nullptr; int64_t sct = 0;  // C^T too (N x M, row stride M), batch stride sct
+    int skip = 0;  // with active: an inactive matrix's workgroups return at entry and write nothing
 };
 
 using f16x8g = __attribute__((ext_vector_type(8))) _Float16;

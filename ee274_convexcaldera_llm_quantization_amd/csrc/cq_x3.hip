@@ -98,6 +98,9 @@ __global__ __launch_bounds__(XW_THREADS, 1) void gemm_x3v_kernel(X3K a) {
     }
     const int64_t m0 = tm * XW_BM, n0 = tn * XW_BN;
     if (a.tri && n0 + XW_BN <= m0) return;
+    // skip form: an inactive matrix's workgroups leave before the ring prologue and write nothing
+    // (C, C^T, the halves, the overflow flag and the split-K partials stay as they were)
+    if (a.skip && !a.active[b]) return;
 
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int wm = wid & 1, wn = wid >> 1;  // rows 96 wm .. +96, cols 64 wn .. +64
@@ -442,6 +445,7 @@ __global__ __launch_bounds__(256) void x3_splitk_epi_kernel(X3K a) {
     const int64_t nq = a.N / 4;
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t b = blockIdx.y;
+    if (a.skip && !a.active[b]) return;  // skip form: nothing written (b is uniform over the workgroup)
     const bool in = t < a.M * nq;
     uint32_t amx = 0u;
     if (in) {
@@ -487,9 +491,20 @@ __global__ __launch_bounds__(256) void x3_splitk_epi_kernel(X3K a) {
 
 using namespace cq;
 
+static int gemm_x3_launch(const cq_x3_args* g, bool skip_form, void* stream);
+
 extern "C" {
 
-int cq_gemm_x3(const cq_x3_args* g, void* stream) {
+int cq_gemm_x3(const cq_x3_args* g, void* stream) { return gemm_x3_launch(g, false, stream); }
+
+// cq_gemm_x3 with the skip form asked for whether or not D is given: matrices with
+// active[b] == 0 are left out altogether (a recurrence step of a filter whose frozen matrices'
+// iterates nobody reads), where cq_gemm_x3 would pass D through to C and the halves.
+int cq_gemm_x3_skip(const cq_x3_args* g, void* stream) { return gemm_x3_launch(g, true, stream); }
+
+}  // extern "C"
+
+static int gemm_x3_launch(const cq_x3_args* g, bool skip_form, void* stream) {
     CQ_REQUIRE(g, "cq_gemm_x3: null args");
     CQ_REQUIRE(g->Ah && g->Al && g->Bh && (g->Bl || g->single || g->b_exact) && (g->C || g->sym_out || g->Ct) && g->inv_scale,
                "cq_gemm_x3: null operand");
@@ -549,7 +564,9 @@ int cq_gemm_x3(const cq_x3_args* g, void* stream) {
     a.o_blocked = g->o_blocked;
     CQ_REQUIRE(!g->o_blocked || g->N % 32 == 0, "cq_gemm_x3: blocked split output needs N % 32 == 0");
     CQ_REQUIRE(!g->a_blocked || g->lda >= g->M, "cq_gemm_x3: blocked A needs lda = rows >= M");
-    CQ_REQUIRE(!g->active || g->D, "cq_gemm_x3: active needs D (the pass-through value)");
+    // active without D (no pass-through value), or cq_gemm_x3_skip: the skip form
+    a.skip = (g->active && (skip_form || !g->D)) ? 1 : 0;
+    CQ_REQUIRE(!a.skip || (!g->tri && !g->sym_out), "cq_gemm_x3: the skip form needs a plain product");
     CQ_REQUIRE(!g->b_blocked || g->ldb >= g->N, "cq_gemm_x3: blocked B needs ldb = rows >= N");
     a.tiles_n = ceil_div(g->N, XW_BN);
     a.tiles_m = ceil_div(g->M, XW_BM);
@@ -590,5 +607,3 @@ int cq_gemm_x3(const cq_x3_args* g, void* stream) {
                                as_stream(stream)>>>(a);
     return check_launch("cq_gemm_x3");
 }
-
-}  // extern "C"

@@ -44,6 +44,13 @@ from .overlap import run_to_end
 # --no-transposed-output)
 TRANSPOSED_OUT = True
 
+# once a solve has frozen matrices (solve_iter), every batch-wide step of a full outer iteration
+# gets the live mask and leaves the frozen matrices out (the masked kernel entries: their
+# workgroups return at entry); False: the steps run for the whole batch and the frozen matrices'
+# results are overwritten afterwards, as before (A/B runs, tests/test_gpu_solver_frozen.py).
+# The results are the same bits either way.
+SKIP_FROZEN = True
+
 class _EventProbe:
     """HIP-event timing of the dominant kernel (the G X filter GEMM) on the stream it is
     launched on; used by bench.py inside its timed region (roofline.achieved).  The event
@@ -202,6 +209,8 @@ class SolverStats:
         self.stalls = 0              # matrices whose solve ended at the products' precision floor
         self.refines = 0             # refinement outer iterations run after convergence
         self.segments = 0            # extra filter segments run (segment_capped), over the batch
+        self.frozen_iters = 0        # outer iterations run with a frozen set
+        self.frozen_matrices = 0     # frozen matrices, summed over those iterations
         self.calls = 0
         self.max_resid = 0.0
         self.resid_hist = []
@@ -211,7 +220,7 @@ class SolverStats:
         return dict(outer=self.outer, matvecs=self.matvecs, calls=self.calls,
                     jacobi_unconverged=self.jacobi_unconverged, bj_readbacks=self.bj_readbacks, stalls=self.stalls,
                     max_resid=self.max_resid, x3_fallbacks=self.x3_fallbacks, refines=self.refines,
-                    segments=self.segments)
+                    segments=self.segments, frozen_iters=self.frozen_iters, frozen_matrices=self.frozen_matrices)
 
 
 class RankRSolver:
@@ -283,6 +292,7 @@ class RankRSolver:
         self.x3 = filter_precision == "f16x3" and not self.direct and self.k % 32 == 0
         self._g_blocked = True  # K-blocked G halves: each K step of a tile is one contiguous run
         self._x3f = True        # split-fp16 filter for the current outer iteration
+        self._skip = False      # this outer iteration's batch-wide steps leave the frozen matrices out
         # the first `cheap_cold` outer iterations of a cold solve and the first `cheap_warm`
         # of a warm one filter with one fp16 product (hi x hi, ~2^-11 relative, half the G
         # bytes, a third of the MFMAs): their residual targets (1e-1 ... 4e-4) sit above the
@@ -349,6 +359,11 @@ class RankRSolver:
                 self._ovf = torch.zeros(B, dtype=torch.int32, device=dev)
             self._active = torch.ones(B, dtype=torch.int32, device=dev)
 
+    def _mask(self):
+        """The live mask for a batch-wide step (None: every matrix).  Outside _filter's calls in
+        _more_segments, self._active is the frozen set's complement."""
+        return self._active if self._skip else None
+
     def _free(self, *used):
         for b in self._bufs:
             if all(b is not u for u in used):
@@ -395,27 +410,31 @@ class RankRSolver:
         K-blocked split of out^T, into the iterate halves (cq_gemm_triu_split: one pass instead
         of the product and a transpose-split pass, the same bits)."""
         out = self._free(X, *keep)
-        M = K.gram_f64(X, X)
-        Wt32, _, info = K.spd_whiten(M)
+        act = self._mask()  # (frozen matrices: no Gram, no factor, `out` and the halves not written)
+        M = K.gram_f64(X, X, active=act)
+        Wt32, _, info = K.spd_whiten(M, active=act)
         self._halves_of = None
         if halves and self.x3 and self._x3f and K.triu_split_ok(self.k, self.p):
-            K.gemm_triu_split(X, Wt32, out, self._xh[0], self._xl[0], X3_SCALE)
+            K.gemm_triu_split(X, Wt32, out, self._xh[0], self._xl[0], X3_SCALE, active=act)
             self._halves_of = out
         else:
-            K.gemm(X, Wt32, C=out, b_triu=True)  # Wt upper triangular (zeros stored)
+            K.gemm(X, Wt32, C=out, b_triu=True, active=act)  # Wt upper triangular (zeros stored)
         return out, info
 
     def _ns(self, X, *keep, steps=2):
         """Newton-Schulz re-orthonormalisation of a nearly orthonormal block (see ns_second)."""
         self._halves_of = None
         eye = None
+        act = self._mask()
         for _ in range(steps):
             out = self._free(X, *keep)
-            M = K.gram_f64(X, X)
+            M = K.gram_f64(X, X, active=act)
             if eye is None:
                 eye = torch.eye(self.p, dtype=torch.float64, device=X.device)
+            # (a frozen matrix's M is unwritten memory: its N is arbitrary bits, which the masked
+            # product below never reads)
             N = (1.5 * eye - 0.5 * M).float()
-            K.gemm(X, N, C=out)
+            K.gemm(X, N, C=out, active=act)
             X = out
         return X, None
 
@@ -434,23 +453,27 @@ class RankRSolver:
         cheap iteration needs no eigenvectors, rotations or residuals."""
         G = self._G
         Z = self._free(X, *keep)
+        # frozen matrices are left out of every step (SKIP_FROZEN): their Z, T, theta, V, rotated
+        # blocks and test value are never written, and solve_iter restores them from its snapshot
+        act = self._mask()
         if self.x3:  # Z = G X on split-fp16 products (X orthonormal: no overflow possible)
             if self._halves_of is not X:   # (else the CholQR product wrote them)
-                K.transpose_split(X, hi=self._xh[0], lo=self._xl[0], scale=X3_SCALE, blocked=True)
+                K.transpose_split(X, hi=self._xh[0], lo=self._xl[0], scale=X3_SCALE, blocked=True, active=act)
             self._halves_of = None
             # (TRANSPOSED_OUT: only Z = C^T is read afterwards, so C is not written)
+            # (no D: with a mask this is cq_gemm_x3's skip form -- a frozen matrix's G is not read)
             K.gemm_x3(self._xh[0], self._xl[0], self._Gh, self._Gl, self._ginv, None if TRANSPOSED_OUT else self._xt[0],
                       b_blocked=self._g_blocked, a_blocked=True, single=single and self._x3f,
-                      Ct=Z if TRANSPOSED_OUT else None)
+                      Ct=Z if TRANSPOSED_OUT else None, active=act)
             if not TRANSPOSED_OUT:
-                K.transpose_split(self._xt[0], out=Z)
+                K.transpose_split(self._xt[0], out=Z, active=act)
         else:
-            K.gemm(G, X, ta=True, C=Z)  # Z = G X  (G symmetric: G^T's layout stages faster)
+            K.gemm(G, X, ta=True, C=Z, active=act)  # Z = G X  (G symmetric: G^T's layout stages faster)
         self.stats.matvecs += 1
-        T = K.gram_f64(X, Z)
+        T = K.gram_f64(X, Z, active=act)
         if values_only and self.values_lanczos > 0 and self.p <= 512:
             # only theta_0 and theta_{p-1} are read (filter bounds): Lanczos ends, the rest NaN
-            ends = K.extreme_eigs(T, self.values_lanczos)
+            ends = K.extreme_eigs(T, self.values_lanczos, active=act)
             theta = torch.full((self.B, self.p), math.nan, dtype=torch.float64, device=T.device)
             theta[:, 0] = ends[:, 0]
             theta[:, self.p - 1] = ends[:, 1]
@@ -464,11 +487,11 @@ class RankRSolver:
             self._last_sw = sw
             return theta, X, None
         theta, V32, _, sw = yield from self._eigh(T, self.jacobi_tol)
-        self._last_sw = sw
+        self._last_sw = sw   # (0 for a frozen matrix: never counted as unconverged)
         Xo = self._free(X, Z, *keep)
-        K.gemm(X, V32, C=Xo)
+        K.gemm(X, V32, C=Xo, active=act)
         Zo = self._free(X, Z, Xo, *keep)
-        K.gemm(Z, V32, C=Zo)
+        K.gemm(Z, V32, C=Zo, active=act)
         return theta, Xo, Zo
 
     def _eigh(self, T, tol, want_vectors=True, max_sweeps=None):
@@ -478,9 +501,11 @@ class RankRSolver:
         what the last call needed, so a warm call usually reads back once.  Generator: yields
         before each read-back, so batches interleaved on other streams (overlap.py) keep
         issuing while this one waits."""
+        act = self._mask()
         if not self.block_jacobi:
-            return K.jacobi_eigh(T, max_sweeps=max_sweeps or JACOBI_MAX_SWEEPS, tol=tol, want_vectors=want_vectors)
-        bj = K.BlockJacobi(T, tol, want_vectors)
+            return K.jacobi_eigh(T, max_sweeps=max_sweeps or JACOBI_MAX_SWEEPS, tol=tol, want_vectors=want_vectors,
+                                 active=act)
+        bj = K.BlockJacobi(T, tol, want_vectors, active=act)
         first = min(self.bj_first, JACOBI_MAX_SWEEPS)
         bj.launch(first, begin=True)
         yield
@@ -606,7 +631,12 @@ class RankRSolver:
         # (a single-product filter reads no lo half, the entry's or a step's: none is written;
         # every later reader of the iterate halves -- _rr, _cholqr(halves), split_block_t --
         # writes both halves itself first)
-        K.transpose_split(X, out=xt[0], hi=xh[0], lo=None if single else xl[0], scale=X3_SCALE, blocked=True)
+        # SKIP_FROZEN: an inactive matrix -- frozen, or in _more_segments one whose segments are
+        # done -- is left out of the entry transpose and of every step (cq_gemm_x3_skip: nothing
+        # written) instead of being passed through: the callers overwrite its block anyway
+        skip = self._skip
+        K.transpose_split(X, out=xt[0], hi=xh[0], lo=None if single else xl[0], scale=X3_SCALE, blocked=True,
+                          active=self._active if skip else None)
         fl = 2.0 * self.k * self.k * self.p * self.B
         # bytes a recurrence step moves per matrix: G's halves (4 B/elem) + the iterate's halves
         # in (4pk) + prev, cur in (8pk) + new out (4pk) + new halves out (4pk): 4k^2 + 20pk.  The
@@ -638,7 +668,7 @@ class RankRSolver:
         K.gemm_x3(xh[0], xl[0], self._Gh, self._Gl, self._ginv, o["C"], D=xt[0], alpha_v=coef[0, 0],
                   gamma_v=coef[0, 2], out_h=o["out_h"], out_l=o["out_l"],
                   out_scale=X3_SCALE, overflow=self._ovf, b_blocked=self._g_blocked, active=self._active,
-                  a_blocked=True, o_blocked=True, single=single, Ct=o["Ct"])
+                  a_blocked=True, o_blocked=True, single=single, Ct=o["Ct"], skip=skip)
         EVENT_PROBE.stop(ev)
         self.stats.matvecs += 1
         prev, cur = 0, 1
@@ -650,12 +680,12 @@ class RankRSolver:
                       alpha_v=coef[i, 0], beta_v=coef[i, 1], gamma_v=coef[i, 2],
                       out_h=o["out_h"], out_l=o["out_l"],
                       out_scale=X3_SCALE, overflow=self._ovf, b_blocked=self._g_blocked,
-                      active=self._active, a_blocked=True, o_blocked=True, single=single, Ct=o["Ct"])
+                      active=self._active, a_blocked=True, o_blocked=True, single=single, Ct=o["Ct"], skip=skip)
             EVENT_PROBE.stop(ev)
             self.stats.matvecs += 1
             prev, cur = cur, prev
         if ct is None:
-            K.transpose_split(xt[cur], out=out)
+            K.transpose_split(xt[cur], out=out, active=self._active if skip else None)
         return out
 
     # ------------------------------------------------------------------ main entry
@@ -781,18 +811,30 @@ class RankRSolver:
         used = []
         hist = []                               # per-matrix test values of the full iterations
         stalled = np.zeros(B, dtype=bool)
-        # matrices that passed the test (or stalled) are FROZEN until every matrix has: the
-        # filter passes their block through (active = 0) and the CholQR / Rayleigh-Ritz steps that
-        # still run batch-wide are undone for them by restoring the state they froze with.  A
-        # matrix's result then does not depend on how long its batch-mates take: it is the same
-        # in any batch of the same size (main.py's layers, each with its own Hessian, batched).
+        # matrices that passed the test (or stalled) are FROZEN until every matrix has: every
+        # batch-wide step of the following outer iterations -- the filter, CholQR, the
+        # Rayleigh-Ritz product, Gram, eigensolve and rotations, the test -- gets the live mask
+        # (self._active) and leaves them out: the launches are the same, a frozen matrix's
+        # workgroups return at entry, and its outputs are never written (SKIP_FROZEN; off: the
+        # filter passes its block through and the other steps compute results nobody reads).
+        # Either way its block, products, values and test are then filled in from the state it
+        # froze with, so a matrix's result does not depend on how long its batch-mates take: it is
+        # the same in any batch of the same size (main.py's layers, each with its own Hessian,
+        # batched).  A matrix is only ever frozen after a full iteration, so that state exists.
         frz = None                              # (host mask, device index, X, Z, theta, ends, resid)
+        self._skip = False
         n_outer = 0
         while n_outer < MAX_OUTER:
             d = degs[min(n_outer, len(degs) - 1)]
             n_outer += 1
             self.stats.outer += 1
             cheap = n_outer <= (self.cheap_cold if cold else self.cheap_warm)
+            if frz is not None:
+                self.stats.frozen_iters += 1
+                self.stats.frozen_matrices += int(frz[0].sum())
+            # (a cheap iteration never has a frozen set: freezing follows a full iteration, and a
+            # refinement that reopens the set is made a full one)
+            self._skip = SKIP_FROZEN and frz is not None and not cheap
             if cheap and not cold and self.skip_warm_cheap_rr:
                 coef = self._cheb_coeffs(ends, d, dev)
                 Xf = self._filter(X, coef, single=True)
@@ -832,9 +874,9 @@ class RankRSolver:
                 if cheap:
                     res = torch.full((B,), math.inf, dtype=torch.float64, device=dev)
                 elif self.criterion == "product" and self.r < p:
-                    res = K.ritz_product_error(Xn, Zn, theta_n, self.r, self._ysq).double()
+                    res = K.ritz_product_error(Xn, Zn, theta_n, self.r, self._ysq, active=self._mask()).double()
                 else:
-                    res = K.ritz_residual(Xn, Zn, theta_n, self.r).double()
+                    res = K.ritz_residual(Xn, Zn, theta_n, self.r, active=self._mask()).double()
                 ovf = (self._ovf.max().double() if self.x3 and self._x3f
                        else torch.zeros((), dtype=torch.float64, device=dev))
                 # matrices whose Jacobi used all JACOBI_MAX_SWEEPS (read back with the residuals)
@@ -845,8 +887,10 @@ class RankRSolver:
                 n_unconv = int(chk[-1])
                 chk = chk[:-1]
                 if frz is not None and Zn is not None:
-                    # restore the frozen matrices' block, products, values and test (batch-wide
-                    # CholQR / Rayleigh-Ritz rotated them; an overflow redo keeps them frozen too)
+                    # fill in the frozen matrices' block, products, values and test from the state
+                    # they froze with (SKIP_FROZEN: the masked steps never wrote them; otherwise
+                    # batch-wide CholQR / Rayleigh-Ritz rotated them; an overflow redo keeps them
+                    # frozen too)
                     fm, fi, fX, fZ, fth, fends, fres = frz
                     Xn.index_copy_(0, fi, fX)
                     Zn.index_copy_(0, fi, fZ)
@@ -915,6 +959,7 @@ class RankRSolver:
                        ends.copy(), resid.copy())
             elif live.all():
                 frz = None
+        self._skip = False  # what follows runs for every matrix
         if Z is None:  # left the loop on a values-only iteration (MAX_OUTER): rotate once
             theta, X, Z = yield from self._rr(X)
         self.stats.history.append((cold, used, list(self.stats.resid_hist)))

@@ -333,7 +333,8 @@ typedef struct cq_x3_args {
                                       the diagonal are skipped; the upper triangle is exact */
     int b_blocked;                 /* B halves K-blocked (see cq_sym_split_f16); ldb = rows */
     const int* active;             /* [batch] or NULL: entries with active[b] == 0 skip the
-                                      product and write C = D (and its split) unchanged */
+                                      product and write C = D (and its split) unchanged; with
+                                      D == NULL they write nothing (the skip form, below) */
     int a_blocked;                 /* A halves K-blocked like b_blocked; lda = rows */
     int o_blocked;                 /* out_h/out_l written K-blocked over C's columns (an A
                                       operand of the next product); N % 32 == 0 */
@@ -372,6 +373,49 @@ typedef struct cq_x3_args {
 } cq_x3_args;
 /* C = alpha * (A B^T) + beta * P + gamma * D, per batch coefficient vectors; K % 32 == 0. */
 int cq_gemm_x3(const cq_x3_args* a, void* stream);
+/* The skip form.  cq_gemm_x3 with `active` given and D == NULL (no pass-through value), and
+ * cq_gemm_x3_skip with `active` given (D or not): a matrix with active[b] == 0 is left out
+ * altogether -- its workgroups return at entry, and C, Ct, out_h / out_l, overflow[b],
+ * absmax_out[b] and the split-K partials are not written.  Plain products only (not tri /
+ * sym_out).  The other matrices get the bits of cq_gemm_x3. */
+int cq_gemm_x3_skip(const cq_x3_args* a, void* stream);
+
+/* Masked entries (ABI 5, additive) of the rank-r solver's batch-wide steps: the unmasked entry
+ * with one more argument, `active` -- [batch] int32 on the device, or NULL for all.  A matrix
+ * with active[b] == 0 is left out: every workgroup that belongs to it returns at entry, so none
+ * of its outputs is written (info[b] of the whitening, ends of cq_extreme_eigs, the values and
+ * vectors of the eigensolvers included) and none of its inputs is read (they may hold NaN).
+ * The exceptions are the eigensolvers' sweeps_out[b], which reads 0, and the staged block
+ * Jacobi, where `active` is read by the BJ_BEGIN and BJ_END stages: a masked-out matrix is done
+ * from the start, so pending_out never counts it.  The matrices with active[b] != 0 run the
+ * same instructions on the same data as in the unmasked entry, which passes NULL: the same
+ * bits.  (The solver freezes a matrix that passed its stopping test until the whole batch has:
+ * solver.py, SKIP_FROZEN.)  cq_gemm_f32_masked takes the LINEAR epilogue without syrk. */
+int cq_gram_f64_masked(int64_t M, int64_t N, int64_t K, int64_t batch, const float* A, int trans_a,
+                       int64_t lda, int64_t stride_a, const float* B, int trans_b, int64_t ldb,
+                       int64_t stride_b, double* C, const int* active, void* ws, size_t ws_bytes, void* stream);
+int cq_spd_whiten_masked(double* S, int64_t p, int64_t batch, double rcond2, float* Wt32, double* Wt64, int* info,
+                         const int* active, void* stream);
+int cq_jacobi_eigh_masked(double* A, int64_t p, int64_t batch, int max_sweeps, double tol, double* evals,
+                          float* V32, double* V64, int* sweeps_out, const int* active, void* ws, size_t ws_bytes,
+                          void* stream);
+int cq_jacobi_eigh_staged_masked(double* A, int64_t p, int64_t batch, int phase, int nsweeps, double tol,
+                                 int want_vectors, double* evals, float* V32, double* V64, int* sweeps_out,
+                                 int* pending_out, const int* active, void* ws, size_t ws_bytes, void* stream);
+int cq_extreme_eigs_masked(const double* T, int64_t p, int64_t batch, int steps, double* ends, const int* active,
+                           void* stream);
+int cq_ritz_residual_masked(const float* X, const float* Z, const double* theta, int64_t k, int64_t p,
+                            int64_t r, int64_t batch, float* out, const int* active, void* ws, size_t ws_bytes,
+                            void* stream);
+int cq_ritz_product_error_masked(const float* X, const float* Z, const double* theta, int64_t k, int64_t p, int64_t r,
+                                 int64_t batch, const double* ysq, float* out, const int* active, void* ws,
+                                 size_t ws_bytes, void* stream);
+int cq_gemm_f32_masked(const cq_gemm_args* a, const int* active, void* ws, size_t ws_bytes, void* stream);
+int cq_gemm_triu_split_masked(const float* X, const float* Wt, int64_t M, int64_t p, int64_t batch, float* C,
+                              uint16_t* hi, uint16_t* lo, float scale, const int* active, void* stream);
+int cq_transpose_split_masked(const float* X, int64_t rows, int64_t cols, int64_t batch, float* Y, uint16_t* hi,
+                              uint16_t* lo, float scale, const float* scale_v, int blocked, const int* active,
+                              void* stream);
 
 /* out[b] = max |X[b]| (n_per values, fp16 or fp32), NaN sorting above inf. */
 int cq_absmax(int dtype, const void* X, int64_t n_per, int64_t batch, float* out, void* stream);
