@@ -103,6 +103,15 @@ class LinearPackedArgs(ctypes.Structure):
     ]
 
 
+class HadamardArgs(ctypes.Structure):
+    _fields_ = [
+        ("x", c_vp), ("x_dtype", c_int), ("ldx", c_i64),
+        ("y", c_vp), ("y_dtype", c_int), ("ldy", c_i64),
+        ("rows", c_i64), ("n_in", c_i64), ("n_out", c_i64), ("P", c_i64),
+        ("bias", c_vp),
+    ]
+
+
 _SIGS = {
     "cq_abi_version": (c_int, []),
     "cq_last_error": (ctypes.c_char_p, []),
@@ -185,6 +194,7 @@ _SIGS = {
     "cq_linear_forward": (c_int, [ctypes.POINTER(LinearArgs), c_vp, c_size, c_vp]),
     "cq_linear_packed_workspace": (c_size, [ctypes.POINTER(LinearPackedArgs)]),
     "cq_linear_packed_forward": (c_int, [ctypes.POINTER(LinearPackedArgs), c_vp, c_size, c_vp]),
+    "cq_hadamard_rows": (c_int, [ctypes.POINTER(HadamardArgs), c_vp]),
     # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
     "cq_gemm_x3_skip": (c_int, [ctypes.POINTER(X3Args), c_vp]),
     "cq_gram_f64_masked": (c_int, [c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_i64,
@@ -1335,4 +1345,48 @@ def linear_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, ws=No
     if ws is None:
         ws = workspace(lib.cq_linear_workspace(ctypes.byref(a)), x.device)
     _check(lib.cq_linear_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)), "cq_linear_forward")
+    return y
+
+
+# ---------------------------------------------------------------------------- Hadamard transform
+HADAMARD_MAX_N = 32768  # include/caldera_hip.h CQ_HADAMARD_MAX_N
+
+
+def _hadamard_need(cond, what):
+    if not cond:
+        raise ValueError(f"cq_hadamard_rows: {what}")
+
+
+def hadamard_args(x, y, *, n_in, n_out, P, bias=None) -> HadamardArgs:
+    """cq_hadamard_args for x (rows, n_in) and y (rows, n_out), each fp16 / bf16 / fp32 and
+    possibly a view with a row stride (unit column stride), bias (n_out,) fp32 or None."""
+    need = _hadamard_need
+    for name, t, cols in (("x", x, n_in), ("y", y, n_out)):
+        need(t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1), f"{name} must be a matrix with unit column stride")
+        need(t.dtype in _ACT_DT, f"{name} must be fp16, bf16 or fp32, got {t.dtype}")
+        need(t.shape[1] == cols, f"{name} {tuple(t.shape)} does not have {cols} columns")
+    need(x.shape[0] == y.shape[0], f"x {tuple(x.shape)} and y {tuple(y.shape)} differ in rows")
+    P = int(P)
+    need(1 <= P <= HADAMARD_MAX_N and P & (P - 1) == 0, f"P = {P} is not a power of two in [1, {HADAMARD_MAX_N}]")
+    need(1 <= n_in <= P and 0 <= n_out <= P, f"n_in = {n_in} / n_out = {n_out} do not fit P = {P}")
+    if bias is not None:
+        need(bias.dtype == torch.float32 and tuple(bias.shape) == (n_out,) and bias.is_contiguous(),
+             f"bias must be a contiguous fp32 ({n_out},) vector, got {bias.dtype} {tuple(bias.shape)}")
+    a = HadamardArgs()
+    rows = x.shape[0]
+    a.x, a.x_dtype, a.ldx = x.data_ptr(), _ACT_DT[x.dtype], (x.stride(0) if rows > 1 else max(x.stride(0), n_in))
+    a.y, a.y_dtype, a.ldy = y.data_ptr(), _ACT_DT[y.dtype], (y.stride(0) if rows > 1 else max(y.stride(0), n_out))
+    a.rows, a.n_in, a.n_out, a.P = rows, n_in, n_out, P
+    if bias is not None:
+        a.bias = bias.data_ptr()
+    return a
+
+
+def hadamard_rows(x, y, *, n_in, n_out, P, bias=None):
+    """y[t, :n_out] = (H_P pad(x[t, :n_in]))[:n_out] / sqrt(P) (+ bias): the normalised
+    Sylvester-Hadamard transform of every row (cq_hadamard_rows).  x and y must not overlap.
+    No workspace, no host synchronisation."""
+    _require_hip(x, y, bias)
+    a = hadamard_args(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias)
+    _check(load().cq_hadamard_rows(ctypes.byref(a), _stream(x.device)), "cq_hadamard_rows")
     return y

@@ -303,3 +303,144 @@ class CalderaLinear(torch.nn.Module):
                              self.R if self.rank else None, self.bias, y, m=self.out_features, n=self.in_features,
                              bits=self.bits)
         return y.to(x.dtype).reshape(*x.shape[:-1], self.out_features)
+
+
+def _launch_packed(lin: CalderaLinear, x2: torch.Tensor, y: torch.Tensor):
+    """The entry `CalderaLinear.forward` takes for this layer, on given fp16 x2 (T, in_features)
+    and y (T, out_features): cq_linear_packed_forward with a coded factor, else cq_linear_forward."""
+    if lin.rank and (lin.L_codes is not None or lin.R_codes is not None):
+        K.linear_packed_forward(
+            x2, lin.codes, lin.qscale, lin.gscale, lin.L, lin.R, lin.bias, y, m=lin.out_features,
+            n=lin.in_features, bits=lin.bits, r=lin.rank,
+            L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
+            R_codes=None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits))
+    else:
+        K.linear_forward(x2, lin.codes, lin.qscale, lin.gscale, lin.L if lin.rank else None,
+                         lin.R if lin.rank else None, lin.bias, y, m=lin.out_features, n=lin.in_features,
+                         bits=lin.bits)
+    return y
+
+
+def _next_pow2(n: int) -> int:
+    return 1 << (int(n) - 1).bit_length()
+
+
+class HadamardCalderaLinear(torch.nn.Module):
+    """A layer decomposed in the Hadamard basis (`model.apply_caldera_quantization(packed=True,
+    packed_hadamard=True)`): `inner` is the CalderaLinear of W~ ~ gs (Q + L R) ~ H1 pad(W) H2 on
+    the padded (pr, pc) = (next_pow2(out_features), next_pow2(in_features)) grid, H the
+    normalised Sylvester-Hadamard matrices.  H is symmetric and orthogonal, so
+
+        y = x W^T = (H1 (W~ (H2 pad(x))))[:out_features] + bias
+
+    and forward is three launch groups with no torch arithmetic: cq_hadamard_rows on x (read in
+    its own dtype, written as the fp16 the inner layer takes), the inner layer's packed forward
+    into an fp32 buffer, cq_hadamard_rows on that (+ bias) written in x's dtype.  `inner` may
+    use any Q / factor format CalderaLinear supports and has no bias; `bias` (out_features,)
+    fp32 or None is added by the output transform.  Extra state: in_features, out_features."""
+
+    def __init__(self, inner: CalderaLinear, in_features: int, out_features: int, bias=None):
+        super().__init__()
+        m, n = int(out_features), int(in_features)
+        pr, pc = _next_pow2(m), _next_pow2(n)
+        if pr > K.HADAMARD_MAX_N or pc > K.HADAMARD_MAX_N:
+            raise ValueError(f"HadamardCalderaLinear: padded shape {(pr, pc)} exceeds {K.HADAMARD_MAX_N} "
+                             "(cq_hadamard_rows' largest transform)")
+        if not isinstance(inner, CalderaLinear) or (inner.out_features, inner.in_features) != (pr, pc):
+            raise ValueError(f"HadamardCalderaLinear: inner must be a CalderaLinear of the padded shape {(pr, pc)} "
+                             f"for a {(m, n)} layer, got "
+                             f"{(getattr(inner, 'out_features', None), getattr(inner, 'in_features', None))}")
+        if inner.bias is not None:
+            raise ValueError("HadamardCalderaLinear: the inner layer must have no bias (the output transform adds it)")
+        if bias is not None and tuple(bias.shape) != (m,):
+            raise ValueError(f"HadamardCalderaLinear: bias {tuple(bias.shape)} does not fit ({m},)")
+        self.in_features, self.out_features = n, m
+        self.inner = inner
+        self.register_buffer("bias", None if bias is None else bias.detach().to(torch.float32).contiguous())
+
+    def _apply(self, fn, *args, **kwargs):
+        """As `CalderaLinear._apply`: moves follow the model, dtype casts (`model.half()`) leave the
+        fp32 bias as stored (the inner layer keeps its own operands the same way)."""
+        def keep_dtype(t):
+            out = fn(t)
+            return out if out.dtype == t.dtype else t.to(out.device)
+        return super()._apply(keep_dtype, *args, **kwargs)
+
+    @property
+    def padded_shape(self):
+        return self.inner.out_features, self.inner.in_features
+
+    # ------------------------------------------------------------------ constructors
+    @classmethod
+    def from_decomposition(cls, dec, Q_bits, original_shape, bias=None, L_bits=None, R_bits=None):
+        """From the CalderaDecomposition of H1 pad(W) H2 (as `CalderaLinear.from_decomposition`
+        takes it) and W's own shape (out_features, in_features)."""
+        m, n = (int(v) for v in original_shape)
+        if max(_next_pow2(m), _next_pow2(n)) > K.HADAMARD_MAX_N:
+            raise ValueError(f"HadamardCalderaLinear: padded shape {(_next_pow2(m), _next_pow2(n))} exceeds "
+                             f"{K.HADAMARD_MAX_N} (cq_hadamard_rows' largest transform)")
+        inner = CalderaLinear.from_decomposition(dec, Q_bits, None, L_bits=L_bits, R_bits=R_bits)
+        return cls(inner, n, m, bias)
+
+    @classmethod
+    def from_result(cls, res, bias=None):
+        """From a `sharding.MatrixResult` of the padded layer whose extra["hadamard"] holds the
+        original [out_features, in_features] (what `to_result` writes)."""
+        shape = (res.extra or {}).get("hadamard")
+        if shape is None or len(shape) != 2:
+            raise ValueError(f"HadamardCalderaLinear.from_result: {res.name}: extra has no \"hadamard\": [m, n]")
+        m, n = int(shape[0]), int(shape[1])
+        return cls(CalderaLinear.from_result(res, None), n, m, bias)
+
+    def to_result(self, name: str):
+        """`inner.to_result(name)` (the padded layer) with extra["hadamard"] = [out_features,
+        in_features]; `from_result` inverts it."""
+        res = self.inner.to_result(name)
+        res.extra = dict(res.extra or {})
+        res.extra["hadamard"] = [self.out_features, self.in_features]
+        return res
+
+    # ------------------------------------------------------------------ state
+    def get_extra_state(self):
+        return {"in_features": self.in_features, "out_features": self.out_features}
+
+    def set_extra_state(self, state):
+        for key, v in state.items():
+            setattr(self, key, v)
+
+    def extra_repr(self):
+        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"
+
+    def packed_bytes(self) -> int:
+        """Bytes a forward streams for the weights: the inner layer's (+ bias)."""
+        return self.inner.packed_bytes() + (0 if self.bias is None else self.bias.numel() * self.bias.element_size())
+
+    def dense_weight(self) -> torch.Tensor:
+        """(H1 inner.dense_weight() H2)[:out_features, :in_features] as dense fp32, by torch ops
+        (checks and baselines only)."""
+        from .model import normalized_hadamard
+        Wt = self.inner.dense_weight()
+        pr, pc = self.padded_shape
+        H1, H2 = normalized_hadamard(pr, Wt.device), normalized_hadamard(pc, Wt.device)
+        return (H1 @ Wt @ H2)[:self.out_features, :self.in_features].contiguous()
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not x.is_cuda or not self.inner.codes.is_cuda:
+            raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
+        if x.shape[-1] != self.in_features:
+            raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {self.in_features}")
+        pr, pc = self.padded_shape
+        x2 = x.reshape(-1, self.in_features)
+        if x2.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            x2 = x2.float()
+        if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < self.in_features):
+            x2 = x2.contiguous()
+        T = x2.shape[0]
+        xh = torch.empty((T, pc), dtype=torch.float16, device=x.device)
+        K.hadamard_rows(x2, xh, n_in=self.in_features, n_out=pc, P=pc)
+        y32 = torch.empty((T, pr), dtype=torch.float32, device=x.device)
+        _launch_packed(self.inner, xh, y32)
+        y = torch.empty((T, self.out_features), dtype=x2.dtype, device=x.device)
+        K.hadamard_rows(y32, y, n_in=pr, n_out=self.out_features, P=pr, bias=self.bias)
+        return y.to(x.dtype).reshape(*x.shape[:-1], self.out_features)

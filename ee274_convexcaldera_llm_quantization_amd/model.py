@@ -185,7 +185,8 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                                scale_W: bool = False, hadamard: bool = False, device="cuda",
                                max_batch: int = 64, keep_dtype: bool = True, decompose: Callable | None = None,
                                log: Callable | None = None, hadamard_gate: bool = False,
-                               packed: bool = False, packed_factors: bool = False) -> QuantizationReport:
+                               packed: bool = False, packed_factors: bool = False,
+                               packed_hadamard: bool = False) -> QuantizationReport:
     """main.py:135-251 on the MI355X engine.
 
     hessians: {module name: diagonal (n,) or dense (n, n)} — `Hall` (a missing name raises
@@ -212,10 +213,21 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
       bytes and no second rounding.  Needs packed=True, the uniform LR quantiser
       (`quant_factory_LR.method`) and L_bits, R_bits in {2, 4}; anything else raises ValueError.
       The default keeps fp16 factors.
+    packed_hadamard: with packed=True, decompose H1 pad(W) H2 exactly as `hadamard=True` does
+      (including its ValueError when padding changes n under a Hessian) and replace a layer that
+      passes the error gate by a `linear.HadamardCalderaLinear`: the packed layer of the padded
+      shape between two cq_hadamard_rows transforms, instead of multiplying back into a dense
+      weight.  The gate and the counters are those of packed=True, judged on the recovered
+      (H1 (Q + L R) H2)[:m, :n]; `packed_factors` composes with it.  Needs packed=True; not with
+      `hadamard=True` (that is main.py's dense write-back) and not with `scale_W=True`; a padded
+      dimension above `_lib.HADAMARD_MAX_N` raises ValueError.
     Returns the QuantizationReport (counters + per-layer outcomes)."""
     qp = quant_params if quant_params is not None else driver_params()
+    if packed_hadamard and not packed:
+        raise ValueError("apply_caldera_quantization: packed_hadamard=True needs packed=True")
     if packed and hadamard:
-        raise ValueError("apply_caldera_quantization: packed=True cannot be combined with hadamard=True")
+        raise ValueError("apply_caldera_quantization: packed=True cannot be combined with hadamard=True (the dense "
+                         "write-back of main.py); packed_hadamard=True runs the Hadamard branch packed")
     if packed and scale_W:
         raise ValueError("apply_caldera_quantization: packed=True cannot be combined with scale_W=True (the gate "
                          "and the write-back use Q + L R without the global scale; the packed layer applies it)")
@@ -231,6 +243,13 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                              f"{getattr(qp, 'L_bits', None)} / {getattr(qp, 'R_bits', None)}")
     say = log or (lambda *a: None)
     jobs, rep = select_layers(model, hessians, selection, say)
+    transform = hadamard or packed_hadamard  # decompose H1 pad(W) H2
+    if packed_hadamard:
+        for name, module, _ in jobs:
+            pshape = tuple(_next_pow2(d) for d in module.weight.shape)
+            if max(pshape) > K.HADAMARD_MAX_N:
+                raise ValueError(f"apply_caldera_quantization: packed_hadamard=True: {name}: padded shape {pshape} "
+                                 f"exceeds {K.HADAMARD_MAX_N} (cq_hadamard_rows' largest transform)")
     # batches: same shape; every layer keeps its own Hessian (a list of per-matrix H, or one
     # shared H / None when the whole batch has the same object)
     groups: dict = {}
@@ -246,7 +265,7 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                 Ws, shapes = [], []
                 for name, module, hj in part:
                     W = module.weight.data
-                    if hadamard:  # main.py:224-232: transform, decompose the fp32 transform
+                    if transform:  # main.py:224-232: transform, decompose the fp32 transform
                         if hj is not None and _next_pow2(W.shape[1]) != W.shape[1]:
                             raise ValueError(f"{name}: Hadamard padding changes n ({W.shape[1]}) but H is n x n")
                         Wt, shp = hadamard_transform(W.to(device))
@@ -266,7 +285,7 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                 W = module.weight.data
                 dev = W.device if W.device.type == "cuda" else torch.device(device)
                 out = _reconstruct(dec, dev)
-                if hadamard:
+                if transform:
                     out = hadamard_transform(out, inverse=True, original_shape=shapes[i]).contiguous()
                 err = _rel_error(W.to(dev), out)
                 if hadamard and not hadamard_gate:
@@ -278,12 +297,17 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                     continue
                 ok = err <= error_threshold
                 if ok and packed:
-                    from .linear import CalderaLinear
+                    from .linear import CalderaLinear, HadamardCalderaLinear
                     fbits = dict(L_bits=qp.L_bits, R_bits=qp.R_bits) if packed_factors else {}
-                    lin = CalderaLinear.from_decomposition(dec, qp.Q_bits, bias=getattr(module, "bias", None), **fbits)
+                    bias = getattr(module, "bias", None)
+                    if packed_hadamard:
+                        lin = HadamardCalderaLinear.from_decomposition(dec, qp.Q_bits, shapes[i], bias=bias, **fbits)
+                    else:
+                        lin = CalderaLinear.from_decomposition(dec, qp.Q_bits, bias=bias, **fbits)
                     _set_module(model, name, lin.to(W.device))
                     rep.quantized_param_count += W.numel()
-                    say(f"Applied CALDERA (packed) to {name}.weight, shape: {tuple(W.shape)}")
+                    say(f"Applied CALDERA (packed{', Hadamard' if packed_hadamard else ''}) to {name}.weight, shape: "
+                        f"{tuple(W.shape)}")
                 elif ok:
                     module.weight.data = (out.to(W.dtype) if keep_dtype else out).to(W.device)
                     rep.quantized_param_count += W.numel()
@@ -305,10 +329,12 @@ def _set_module(model: torch.nn.Module, name: str, new: torch.nn.Module):
 
 def apply_packed_results(model: torch.nn.Module, results, device=None) -> list:
     """Replace each `nn.Linear` named by a `sharding.MatrixResult` (e.g. from `load_results`) by
-    a `linear.CalderaLinear` holding that result (the module's bias is kept).  device: where
+    a `linear.CalderaLinear` holding that result (the module's bias is kept); a result whose
+    `extra` has "hadamard": [m, n] (a layer decomposed in the Hadamard basis, on the padded grid)
+    is matched against that original shape and becomes a `linear.HadamardCalderaLinear`.  device: where
     the new layers live (default: each replaced module's own device).  KeyError for a result
     whose module the model does not have; returns the replaced names."""
-    from .linear import CalderaLinear
+    from .linear import CalderaLinear, HadamardCalderaLinear
     modules = dict(model.named_modules())
     done = []
     for res in results:
@@ -316,10 +342,13 @@ def apply_packed_results(model: torch.nn.Module, results, device=None) -> list:
             raise KeyError(f"apply_packed_results: the model has no module {res.name!r}")
         mod = modules[res.name]
         w = getattr(mod, "weight", None)
-        if w is None or tuple(w.shape) != (res.m, res.n):
+        had = (res.extra or {}).get("hadamard")
+        want = (res.m, res.n) if had is None else tuple(int(v) for v in had)
+        if w is None or tuple(w.shape) != want:
             raise ValueError(f"apply_packed_results: {res.name}: weight {None if w is None else tuple(w.shape)} "
-                             f"!= result {(res.m, res.n)}")
-        lin = CalderaLinear.from_result(res, bias=getattr(mod, "bias", None))
+                             f"!= result {want}")
+        cls = CalderaLinear if had is None else HadamardCalderaLinear
+        lin = cls.from_result(res, bias=getattr(mod, "bias", None))
         _set_module(model, res.name, lin.to(w.device if device is None else device))
         done.append(res.name)
     return done

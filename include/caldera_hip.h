@@ -688,6 +688,41 @@ typedef struct cq_linear_packed_args {
 size_t cq_linear_packed_workspace(const cq_linear_packed_args* a);
 int cq_linear_packed_forward(const cq_linear_packed_args* a, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Row-wise normalised Sylvester-Hadamard transform (fast Walsh-Hadamard transform), the
+ * transform around a packed layer that was decomposed in the Hadamard basis (main.py:108-133,
+ * 224-240 decomposes H1 pad(W) H2; H is symmetric and orthogonal, so
+ * y = (H1 (W~ (H2 pad(x))))[:m] + bias with W~ ~ gs (Q + L R) on the padded grid):
+ *
+ *   y[t, i] = c * sum_{j < n_in} (-1)^popcount(i & j) x[t, j] (+ bias[i])      for i < n_out
+ *   c = (float)(1.0 / sqrt((double)P)),   P = 2^p,   1 <= P <= CQ_HADAMARD_MAX_N
+ *
+ * (scipy.linalg.hadamard's ordering.)  Contract:
+ *   - x (rows x n_in, fp16 | bf16 | fp32, row stride ldx elements) is read only in [0, n_in);
+ *     columns n_in .. P count as zero.  y (rows x n_out, fp16 | bf16 | fp32, row stride ldy) is
+ *     written only in [0, n_out).  Whatever lies beyond, inside ldx / ldy, is neither read nor
+ *     written;
+ *   - inputs are widened exactly to fp32 and every butterfly (a, b) -> (a + b, a - b) runs in
+ *     fp32; c is applied once, to the finished sum; bias (n_out fp32, may be NULL) is added
+ *     after that; an fp16 / bf16 output is that fp32 value rounded once (to nearest even);
+ *   - no atomics and a stage order that depends on P alone: a row's bits do not depend on the
+ *     other rows, on `rows`, on the row's index or on the strides;
+ *   - stream-ordered, no allocation, no host synchronisation (graph-capturable), no workspace;
+ *   - x and y must not overlap.
+ * CQ_EINVAL (before any HIP call): P not a power of two or out of range; n_in > P, n_out > P,
+ * n_in < 1 or n_out < 0; rows < 0; an unknown dtype; x, y or bias not aligned to its element; a
+ * row stride below the row.  rows == 0 (or n_out == 0) returns 0 without a launch. */
+#define CQ_HADAMARD_MAX_N 32768
+
+typedef struct cq_hadamard_args {
+    const void* x; int x_dtype; int64_t ldx;   /* fp16 | bf16 | fp32, rows x n_in  */
+    void* y;       int y_dtype; int64_t ldy;   /* fp16 | bf16 | fp32, rows x n_out */
+    int64_t rows, n_in, n_out, P;              /* P = 2^p, 1 <= P <= CQ_HADAMARD_MAX_N */
+    const float* bias;                         /* n_out fp32 or NULL, added after the scale */
+} cq_hadamard_args;
+
+int cq_hadamard_rows(const cq_hadamard_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

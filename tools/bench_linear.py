@@ -18,6 +18,15 @@ times three graphs in the same process, alternating as above: the layer with its
 packed codes (cq_linear_packed_forward), the same layer with those factors stored as fp16
 (cq_linear_forward, the path without this option) and the dense fp16 F.linear.  `copies` is
 sized by the smaller, coded layer.
+
+--hadamard: the layer decomposed in the Hadamard basis (HadamardCalderaLinear: cq_hadamard_rows, the
+packed layer of the padded shape, cq_hadamard_rows).  Shapes 4096^2 and 4096 x 11008 (padded to
+4096 x 16384), 2-bit, r = 128.  Every point times five graphs in the same process, alternating as
+above: the Hadamard layer; the plain CalderaLinear of the padded shape (its inner layer alone, on
+the padded fp16 x); dense fp16 F.linear on the m x n weight; the two transform launches alone; the
+same two transforms as fp16 matmuls x @ H with dense normalised Hadamard matrices (distinct copies
+of H up to the cache size, so H comes from memory like the weights).  Written to --out (default
+profiles/linear_forward_hadamard.txt) as well as printed.
 """
 from __future__ import annotations
 
@@ -166,22 +175,145 @@ def bench_factor_point(m, n, bits, r, T, dev, rounds, factor_bits):
     return out
 
 
+HADAMARD_SHAPES = ((4096, 4096), (4096, 11008))
+
+
+def bench_hadamard_point(m, n, bits, r, T, dev, rounds):
+    """Hadamard layer, its inner layer alone, dense fp16, the two transforms alone, and the two
+    transforms as dense fp16 matmuls; one process, alternating."""
+    import torch.nn.functional as F
+    import copy as _copy
+    import ee274_convexcaldera_llm_quantization_amd._lib as K
+    from ee274_convexcaldera_llm_quantization_amd.linear import HadamardCalderaLinear
+    from ee274_convexcaldera_llm_quantization_amd.model import normalized_hadamard
+    pr, pc = 1 << (m - 1).bit_length(), 1 << (n - 1).bit_length()
+    had = HadamardCalderaLinear(make_layer(pr, pc, bits, r, dev, seed=m + n + bits), n, m, None)
+    pbytes = had.packed_bytes()
+    copies = max(2, int(CACHE_BYTES // pbytes) + 1)
+    layers = [had] + [_copy.deepcopy(had) for _ in range(copies - 1)]
+    w16 = had.dense_weight().half()
+    dense = [w16] + [w16.clone() for _ in range(copies - 1)]
+    g = torch.Generator(device=dev).manual_seed(T)
+    x = torch.randn(T, n, device=dev, generator=g).half()
+    xpad = torch.zeros(T, pc, device=dev, dtype=torch.float16)
+    xpad[:, :n] = x
+    yh, yd = layers[-1](x), F.linear(x, dense[-1])
+    rel = float((yh.float() - yd.float()).norm() / yd.float().norm())
+    assert rel < 2e-2, rel
+    # the transforms alone, on preallocated buffers: x -> xh (fp16), y32 -> y (fp16)
+    xh = torch.empty(T, pc, device=dev, dtype=torch.float16)
+    y32 = torch.randn(T, pr, device=dev, generator=g)
+    y = torch.empty(T, m, device=dev, dtype=torch.float16)
+
+    def transforms(i):
+        K.hadamard_rows(x, xh, n_in=n, n_out=pc, P=pc)
+        K.hadamard_rows(y32, y, n_in=pr, n_out=m, P=pr)
+
+    # the same as matmuls with dense H (fp16; symmetric); distinct copies up to the cache size
+    def h_copies(P):
+        H = normalized_hadamard(P, dev).half()
+        k = min(copies, max(1, int(CACHE_BYTES // (2 * P * P)) + 1))
+        return [H] + [H.clone() for _ in range(k - 1)]
+
+    H2s, H1s = h_copies(pc), h_copies(pr)
+    y16 = y32.half()
+    ref = (xpad.float() @ H2s[0].float())
+    got = torch.empty_like(xh)
+    K.hadamard_rows(x, got, n_in=n, n_out=pc, P=pc)
+    assert float((got.float() - ref).norm() / ref.norm()) < 2e-3
+
+    def matmuls(i):
+        torch.matmul(xpad, H2s[i % len(H2s)])
+        torch.matmul(y16, H1s[i % len(H1s)])
+
+    graphs = [timed_graph(lambda i: layers[i](x), copies), timed_graph(lambda i: layers[i].inner(xpad), copies),
+              timed_graph(lambda i: F.linear(x, dense[i]), copies), timed_graph(transforms, copies),
+              timed_graph(matmuls, copies)]
+    for _ in range(2):
+        for gr in graphs:
+            replay_ms(gr)
+    ts = [[] for _ in graphs]
+    for _ in range(rounds):  # alternate
+        for gr, t in zip(graphs, ts):
+            t.append(replay_ms(gr) / copies)
+    ms = [statistics.median(t) for t in ts]
+    out = dict(m=m, n=n, pr=pr, pc=pc, bits=bits, r=r, T=T, branch="decode" if T <= 16 else "prefill", copies=copies,
+               h_copies=[len(H2s), len(H1s)], hadamard_ms=ms[0], padded_plain_ms=ms[1], dense_ms=ms[2],
+               transforms_ms=ms[3], matmul_transforms_ms=ms[4], hadamard_min_ms=min(ts[0]),
+               padded_plain_min_ms=min(ts[1]), dense_min_ms=min(ts[2]), transforms_min_ms=min(ts[3]),
+               matmul_transforms_min_ms=min(ts[4]), packed_bytes=pbytes, dense_bytes=2 * m * n,
+               hadamard_over_plain=ms[0] / ms[1], dense_over_hadamard=ms[2] / ms[0],
+               matmul_over_kernel=ms[4] / ms[3], rel_diff=rel)
+    del graphs, layers, dense, H2s, H1s
+    torch.cuda.empty_cache()
+    return out
+
+
+def hadamard_main(a, dev):
+    lines = ["# Packed layer in the Hadamard basis (HadamardCalderaLinear) against the plain CalderaLinear of the padded",
+             "# shape, dense fp16 F.linear, its two cq_hadamard_rows launches alone and the same two transforms as fp16",
+             "# matmuls with dense H; one MI355X, one process, the five graphs alternating, median of "
+             f"{a.rounds}; ms per call:",
+             "#   python tools/bench_linear.py --hadamard"]
+    rows = []
+    shapes = [tuple(int(v) for v in s.split("x")) for s in a.shapes]
+    configs = [tuple(int(v) for v in c.split(",")) for c in a.configs]
+    for m, n in shapes:
+        for bits, r in configs:
+            for T in a.tokens:
+                res = bench_hadamard_point(m, n, bits, r, T, dev, a.rounds)
+                rows.append(res)
+                lines.append(json.dumps(res))
+                print(lines[-1], flush=True)
+    table = ["", "| m x n (padded) | bits, r | T | Hadamard layer ms | padded plain ms | dense fp16 ms | 2 transforms ms | "
+             "2 matmul transforms ms | Hadamard / plain | dense / Hadamard | matmul / kernel |",
+             "|---|---|---|---|---|---|---|---|---|---|---|"]
+    for q in rows:
+        table.append(f"| {q['m']} x {q['n']} ({q['pr']} x {q['pc']}) | {q['bits']}, {q['r']} | {q['T']} | "
+                     f"{q['hadamard_ms']:.4f} | {q['padded_plain_ms']:.4f} | {q['dense_ms']:.4f} | "
+                     f"{q['transforms_ms']:.4f} | {q['matmul_transforms_ms']:.4f} | {q['hadamard_over_plain']:.2f} | "
+                     f"{q['dense_over_hadamard']:.2f} | {q['matmul_over_kernel']:.2f} |")
+    gate = [q for q in rows if (q["pr"], q["pc"], q["T"]) == (4096, 4096, 1)]
+    for q in gate:
+        verdict = "faster than" if q["transforms_ms"] < q["matmul_transforms_ms"] else "NOT faster than"
+        table.append(f"\nT = 1, P = 4096: the two transform launches take {q['transforms_ms'] * 1e3:.2f} us, "
+                     f"{verdict} the two fp16 x @ H matmuls on dense 32 MB H ({q['matmul_transforms_ms'] * 1e3:.2f} us).")
+    print("\n".join(table))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write("\n".join(lines + table) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--tokens", type=int, nargs="*", default=list(TOKENS))
-    ap.add_argument("--shapes", type=str, nargs="*", default=[f"{m}x{n}" for m, n in SHAPES])
-    ap.add_argument("--configs", type=str, nargs="*", default=[f"{b},{r}" for b, r in CONFIGS], help="bits,rank")
+    ap.add_argument("--shapes", type=str, nargs="*", default=None,
+                    help=f"m x n (default {' '.join(f'{m}x{n}' for m, n in SHAPES)}; --hadamard: "
+                         f"{' '.join(f'{m}x{n}' for m, n in HADAMARD_SHAPES)})")
+    ap.add_argument("--configs", type=str, nargs="*", default=None,
+                    help=f"bits,rank (default {' '.join(f'{b},{r}' for b, r in CONFIGS)}; --hadamard: 2,128)")
     ap.add_argument("--factor-bits", type=int, default=0, choices=(0, 2, 4),
                     help="L and R as uniform codes of this width: coded vs fp16 factors vs dense (0: fp16 factors only)")
+    ap.add_argument("--hadamard", action="store_true",
+                    help="the Hadamard-basis layer against the padded plain layer, dense fp16 and the transforms alone")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "linear_forward_hadamard.txt"),
+                    help="where --hadamard writes its lines and table")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
+    hshapes, hconfigs = (HADAMARD_SHAPES, ((2, 128),)) if a.hadamard else (SHAPES, CONFIGS)
+    if a.shapes is None:
+        a.shapes = [f"{m}x{n}" for m, n in hshapes]
+    if a.configs is None:
+        a.configs = [f"{b},{r}" for b, r in hconfigs]
     if not torch.cuda.is_available():
         raise SystemExit("bench_linear.py needs a HIP device (no CPU timing)")
     import ee274_convexcaldera_llm_quantization_amd._lib as K
     K.load()
     dev = torch.device(a.device)
     torch.cuda.set_device(dev)
+    if a.hadamard:
+        return hadamard_main(a, dev)
     rows = []
     for shp in a.shapes:
         m, n = (int(v) for v in shp.split("x"))
