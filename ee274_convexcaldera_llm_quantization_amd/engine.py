@@ -562,18 +562,14 @@ class CalderaEngine:
                 self._sg_A = scratch.get("sgram.A", (B, n, n), torch.float32, dev)
                 self._sg = sgram.SparseGram(B, n, m, dev)
                 self._sg_w = None
-                sv._alloc(dev)
+                Gh, Gl = sv.gram_halves(dev)
                 self._wth = scratch.get("lr.wth", (B, m, n), torch.float16, dev)
                 self._wtl = None  # W's halves are exact (lo = 0, sgram.gram_A): b_exact products
                 self._ysw = torch.empty(B, dtype=torch.float32, device=dev)
                 self._wsq = torch.empty(B, dtype=torch.float64, device=dev)
-                gev = GRAM_PROBE.start("gram_A", 1.0 * n * n * m * B, 2.0 * m * n * B + 4.0 * n * n * B)
-                if gev is not None:
-                    gev[0].record()
-                sgram.gram_A(self._wt16, None, 1.0, self._wmax, self._sg_A, sv._Gh, sv._Gl, X3_SCALE, self._yh,
-                             self._yl, ys=self._ysw, wth=self._wth, wtl=self._wtl, wsq=self._wsq)
-                if gev is not None:
-                    gev[1].record()
+                with GRAM_PROBE.timed("gram_A", 1.0 * n * n * m * B, 2.0 * m * n * B + 4.0 * n * n * B):
+                    sgram.gram_A(self._wt16, None, 1.0, self._wmax, self._sg_A, Gh, Gl, X3_SCALE, self._yh,
+                                 self._yl, ys=self._ysw, wth=self._wth, wtl=self._wtl, wsq=self._wsq)
             if tall:
                 ct = scratch.get("sgram.codes_t", st.Qc.shape, torch.uint8, dev)
                 K.codes_transpose(st.Qc, m, n, out=ct)
@@ -585,7 +581,7 @@ class CalderaEngine:
                 self._sg_A = scratch.get("sgram.A", (B, m, m), torch.float32, dev)
                 self._sg = sgram.SparseGram(B, m, n, dev, split=not weighted)
                 self._sg_w = (wts.ycol * wts.ycol).contiguous() if weighted else None
-                sv._alloc(dev)
+                Gh, Gl = sv.gram_halves(dev)
                 if lite:
                     self._wth = scratch.get("lr.wth", (B, n, m), torch.float16, dev)
                     # W^T's halves are exact (lo = 0, sgram.gram_A), not written; diagonal H
@@ -596,15 +592,11 @@ class CalderaEngine:
                 # fp16 MFMA work: one product over the upper half (H = I: W's halves are W and 0),
                 # else the three split products; bytes: the operand halves read once, A written
                 nprod = 3.0 if weighted else 1.0
-                gev = GRAM_PROBE.start("gram_A", nprod * m * m * n * B, (4.0 if weighted else 2.0) * m * n * B
-                                       + 4.0 * m * m * B)
-                if gev is not None:
-                    gev[0].record()
-                sgram.gram_A(Ws, wts.ycol if weighted else None, wts.ycol_max if weighted else 1.0, self._wmax,
-                             self._sg_A, sv._Gh, sv._Gl, X3_SCALE, self._yh, self._yl,
-                             **(dict(ys=self._ysw, wth=self._wth, wtl=self._wtl, wsq=self._wsq) if lite else {}))
-                if gev is not None:
-                    gev[1].record()
+                with GRAM_PROBE.timed("gram_A", nprod * m * m * n * B, (4.0 if weighted else 2.0) * m * n * B
+                                      + 4.0 * m * m * B):
+                    sgram.gram_A(Ws, wts.ycol if weighted else None, wts.ycol_max if weighted else 1.0, self._wmax,
+                                 self._sg_A, Gh, Gl, X3_SCALE, self._yh, self._yl,
+                                 **(dict(ys=self._ysw, wth=self._wth, wtl=self._wtl, wsq=self._wsq) if lite else {}))
             if sparse_g and not tall:
                 # (the codes' norm correction of ||Y||^2 comes with the count where it is used)
                 corr = dict(W=Ws, qscale=st.Qs, wcol=self._sg_w) if lite and self._wth is not None else {}

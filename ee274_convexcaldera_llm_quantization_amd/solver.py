@@ -27,6 +27,9 @@ the only host synchronisation is the convergence test once per outer iteration.
 """
 from __future__ import annotations
 
+import collections
+import contextlib
+import dataclasses
 import math
 import warnings
 
@@ -36,7 +39,6 @@ import torch
 from . import _lib as K
 from . import scratch
 from .overlap import run_to_end
-
 
 
 # the filter's last step and the Rayleigh-Ritz product write X's k x p layout from their epilogue
@@ -156,6 +158,17 @@ class _GroupProbe:
         self.meta.append((kind, flops, nbytes))
         return ev  # recorded by the caller around the kernel launches (_lib.q_update_x3 events=)
 
+    @contextlib.contextmanager
+    def timed(self, kind, flops, nbytes):
+        """start(), with the pair recorded around the body's launches on the current stream;
+        nothing but the body when the probe is off or its pool is full."""
+        ev = self.start(kind, flops, nbytes)
+        if ev is not None:
+            ev[0].record()
+        yield
+        if ev is not None:
+            ev[1].record()
+
     def summary(self):
         if not self.meta:
             return {}
@@ -223,8 +236,135 @@ class SolverStats:
                     segments=self.segments, frozen_iters=self.frozen_iters, frozen_matrices=self.frozen_matrices)
 
 
+_Check = collections.namedtuple("_Check", "overflow top bottom resid n_unconv")
+
+
+def _pack_check(ovf, theta_n, res, unconv):
+    """The one device vector (3 B + 2 fp64 values) an outer iteration reads back: the fp16
+    overflow flag of the filter's iterates, theta_0 and theta_{p-1} per matrix, the stopping
+    test's values, and the count of matrices whose Jacobi used all JACOBI_MAX_SWEEPS."""
+    return torch.cat([ovf.view(1), theta_n[:, 0], theta_n[:, theta_n.shape[1] - 1], res, unconv])
+
+
+def _unpack_check(chk, B):
+    """Its host copy as a _Check (numpy views of one array: _Frozen.restore writes into them)."""
+    chk = chk.cpu().numpy()
+    return _Check(chk[0], chk[1:1 + B], chk[1 + B:1 + 2 * B], chk[1 + 2 * B:1 + 3 * B], int(chk[1 + 3 * B]))
+
+
+def _new_stalls(hist, resid, stalled, tol):
+    """Matrices that reached the precision floor of the split-fp16 products, decided per matrix:
+    one whose test has not improved at all over its last two full iterations (best of the two
+    above STALL_RATIO x its best before them) is done; one still converging, however slowly,
+    keeps iterating (the filter gains far more than 2 % per outer iteration unless the products'
+    rounding dominates).  hist: the full iterations' test values, the last of them `resid`."""
+    if len(hist) < 3:
+        return np.zeros(len(resid), dtype=bool)
+    Hh = np.stack(hist)
+    before = np.min(Hh[:-2], axis=0)
+    recent = np.min(Hh[-2:], axis=0)
+    return (~stalled) & (resid > tol) & np.isfinite(before) & (recent > STALL_RATIO * before)
+
+
+@dataclasses.dataclass(eq=False)
+class _Frozen:
+    """Matrices that passed the test (or stalled) are FROZEN until every matrix has: every
+    batch-wide step of the following outer iterations -- the filter, CholQR, the Rayleigh-Ritz
+    product, Gram, eigensolve and rotations, the test -- gets the live mask (solver._active) and
+    leaves them out: the launches are the same, a frozen matrix's workgroups return at entry, and
+    its outputs are never written (SKIP_FROZEN; off: the filter passes its block through and the
+    other steps compute results nobody reads).  Either way its block, products, values and test
+    are then filled in from the state it froze with, kept here, so a matrix's result does not
+    depend on how long its batch-mates take: it is the same in any batch of the same size
+    (main.py's layers, each with its own Hessian, batched).  A matrix is only ever frozen after
+    a full iteration, so that state exists."""
+    mask: np.ndarray        # host, (B,) bool: True = frozen
+    index: torch.Tensor     # device, the frozen matrices' batch indices; their rows of:
+    X: torch.Tensor
+    Z: torch.Tensor
+    theta: torch.Tensor
+    ends: np.ndarray        # host, the whole batch's (restore reads the frozen rows)
+    resid: np.ndarray
+
+    @classmethod
+    def take(cls, live, X, Z, theta, ends, resid, dev):
+        mask = ~live
+        index = torch.from_numpy(np.nonzero(mask)[0]).to(dev)
+        return cls(mask, index, X.index_select(0, index), Z.index_select(0, index), theta.index_select(0, index),
+                   ends.copy(), resid.copy())
+
+    @staticmethod
+    def update(frozen, live, X, Z, theta, ends, resid, dev):
+        """The frozen set after an outer iteration that left `live` matrices: none when all are
+        live, a new snapshot when the set grew (or a refinement reopened it), else as it was."""
+        if live.all():
+            return None
+        if frozen is None or (frozen.mask != ~live).any():
+            return _Frozen.take(live, X, Z, theta, ends, resid, dev)
+        return frozen
+
+    def restore(self, Xn, Zn, theta_n, check):
+        """Fill in the frozen rows of an iteration's results (SKIP_FROZEN: the masked steps never
+        wrote them; otherwise batch-wide CholQR and Rayleigh-Ritz rotated them).  Returns theta."""
+        Xn.index_copy_(0, self.index, self.X)
+        Zn.index_copy_(0, self.index, self.Z)
+        m = self.mask
+        check.top[m] = self.ends[m, 0]
+        check.bottom[m] = self.ends[m, 1]
+        check.resid[m] = self.resid[m]
+        return theta_n.index_copy(0, self.index, self.theta)
+
+
 class RankRSolver:
-    """Top-r eigenpairs of the Gram of a batch of matrices, warm-started across calls."""
+    """Top-r eigenpairs of the Gram of a batch of matrices, warm-started across calls.
+
+    Keyword options, kept as attributes of the same names:
+
+    p: block size; by default ~1.4 r rounded up to a multiple of 32: at r = 128 this is p = 192,
+      the largest block whose fp64 Rayleigh-Ritz matrix fits the 160 KB LDS of one CU
+      (cq_jacobi_eigh register/LDS path) and one 192-wide GEMM tile; same GEMM cost to tolerance
+      as p = 2r (solver tuning).
+    jacobi_tol, jacobi_tol_values: Jacobi off-norm tolerances (relative to the diagonal), tuned at
+      config 2 B = 256 (profiles/r01i_tune_jacobi_tol*.log): the full Rayleigh-Ritz at 1e-7 (1e-5
+      stalls the Ritz residuals, 1e-6 leaves a thin margin), the values-only one at 1e-2
+      (eigenvalue errors ~1e-4 relative are ample for filter bounds): 243 -> 259 matrices/s.
+    jacobi_values_sweeps: sweep cap of the values-only eigensolves (cheap iterations: the Ritz
+      values only set the next filter's bounds).
+    values_lanczos: the cheap iterations' filter bounds (the two ends of the Ritz spectrum) from
+      this many Lanczos steps on T (cq_extreme_eigs, one launch, no read-back) instead of a
+      values-only eigensolve; 0: the eigensolve (p > 512 always).
+    cheap_cold, cheap_warm: the first `cheap_cold` outer iterations of a cold solve and the first
+      `cheap_warm` of a warm one filter with one fp16 product (hi x hi, ~2^-11 relative, half the
+      G bytes, a third of the MFMAs): their residual targets (1e-1 ... 4e-4) sit above the ~1.5e-4
+      floor of that filter, and the following split-fp16 steps damp its error like any other
+      unwanted component; the Rayleigh-Ritz products stay split-fp16, so the convergence test is
+      exact (tools/tune_solver.py, config 2: (10, 7) warm degrees with one cheap outer iteration
+      converge in two outer iterations per call, 6% faster).
+    skip_warm_cheap_rr: a warm solve's cheap outer iterations skip Rayleigh-Ritz: their filter
+      bounds are the previous call's converged Ritz values (the residual moved by <1%), their
+      convergence test could never pass (single-product floor), and the subspace does not depend
+      on the basis, so the G X product, Jacobi and rotations of that step are dropped.  None: on
+      for latency batches (B <= LATENCY_BATCH) only: measured at config 2 (B = 256) the stale
+      bounds cost later warm calls a third outer iteration (131 vs 121 G products per step, 243.6
+      vs 244.1 matrices/s).
+    ns_second: CholQR2's second pass (and the final re-orthonormalisation) as Newton-Schulz steps
+      X <- X (3 I - X^T X) / 2 (fp64 Gram, one fp32 product each) instead of a whitening: the
+      block after one CholQR pass is orthonormal to ~eps32 cond(X) <= ~1e-2, two steps take that
+      to the fp32 floor (error^2 per step) -- the same subspace without the whitening's chain of
+      32-pivot panels on one CU (0.2 ms at p = 192).  None: for latency batches, where that chain
+      is the critical path (one caldera() call), not for large ones (there the whitening costs
+      less than the two Grams and products that replace it).
+    segment_capped: a requested filter degree the amplification cap cuts runs as several segments
+      with a CholQR pass between them, inside one outer iteration (False: the cut degree and more
+      outer iterations).
+    cheap_one_pass: cheap (values-only) outer iterations: one CholQR pass instead of two -- the
+      block only feeds the next filter and the two ends of a Lanczos spectrum, for which
+      orthonormality to eps32 * cond(filtered block) is plenty (fp64 Gram).  Config 2: +1.7-2.0 %
+      (320.9 -> 326.4, 323.3 -> 329.8 matrices/s), pinned / exact-LR / held-out parity at B = 256
+      unchanged at 11/16, 15/16, 27/32 (tools/ab_solver_kw.py, profiles/r06ba_*, r06bb_*); at
+      B = 64 (test_gpu_holdout.py) the held-out classes move from 26 / 30 / 2 misses to 28 / 28 /
+      2 misses (bit-exact vs the reference / vs exact LR / in no class: profiles/r06bi_holdout.log,
+      r06bc_gpu_suite_onepass.log) -- two more seeds on the reference's own codes."""
 
     def __init__(self, B: int, m: int, n: int, r: int, device, *, p: int | None = None,
                  tol: float = 1e-5, deg_cold=(6, 12, 12, 12, 12, 12, 12), deg_warm=(10, 7, 6, 6, 6, 6),
@@ -238,10 +378,6 @@ class RankRSolver:
         self.left = m <= n  # G = Y Y^T -> eigenvectors are left singular vectors
         self.r = min(r, self.k)
         if p is None:
-            # block size ~1.4 r rounded up to a multiple of 32: at r = 128 this is p = 192,
-            # the largest block whose fp64 Rayleigh-Ritz matrix fits the 160 KB LDS of one CU
-            # (cq_jacobi_eigh register/LDS path) and one 192-wide GEMM tile; same GEMM cost to
-            # tolerance as p = 2r (solver tuning).
             p = max(int(1.4 * self.r) + 4, self.r + 16)
             p = (p + 31) // 32 * 32
         p = p + (p & 1)
@@ -254,31 +390,21 @@ class RankRSolver:
         self.deg_cold, self.deg_warm = tuple(deg_cold), tuple(deg_warm)
         self.device = device
         self.seed = seed
-        # Jacobi off-norm tolerances (relative to the diagonal), tuned at config 2 B = 256
-        # (profiles/r01i_tune_jacobi_tol*.log): the full Rayleigh-Ritz at 1e-7 (1e-5 stalls the
-        # Ritz residuals, 1e-6 leaves a thin margin), the values-only one at 1e-2 (eigenvalue
-        # errors ~1e-4 relative are ample for filter bounds): 243 -> 259 matrices/s
         self.jacobi_tol = jacobi_tol
         self.jacobi_tol_values = jacobi_tol_values
-        # sweep cap of the values-only eigensolves (cheap iterations: the Ritz values only set
-        # the next filter's bounds)
         self.jacobi_values_sweeps = int(jacobi_values_sweeps)
-        # the cheap iterations' filter bounds (the two ends of the Ritz spectrum) from this many
-        # Lanczos steps on T (cq_extreme_eigs, one launch, no read-back) instead of a values-only
-        # eigensolve; 0: the eigensolve (p > 512 always)
         self.values_lanczos = int(VALUES_LANCZOS if values_lanczos is None else values_lanczos)
         self.refine = ()   # extra full outer iterations after convergence (per call; engine.py)
         self.X = None      # warm-start Ritz block (B, k, p)
         self.theta = None  # its Ritz values (B, p) fp64: filter bounds for the next call
         self.stats = SolverStats()
         self.valid_k = self.k  # rows >= valid_k of the eigenproblem are zero padding (engine.py)
-        # Rayleigh-Ritz sweep budget: fixed for the one-workgroup Jacobi (its sweep loop runs
-        # inside one kernel), adaptive for the block Jacobi (each sweep is a set of launches)
-        # block Jacobi over many workgroups where one CU cannot hold the problem (p > 192), and
-        # for batches whose 64 x 64 subproblems (p / 64 per matrix) do not outnumber the CUs,
-        # where the one-workgroup-per-matrix kernel (~4 ms per 192 x 192 eigensolve on one CU)
-        # would leave most of the chip idle: one caldera() call, config 4's batches of 64, the
-        # 8-GPU model run's batches of 16
+        # block Jacobi over many workgroups (adaptive sweep budget: each sweep is a set of launches)
+        # where one CU cannot hold the problem (p > 192), and for batches whose 64 x 64
+        # subproblems (p / 64 per matrix) do not outnumber the CUs, where the one-workgroup-per-
+        # matrix kernel (~4 ms per 192 x 192 eigensolve, its sweep loop inside the kernel) would
+        # leave most of the chip idle: one caldera() call, config 4's batches of 64, the 8-GPU
+        # model run's batches of 16
         nblk = -(-self.p // 32)
         self.block_jacobi = self.p > 192 or B * ((nblk + (nblk & 1)) // 2) <= BJ_SMALL_SUBPROBLEMS
         self.bj_first = BJ_FIRST  # block Jacobi: sweeps launched before the first read-back
@@ -290,51 +416,35 @@ class RankRSolver:
             raise ValueError(f"filter_precision must be 'f16x3' or 'f32', got {filter_precision!r}")
         # split-fp16 filter needs K (= k) a multiple of 32 and 16-byte aligned rows
         self.x3 = filter_precision == "f16x3" and not self.direct and self.k % 32 == 0
-        self._g_blocked = True  # K-blocked G halves: each K step of a tile is one contiguous run
-        self._x3f = True        # split-fp16 filter for the current outer iteration
-        self._skip = False      # this outer iteration's batch-wide steps leave the frozen matrices out
-        # the first `cheap_cold` outer iterations of a cold solve and the first `cheap_warm`
-        # of a warm one filter with one fp16 product (hi x hi, ~2^-11 relative, half the G
-        # bytes, a third of the MFMAs): their residual targets (1e-1 ... 4e-4) sit above the
-        # ~1.5e-4 floor of that filter, and the following split-fp16 steps damp its error like
-        # any other unwanted component; the Rayleigh-Ritz products stay split-fp16, so the
-        # convergence test is exact (tools/tune_solver.py, config 2: (10, 7) warm degrees with
-        # one cheap outer iteration converge in two outer iterations per call, 6% faster)
+        self._begin_solve(None)
         self.cheap_cold = int(cheap_cold)
         self.cheap_warm = int(cheap_warm)
-        # a warm solve's cheap outer iterations skip Rayleigh-Ritz: their filter bounds are the
-        # previous call's converged Ritz values (the residual moved by <1%), their convergence
-        # test could never pass (single-product floor), and the subspace does not depend on the
-        # basis, so the G X product, Jacobi and rotations of that step are dropped.  Off by
-        # default: measured at config 2 (B = 256) the stale bounds cost later warm calls a third
-        # outer iteration (131 vs 121 G products per step, 243.6 vs 244.1 matrices/s)
-        # (None: on for latency batches, below)
         self.latency = B <= LATENCY_BATCH
         self.skip_warm_cheap_rr = self.latency if skip_warm_cheap_rr is None else bool(skip_warm_cheap_rr)
-        # CholQR2's second pass (and the final re-orthonormalisation) as Newton-Schulz steps
-        # X <- X (3 I - X^T X) / 2 (fp64 Gram, one fp32 product each) instead of a whitening: the
-        # block after one CholQR pass is orthonormal to ~eps32 cond(X) <= ~1e-2, two steps take that
-        # to the fp32 floor (error^2 per step) -- the same subspace without the whitening's chain of
-        # 32-pivot panels on one CU (0.2 ms at p = 192): for latency batches, where that chain is
-        # the critical path (one caldera() call), not for large ones (there the whitening costs
-        # less than the two Grams and products that replace it)
         self.ns_second = self.latency if ns_second is None else bool(ns_second)
-        # a requested filter degree the amplification cap cuts runs as several segments with a
-        # CholQR pass between them, inside one outer iteration (round 6; False: the cut degree
-        # and more outer iterations, as through round 5)
         self.segment_capped = bool(segment_capped)
-        # cheap (values-only) outer iterations: one CholQR pass instead of two -- the block only
-        # feeds the next filter and the two ends of a Lanczos spectrum, for which orthonormality
-        # to eps32 * cond(filtered block) is plenty (fp64 Gram).  Config 2: +1.7-2.0 % (320.9 ->
-        # 326.4, 323.3 -> 329.8 matrices/s), pinned / exact-LR / held-out parity at B = 256
-        # unchanged at 11/16, 15/16, 27/32 (tools/ab_solver_kw.py, profiles/r06ba_*, r06bb_*);
-        # at B = 64 (test_gpu_holdout.py) the held-out classes move from 26 / 30 / 2 misses to
-        # 28 / 28 / 2 misses (bit-exact vs the reference / vs exact LR / in no class:
-        # profiles/r06bi_holdout.log, r06bc_gpu_suite_onepass.log) -- two more seeds on the
-        # reference's own codes
         self.cheap_one_pass = bool(cheap_one_pass)
 
     # ------------------------------------------------------------------ buffers
+    def _begin_solve(self, Y):
+        """The state that lives for one solve_iter call (X, theta and _ends, the warm start,
+        outlive it)."""
+        self._Y = Y                 # for an fp32 G after an fp16 overflow (_fill_G)
+        self._y_halves = None       # (hi, lo, scale) of the Gram operand, when G came from them
+        self._gram_fill = None      # the caller's fill(Gh, Gl, gscale, ginv, G32=None), when it forms G
+        self._ysq = None            # ||Y||_F^2 = trace(G), for the product-error test
+        self._g_fp32_valid = False  # self._G holds this solve's G
+        self._x3f = True            # split-fp16 filter for the current outer iteration
+        self._skip = False          # this outer iteration's batch-wide steps leave the frozen matrices out
+        self._last_sw = None        # sweeps of the last Rayleigh-Ritz eigensolve, per matrix
+        self._eff_deg = None        # the last filter's capped degree, per matrix (_cheb_coeffs)
+
+    def gram_halves(self, dev):
+        """G's K-blocked split-fp16 halves (Gh, Gl), allocated if need be: between solves a
+        caller that forms G itself (solve_iter's gram=) may use them as scratch (sgram.gram_A)."""
+        self._alloc(dev)
+        return self._Gh, self._Gl
+
     def _alloc(self, dev):
         B, k, p = self.B, self.k, self.p
         if self._bufs is None:
@@ -390,19 +500,21 @@ class RankRSolver:
 
     def _fill_G(self, Y):
         """fp32 G = Y Y^T (m <= n) or Y^T Y: from the Gram operand's split halves when the
-        caller provided them (Y itself may not exist in fp32), else on the fp32 MFMA GEMM."""
+        caller provided them (Y itself may not exist in fp32), else on the fp32 MFMA GEMM.  The
+        split-fp16 path has no fp32 G until it needs one: allocated here."""
+        if self._G is None:
+            self._G = torch.empty((self.B, self.k, self.k), dtype=torch.float32, device=Y.device)
         if self._gram_fill is not None:  # caller-formed G (sgram.py): its fp32 form
             self._gram_fill(self._Gh, self._Gl, self._gscale, self._ginv, G32=self._G)
-            return
-        if self._y_halves is not None:
+        elif self._y_halves is not None:
             yh, yl, ys = self._y_halves
             K.gemm_x3(yh, yl, yh, yl, 1.0 / (ys * ys), self._G, tri=True, a_blocked=True, b_blocked=True)
             self._G.copy_(torch.triu(self._G) + torch.triu(self._G, 1).transpose(1, 2))
-            return
-        if self.left:
+        elif self.left:
             K.gemm(Y, Y, tb=True, C=self._G, syrk=True)
         else:
             K.gemm(Y, Y, ta=True, C=self._G, syrk=True)
+        self._g_fp32_valid = True
 
     # ------------------------------------------------------------------ steps
     def _cholqr(self, X, *keep, halves=False):
@@ -445,12 +557,13 @@ class RankRSolver:
         return self._cholqr(X, *keep, halves=halves)
 
     def _rr(self, X, *keep, single=False, values_only=False):
-        """Rayleigh-Ritz on the block X (generator: yields before the block Jacobi's read-backs).  single: Z = G X with one fp16 product (cheap outer
-        iterations: the Ritz values only set the next filter's bounds, and the residuals it
-        reports sit at the ~1.5e-4 floor of that product, far above the tolerance, so no
-        matrix can be declared converged on them).  values_only: Ritz values only, X returned
-        unrotated and Z = None — the next filter sees the same subspace either way, so a
-        cheap iteration needs no eigenvectors, rotations or residuals."""
+        """Rayleigh-Ritz on the block X (generator: yields before the block Jacobi's read-backs).
+        single: Z = G X with one fp16 product (cheap outer iterations: the Ritz values only set
+        the next filter's bounds, and the residuals it reports sit at the ~1.5e-4 floor of that
+        product, far above the tolerance, so no matrix can be declared converged on them).
+        values_only: Ritz values only, X returned unrotated and Z = None — the next filter sees
+        the same subspace either way, so a cheap iteration needs no eigenvectors, rotations or
+        residuals."""
         G = self._G
         Z = self._free(X, *keep)
         # frozen matrices are left out of every step (SKIP_FROZEN): their Z, T, theta, V, rotated
@@ -463,7 +576,7 @@ class RankRSolver:
             # (TRANSPOSED_OUT: only Z = C^T is read afterwards, so C is not written)
             # (no D: with a mask this is cq_gemm_x3's skip form -- a frozen matrix's G is not read)
             K.gemm_x3(self._xh[0], self._xl[0], self._Gh, self._Gl, self._ginv, None if TRANSPOSED_OUT else self._xt[0],
-                      b_blocked=self._g_blocked, a_blocked=True, single=single and self._x3f,
+                      b_blocked=True, a_blocked=True, single=single and self._x3f,
                       Ct=Z if TRANSPOSED_OUT else None, active=act)
             if not TRANSPOSED_OUT:
                 K.transpose_split(self._xt[0], out=Z, active=act)
@@ -607,15 +720,12 @@ class RankRSolver:
         fl = 2.0 * self.k * self.k * self.p * self.B
         nb = float(self.B) * (4.0 * self.k * self.k + 16.0 * self.p * self.k)
         kn = "gemm_f32_kernel (fp32 G X, Chebyshev filter)"
-        ev = EVENT_PROBE.start(fl, nb, kn)
-        K.gemm(G, X0, ta=True, C=Y1, D=X0, alpha_v=coef[0, 0], gamma_v=coef[0, 2])
-        EVENT_PROBE.stop(ev)
-        self.stats.matvecs += 1
-        prev, cur = X0, Y1
-        for i in range(1, deg):
-            # prev <- a G cur + b prev + c cur
+        prev, cur = Y1, X0
+        for i in range(deg):
+            # prev <- a G cur + b prev + c cur (the first step: no b)
             ev = EVENT_PROBE.start(fl, nb, kn)
-            K.gemm(G, cur, ta=True, C=prev, D=cur, alpha_v=coef[i, 0], beta_v=coef[i, 1], gamma_v=coef[i, 2])
+            K.gemm(G, cur, ta=True, C=prev, D=cur, alpha_v=coef[i, 0], beta_v=coef[i, 1] if i else None,
+                   gamma_v=coef[i, 2])
             EVENT_PROBE.stop(ev)
             self.stats.matvecs += 1
             prev, cur = cur, prev
@@ -662,24 +772,14 @@ class RankRSolver:
                 return dict(C=xt[c], out_h=xh[c], out_l=None if single else xl[c], Ct=None)
             return dict(C=xt[c] if ct is None else None, out_h=None, out_l=None, Ct=ct)
 
-        last = deg == 1
-        o = outputs(last, 1)
-        ev = probe(fl, nb_last if last else nb_mid, kn)
-        K.gemm_x3(xh[0], xl[0], self._Gh, self._Gl, self._ginv, o["C"], D=xt[0], alpha_v=coef[0, 0],
-                  gamma_v=coef[0, 2], out_h=o["out_h"], out_l=o["out_l"],
-                  out_scale=X3_SCALE, overflow=self._ovf, b_blocked=self._g_blocked, active=self._active,
-                  a_blocked=True, o_blocked=True, single=single, Ct=o["Ct"], skip=skip)
-        EVENT_PROBE.stop(ev)
-        self.stats.matvecs += 1
-        prev, cur = 0, 1
-        for i in range(1, deg):
+        prev, cur = 1, 0
+        for i in range(deg):  # (the first step has no previous iterate: no P, no beta)
             last = i == deg - 1
             o = outputs(last, prev)
             ev = probe(fl, nb_last if last else nb_mid, kn)
-            K.gemm_x3(xh[cur], xl[cur], self._Gh, self._Gl, self._ginv, o["C"], P=xt[prev], D=xt[cur],
-                      alpha_v=coef[i, 0], beta_v=coef[i, 1], gamma_v=coef[i, 2],
-                      out_h=o["out_h"], out_l=o["out_l"],
-                      out_scale=X3_SCALE, overflow=self._ovf, b_blocked=self._g_blocked,
+            K.gemm_x3(xh[cur], xl[cur], self._Gh, self._Gl, self._ginv, o["C"], P=xt[prev] if i else None, D=xt[cur],
+                      alpha_v=coef[i, 0], beta_v=coef[i, 1] if i else None, gamma_v=coef[i, 2],
+                      out_h=o["out_h"], out_l=o["out_l"], out_scale=X3_SCALE, overflow=self._ovf, b_blocked=True,
                       active=self._active, a_blocked=True, o_blocked=True, single=single, Ct=o["Ct"], skip=skip)
             EVENT_PROBE.stop(ev)
             self.stats.matvecs += 1
@@ -700,84 +800,149 @@ class RankRSolver:
         (cq_residual_split).  gram: optional dict(fill, ysq) -- the caller forms G itself
         (sgram.py): fill(Gh, Gl, gscale, ginv, G32=None) writes G's K-blocked split halves
         (and fp32 G when asked), ysq = ||Y||_F^2; Y is then not read."""
-        B, k, p = self.B, self.k, self.p
-        dev = Y.device
+        B, dev = self.B, Y.device
         self.stats.calls += 1
         if self.direct:
             Gd = K.gram_f64(Y, Y, ta=True, tb=True) if self.left else K.gram_f64(Y, Y)
             theta, V32, _, _ = K.jacobi_eigh(Gd)
             return V32[:, :, : self.r], theta[:, : self.r]
+        self._begin_solve(Y)
         self._alloc(dev)
-        self._g_upper_only = False
-        self._Y = Y
-        self._y_halves = None
-        g_split = False
-        self._gram_fill = None
+        self._form_gram(Y, y_split, gram)
+        cold = not (warm and self.X is not None)
+        X, theta, ends, Z, degs = yield from self._start(cold, dev)
+        self.stats.resid_hist = []
+        # refinement: after every matrix passed the test, `refine` more full outer iterations
+        # (filter of degree refine[i], CholQR2, Rayleigh-Ritz) for the whole batch -- set per
+        # call by the engine (its first LR steps decide the kept Q's codes, DESIGN.md §6)
+        refine = list(self.refine or ())
+        used = []
+        hist = []                               # per-matrix test values of the full iterations
+        stalled = np.zeros(B, dtype=bool)
+        frozen = None                           # the matrices that sit out (_Frozen)
+        n_cheap = self.cheap_cold if cold else self.cheap_warm
+        n_outer = 0
+        while n_outer < MAX_OUTER:
+            d = degs[min(n_outer, len(degs) - 1)]
+            n_outer += 1
+            self.stats.outer += 1
+            cheap = n_outer <= n_cheap
+            if frozen is not None:
+                self.stats.frozen_iters += 1
+                self.stats.frozen_matrices += int(frozen.mask.sum())
+            # (a cheap iteration never has a frozen set: freezing follows a full iteration, and a
+            # refinement that reopens the set is made a full one)
+            self._skip = SKIP_FROZEN and frozen is not None and not cheap
+            if cheap and not cold and self.skip_warm_cheap_rr:
+                Xb = yield from self._cheap_warm_iteration(X, d, ends)
+                if Xb is not None:
+                    X = Xb
+                    used.append(d)
+                    continue
+            theta, X, Z, check = yield from self._full_iteration(X, d, ends, cheap, cold, frozen)
+            ends = np.stack([check.top, check.bottom], 1)
+            resid = check.resid
+            mr = float(resid.max())
+            self.stats.max_resid = mr
+            self.stats.resid_hist.append(mr)
+            used.append(d)
+            if math.isfinite(mr) or np.isfinite(resid).any():
+                hist.append(resid.copy())
+            new_stall = _new_stalls(hist, resid, stalled, self.tol)
+            self.stats.stalls += int(new_stall.sum())
+            if new_stall.any():
+                # the split-fp16 products' precision floor sits above the tolerance for these
+                # matrices (an input whose dynamic range erodes the fp32-grade margin): the
+                # rank-r projection is then only as accurate as the residual reached
+                warnings.warn(f"rank-r solver: {int(new_stall.sum())} matrices stopped at the product "
+                              f"precision floor above tolerance {self.tol:g} (residual estimate "
+                              f"{float(resid[new_stall].max()):.2e})", RuntimeWarning, stacklevel=2)
+            stalled |= new_stall
+            # converged (or stalled) matrices sit out the remaining filter products (X passes through)
+            live = (resid > self.tol) & ~stalled
+            if not live.any() and refine:
+                degs = (refine.pop(0),)
+                n_outer = max(n_outer, n_cheap)  # a full iteration
+                live = np.ones(B, dtype=bool)
+                self.stats.refines += 1
+            self._active.copy_(torch.from_numpy(live.astype(np.int32)))
+            if not live.any():
+                break
+            frozen = _Frozen.update(frozen, live, X, Z, theta, ends, resid, dev)
+        return (yield from self._finish(X, Z, theta, ends, cold, used))
+
+    # ------------------------------------------------------------------ the solve's parts
+    def _form_gram(self, Y, y_split, gram):
+        """G = Y Y^T (m <= n) or Y^T Y as the filter reads it, ||Y||_F^2 = trace(G) for the
+        product-error test, every matrix live: from the caller (gram=), on split-fp16 products
+        from the operand's halves (y_split, or the solver's own split of Y), or in fp32."""
         if gram is not None:
             assert self.x3, "solver: a caller-formed Gram needs the split-fp16 path"
             self._gram_fill = gram["fill"]
             self._ysq = gram["ysq"]
             # algorithmic bytes of the sparse Gram: W and its codes once (E slabs), P written
             # and read back, A's upper triangle, G's split halves written
-            kk, nn = k, Y.shape[1] + Y.shape[2] - k
-            gev = GRAM_PROBE.start("gram_sparse", 0.0, B * (2.25 * kk * nn + 14.0 * kk * kk))
-            if gev is not None:
-                gev[0].record()
-            self._gram_fill(self._Gh, self._Gl, self._gscale, self._ginv)
-            if gev is not None:
-                gev[1].record()
-            g_split = True
+            kk, nn = self.k, Y.shape[1] + Y.shape[2] - self.k
+            with GRAM_PROBE.timed("gram_sparse", 0.0, self.B * (2.25 * kk * nn + 14.0 * kk * kk)):
+                self._gram_fill(self._Gh, self._Gl, self._gscale, self._ginv)
         elif self.x3 and (self.n if self.left else self.m) % 32 == 0:
-            # G = Y Y^T (or Y^T Y) on split-fp16 products, Y scaled per matrix by a power of two;
-            # the Gram writes G's K-blocked split halves itself (scale from ||Y||_F^2 >= max|G|)
-            ysq = None
-            if y_split is not None:
-                yh, yl, ys, ysq = y_split
-                # the Gram operand: Y (k x n) when m <= n, Y^T (k x m) otherwise
-                assert yh.shape == (B, k, Y.shape[1] + Y.shape[2] - k), "solver: Gram operand halves misshaped"
+            self._gram_split(Y, y_split)
+        else:
+            return self._gram_f32(Y)
+        self._active.fill_(1)
+        self._ovf.zero_()
+
+    def _gram_f32(self, Y):
+        """fp32 G on the fp32 MFMA GEMM (Y Y^T: upper tiles + mirror): for the fp32 filter, or
+        split into G's halves afterwards (a Gram operand whose K is no multiple of 32)."""
+        if not self.x3:
+            self._fill_G(Y)
+        self._active.fill_(1)
+        self._ysq = K.weighted_sqsum(Y, None, Y.shape[2])
+        if self.x3:
+            self._fill_G(Y)
+            K.sym_split_f16(self._G, X3_SCALE, hi=self._Gh, lo=self._Gl, scale=self._gscale,
+                            inv_scale=self._ginv, upper_only=False, blocked=True)
+            self._ovf.zero_()
+
+    def _gram_split(self, Y, y_split):
+        """G on split-fp16 products, Y scaled per matrix by a power of two; the Gram writes G's
+        K-blocked split halves itself (scale from ||Y||_F^2 >= max|G|)."""
+        B, k = self.B, self.k
+        dev = Y.device
+        ysq = None
+        if y_split is not None:
+            yh, yl, ys, ysq = y_split
+            # the Gram operand: Y (k x n) when m <= n, Y^T (k x m) otherwise
+            assert yh.shape == (B, k, Y.shape[1] + Y.shape[2] - k), "solver: Gram operand halves misshaped"
+        else:
+            if self._yh is None:
+                yshape = (B, k, Y.shape[1] + Y.shape[2] - k)
+                self._yh = scratch.get("solver.yh", yshape, torch.float16, dev)
+                self._yl = scratch.get("solver.yl", yshape, torch.float16, dev)
+                self._ys = torch.empty(B, dtype=torch.float32, device=dev)
+            yh, yl, ys = self._yh, self._yl, self._ys
+            K.pow2_scale(Y, 14, out=ys)
+            if self.left:
+                K.split_f16(Y, ys, hi=yh, lo=yl, blocked=True)
             else:
-                if self._yh is None:
-                    yshape = (B, k, Y.shape[1] + Y.shape[2] - k)
-                    self._yh = scratch.get("solver.yh", yshape, torch.float16, dev)
-                    self._yl = scratch.get("solver.yl", yshape, torch.float16, dev)
-                    self._ys = torch.empty(B, dtype=torch.float32, device=dev)
-                yh, yl, ys = self._yh, self._yl, self._ys
-                K.pow2_scale(Y, 14, out=ys)
-                if self.left:
-                    K.split_f16(Y, ys, hi=yh, lo=yl, blocked=True)
-                else:
-                    K.transpose_split(Y, hi=yh, lo=yl, scale=ys, blocked=True)
-            yinv = 1.0 / (ys * ys)
-            self._y_halves = (yh, yl, ys)
-            if ysq is None:
-                ysq = K.weighted_sqsum(Y, None, Y.shape[2])
-            self._ysq = ysq
-            # fp16 MFMA work issued: 3 products x k^2 n (the upper half of the symmetric 2 k^2 n)
-            kk, nn = k, yh.shape[2]
-            gev = GRAM_PROBE.start("gram", 3.0 * kk * kk * nn * B, 4.0 * kk * nn * B + 4.0 * kk * kk * B)
-            if gev is not None:
-                gev[0].record()
+                K.transpose_split(Y, hi=yh, lo=yl, scale=ys, blocked=True)
+        yinv = 1.0 / (ys * ys)
+        self._y_halves = (yh, yl, ys)
+        if ysq is None:
+            ysq = K.weighted_sqsum(Y, None, Y.shape[2])
+        self._ysq = ysq
+        # fp16 MFMA work issued: 3 products x k^2 n (the upper half of the symmetric 2 k^2 n)
+        kk, nn = k, yh.shape[2]
+        with GRAM_PROBE.timed("gram", 3.0 * kk * kk * nn * B, 4.0 * kk * nn * B + 4.0 * kk * kk * B):
             K.gemm_x3(yh, yl, yh, yl, yinv, None, tri=True, a_blocked=True, b_blocked=True,
                       out_h=self._Gh, out_l=self._Gl, out_scale=X3_SCALE, sym_bound=ysq,
                       scale_out=self._gscale, inv_out=self._ginv)
-            if gev is not None:
-                gev[1].record()
-            g_split = True
-        elif not self.x3:
-            self._fill_G(Y)  # Y Y^T (upper tiles + mirror) or Y^T Y
-        self._active.fill_(1)
-        if not g_split:
-            self._ysq = K.weighted_sqsum(Y, None, Y.shape[2])  # trace(G) for the product-error test
-        if self.x3:
-            if not g_split:
-                if self._G is None:
-                    self._G = torch.empty((B, k, k), dtype=torch.float32, device=dev)
-                self._fill_G(Y)
-                K.sym_split_f16(self._G, X3_SCALE, hi=self._Gh, lo=self._Gl, scale=self._gscale,
-                                inv_scale=self._ginv, upper_only=False, blocked=self._g_blocked)
-            self._g_fp32_valid = not g_split
-            self._ovf.zero_()
-        cold = not (warm and self.X is not None)
+
+    def _start(self, cold, dev):
+        """The block a solve starts from (generator): (X, theta, ends, Z, degs) -- a cold one
+        with its Ritz values read back, or the previous call's with the bounds kept on the host."""
+        B, k, p = self.B, self.k, self.p
         if cold:
             # same start block for every matrix: a matrix's result does not depend on its
             # position in the batch or on how the batch is split across streams
@@ -792,173 +957,90 @@ class RankRSolver:
             theta, X, Z = yield from self._rr(X, single=self.cheap_cold > 0, values_only=self.cheap_cold > 0)
             ends = torch.stack([theta[:, 0], theta[:, p - 1]], 1)
             yield
-            ends = ends.cpu().numpy()
-            degs = self.deg_cold
-        else:
-            # previous Ritz block (kept in self.X, never handed out by the pool) and values:
-            # orthonormal, and its Ritz values bound the new spectrum closely (the residual
-            # changes in <1% of its entries between updates)
-            X = self.X
-            theta = self.theta
-            ends = self._ends
-            Z = None
-            degs = self.deg_warm
-        self.stats.resid_hist = []
-        # refinement: after every matrix passed the test, `refine` more full outer iterations
-        # (filter of degree refine[i], CholQR2, Rayleigh-Ritz) for the whole batch -- set per
-        # call by the engine (its first LR steps decide the kept Q's codes)
-        refine = list(self.refine or ())
-        used = []
-        hist = []                               # per-matrix test values of the full iterations
-        stalled = np.zeros(B, dtype=bool)
-        # matrices that passed the test (or stalled) are FROZEN until every matrix has: every
-        # batch-wide step of the following outer iterations -- the filter, CholQR, the
-        # Rayleigh-Ritz product, Gram, eigensolve and rotations, the test -- gets the live mask
-        # (self._active) and leaves them out: the launches are the same, a frozen matrix's
-        # workgroups return at entry, and its outputs are never written (SKIP_FROZEN; off: the
-        # filter passes its block through and the other steps compute results nobody reads).
-        # Either way its block, products, values and test are then filled in from the state it
-        # froze with, so a matrix's result does not depend on how long its batch-mates take: it is
-        # the same in any batch of the same size (main.py's layers, each with its own Hessian,
-        # batched).  A matrix is only ever frozen after a full iteration, so that state exists.
-        frz = None                              # (host mask, device index, X, Z, theta, ends, resid)
-        self._skip = False
-        n_outer = 0
-        while n_outer < MAX_OUTER:
-            d = degs[min(n_outer, len(degs) - 1)]
-            n_outer += 1
-            self.stats.outer += 1
-            cheap = n_outer <= (self.cheap_cold if cold else self.cheap_warm)
-            if frz is not None:
-                self.stats.frozen_iters += 1
-                self.stats.frozen_matrices += int(frz[0].sum())
-            # (a cheap iteration never has a frozen set: freezing follows a full iteration, and a
-            # refinement that reopens the set is made a full one)
-            self._skip = SKIP_FROZEN and frz is not None and not cheap
-            if cheap and not cold and self.skip_warm_cheap_rr:
-                coef = self._cheb_coeffs(ends, d, dev)
-                Xf = self._filter(X, coef, single=True)
-                if B <= SEGMENTS_SMALL_BATCH:
-                    Xf = self._more_segments(Xf, X, d, coef, True, ends)
-                Xa, _ = self._cholqr(Xf, X)
-                Xb, _ = self._orth2(Xa, X)
-                ok = True
-                if self.x3:  # an fp16 overflow of a single-product iterate: redo this outer
-                    ovf = self._ovf.max()  # iteration on the regular path below (fp32 fallback)
-                    yield
-                    ok = int(ovf.item()) == 0
-                    self._ovf.zero_()
-                if ok:
-                    X = Xb
-                    used.append(d)
-                    continue
-            while True:
-                coef = self._cheb_coeffs(ends, d, dev)
-                # a widely spread spectrum caps the degree (FILTER_MAX_AMP): in the full
-                # iterations the rest of the requested degree runs as further segments, each after
-                # a CholQR pass that re-conditions the block (the same subspace), instead of as
-                # further outer iterations with a Rayleigh-Ritz eigensolve and a read-back each.
-                # (Not in the cheap ones: their bounds are a cold block's or the previous call's,
-                # and a cold block's loose ends cap flat spectra too -- config 2's first iterations)
-                Xf = self._filter(X, coef, single=cheap)
-                # (a warm solve's cheap iteration too in small batches, SEGMENTS_SMALL_BATCH)
-                if not cheap or (not cold and B <= SEGMENTS_SMALL_BATCH):
-                    Xf = self._more_segments(Xf, X, d, coef, cheap, ends)
-                Xa, _ = self._cholqr(Xf, X)
-                Xb = Xa if (cheap and self.cheap_one_pass) else self._orth2(Xa, X, halves=True)[0]
-                theta_n, Xn, Zn = yield from self._rr(Xb, X, single=cheap, values_only=cheap)
-                # (B,) per-matrix max residual; a cheap iteration cannot converge (see _rr)
-                # stopping test: estimated relative error of the rank-r projection of Y (a
-                # residual relative to theta_0 over-converges flat spectra and under-converges
-                # activation-weighted ones); "theta0": the max Ritz residual / theta_0
-                if cheap:
-                    res = torch.full((B,), math.inf, dtype=torch.float64, device=dev)
-                elif self.criterion == "product" and self.r < p:
-                    res = K.ritz_product_error(Xn, Zn, theta_n, self.r, self._ysq, active=self._mask()).double()
-                else:
-                    res = K.ritz_residual(Xn, Zn, theta_n, self.r, active=self._mask()).double()
-                ovf = (self._ovf.max().double() if self.x3 and self._x3f
-                       else torch.zeros((), dtype=torch.float64, device=dev))
-                # matrices whose Jacobi used all JACOBI_MAX_SWEEPS (read back with the residuals)
-                unconv = (self._last_sw >= JACOBI_MAX_SWEEPS).sum().double().view(1)
-                chk = torch.cat([ovf.view(1), theta_n[:, 0], theta_n[:, p - 1], res, unconv])
-                yield
-                chk = chk.cpu().numpy()
-                n_unconv = int(chk[-1])
-                chk = chk[:-1]
-                if frz is not None and Zn is not None:
-                    # fill in the frozen matrices' block, products, values and test from the state
-                    # they froze with (SKIP_FROZEN: the masked steps never wrote them; otherwise
-                    # batch-wide CholQR / Rayleigh-Ritz rotated them; an overflow redo keeps them
-                    # frozen too)
-                    fm, fi, fX, fZ, fth, fends, fres = frz
-                    Xn.index_copy_(0, fi, fX)
-                    Zn.index_copy_(0, fi, fZ)
-                    theta_n = theta_n.index_copy(0, fi, fth)
-                    chk[1:1 + B][fm] = fends[fm, 0]
-                    chk[1 + B:1 + 2 * B][fm] = fends[fm, 1]
-                    chk[1 + 2 * B:][fm] = fres[fm]
-                self.stats.jacobi_unconverged += n_unconv
-                if self.x3 and self._x3f and chk[0] != 0:
-                    # an fp16 half overflowed (a Ritz value far below the true top of the
-                    # spectrum, cold start): redo this outer iteration with the fp32 filter
-                    self._x3f = False
-                    self._ovf.zero_()
-                    self.stats.x3_fallbacks += 1
-                    if not self._g_fp32_valid:  # the fp32 products need G itself
-                        if self._G is None:
-                            self._G = torch.empty((B, k, k), dtype=torch.float32, device=dev)
-                        self._fill_G(self._Y)
-                        self._g_fp32_valid = True
-                    continue
-                break
-            self._x3f = True
-            theta, X, Z = theta_n, Xn, Zn
-            ends = np.stack([chk[1:1 + B], chk[1 + B:1 + 2 * B]], 1)
-            resid = chk[1 + 2 * B:]
-            mr = float(resid.max())
-            self.stats.max_resid = mr
-            self.stats.resid_hist.append(mr)
-            used.append(d)
-            if math.isfinite(mr) or np.isfinite(resid).any():
-                hist.append(resid.copy())
-            # precision floor (split-fp16 products), decided per matrix: a matrix whose test has
-            # not improved at all over its last two outer iterations (best of the two above
-            # STALL_RATIO x its best before them) is done; one still converging, however
-            # slowly, keeps iterating (the filter gains far more than 2 % per outer iteration
-            # unless the products' rounding dominates)
-            if len(hist) >= 3:
-                Hh = np.stack(hist)
-                before = np.min(Hh[:-2], axis=0)
-                recent = np.min(Hh[-2:], axis=0)
-                new_stall = (~stalled) & (resid > self.tol) & np.isfinite(before) & (recent > STALL_RATIO * before)
-                self.stats.stalls += int(new_stall.sum())
-                if new_stall.any():
-                    # the split-fp16 products' precision floor sits above the tolerance for these
-                    # matrices (an input whose dynamic range erodes the fp32-grade margin): the
-                    # rank-r projection is then only as accurate as the residual reached
-                    warnings.warn(f"rank-r solver: {int(new_stall.sum())} matrices stopped at the product "
-                                  f"precision floor above tolerance {self.tol:g} (residual estimate "
-                                  f"{float(resid[new_stall].max()):.2e})", RuntimeWarning, stacklevel=2)
-                stalled |= new_stall
-            # converged (or stalled) matrices sit out the remaining filter products (X passes through)
-            live = (resid > self.tol) & ~stalled
-            if not live.any() and refine:
-                degs = (refine.pop(0),)
-                n_outer = max(n_outer, self.cheap_cold if cold else self.cheap_warm)  # a full iteration
-                live = np.ones(B, dtype=bool)
-                self.stats.refines += 1
-            self._active.copy_(torch.from_numpy(live.astype(np.int32)))
-            if not live.any():
-                break
-            if (~live).any() and (frz is None or (frz[0] != ~live).any()):
-                # the frozen set grew (or a refinement reopened it): snapshot the frozen rows
-                fm = ~live
-                fi = torch.from_numpy(np.nonzero(fm)[0]).to(dev)
-                frz = (fm, fi, X.index_select(0, fi), Z.index_select(0, fi), theta.index_select(0, fi),
-                       ends.copy(), resid.copy())
-            elif live.all():
-                frz = None
+            return X, theta, ends.cpu().numpy(), Z, self.deg_cold
+        # previous Ritz block (kept in self.X, never handed out by the pool) and values:
+        # orthonormal, and its Ritz values bound the new spectrum closely (the residual
+        # changes in <1% of its entries between updates)
+        return self.X, self.theta, self._ends, None, self.deg_warm
+
+    def _cheap_warm_iteration(self, X, d, ends):
+        """A warm solve's cheap outer iteration without Rayleigh-Ritz (skip_warm_cheap_rr;
+        generator): the filtered, re-orthonormalised block, or None when an fp16 half of a
+        single-product iterate overflowed -- the iteration is then redone on the regular path
+        (_full_iteration, fp32 fallback)."""
+        coef = self._cheb_coeffs(ends, d, X.device)
+        Xf = self._filter(X, coef, single=True)
+        if self.B <= SEGMENTS_SMALL_BATCH:
+            Xf = self._more_segments(Xf, X, d, coef, True, ends)
+        Xa, _ = self._cholqr(Xf, X)
+        Xb, _ = self._orth2(Xa, X)
+        if self.x3:
+            ovf = self._ovf.max()
+            yield
+            ok = int(ovf.item()) == 0
+            self._ovf.zero_()
+            if not ok:
+                return None
+        return Xb
+
+    def _full_iteration(self, X, d, ends, cheap, cold, frozen):
+        """One outer iteration with Rayleigh-Ritz (generator): filter of degree d (in segments
+        where the cap binds), CholQR2, Rayleigh-Ritz, the stopping test, and the iteration's one
+        read-back; redone with the fp32 filter if an fp16 half of an iterate overflowed.  Returns
+        (theta, X, Z, check), the frozen matrices' rows as they froze."""
+        B, dev = self.B, X.device
+        while True:
+            coef = self._cheb_coeffs(ends, d, dev)
+            # a widely spread spectrum caps the degree (FILTER_MAX_AMP): in the full
+            # iterations the rest of the requested degree runs as further segments, each after
+            # a CholQR pass that re-conditions the block (the same subspace), instead of as
+            # further outer iterations with a Rayleigh-Ritz eigensolve and a read-back each.
+            # (Not in the cheap ones: their bounds are a cold block's or the previous call's,
+            # and a cold block's loose ends cap flat spectra too -- config 2's first iterations)
+            Xf = self._filter(X, coef, single=cheap)
+            # (a warm solve's cheap iteration too in small batches, SEGMENTS_SMALL_BATCH)
+            if not cheap or (not cold and B <= SEGMENTS_SMALL_BATCH):
+                Xf = self._more_segments(Xf, X, d, coef, cheap, ends)
+            Xa, _ = self._cholqr(Xf, X)
+            Xb = Xa if (cheap and self.cheap_one_pass) else self._orth2(Xa, X, halves=True)[0]
+            theta_n, Xn, Zn = yield from self._rr(Xb, X, single=cheap, values_only=cheap)
+            res = self._test(cheap, Xn, Zn, theta_n)
+            ovf = (self._ovf.max().double() if self.x3 and self._x3f
+                   else torch.zeros((), dtype=torch.float64, device=dev))
+            # matrices whose Jacobi used all JACOBI_MAX_SWEEPS (read back with the residuals)
+            unconv = (self._last_sw >= JACOBI_MAX_SWEEPS).sum().double().view(1)
+            chk = _pack_check(ovf, theta_n, res, unconv)
+            yield
+            check = _unpack_check(chk, B)
+            if frozen is not None and Zn is not None:  # (an overflow redo keeps them frozen too)
+                theta_n = frozen.restore(Xn, Zn, theta_n, check)
+            self.stats.jacobi_unconverged += check.n_unconv
+            if not (self.x3 and self._x3f and check.overflow != 0):
+                self._x3f = True
+                return theta_n, Xn, Zn, check
+            # an fp16 half overflowed (a Ritz value far below the true top of the spectrum, cold
+            # start): redo this outer iteration with the fp32 filter
+            self._x3f = False
+            self._ovf.zero_()
+            self.stats.x3_fallbacks += 1
+            if not self._g_fp32_valid:  # the fp32 products need G itself
+                self._fill_G(self._Y)
+
+    def _test(self, cheap, Xn, Zn, theta_n):
+        """The stopping test's (B,) fp64 values: the estimated relative error of the rank-r
+        projection of Y (a residual relative to theta_0 over-converges flat spectra and
+        under-converges activation-weighted ones); criterion "theta0": the max Ritz residual /
+        theta_0.  A cheap iteration cannot converge (see _rr): inf."""
+        if cheap:
+            return torch.full((self.B,), math.inf, dtype=torch.float64, device=Xn.device)
+        if self.criterion == "product" and self.r < self.p:
+            return K.ritz_product_error(Xn, Zn, theta_n, self.r, self._ysq, active=self._mask()).double()
+        return K.ritz_residual(Xn, Zn, theta_n, self.r, active=self._mask()).double()
+
+    def _finish(self, X, Z, theta, ends, cold, used):
+        """The end of a solve (generator): the last rotation if it is missing, one
+        re-orthonormalisation, and the block, its values and bounds kept as the next call's warm
+        start.  Returns (vecs (B, k, r), theta (B, r))."""
         self._skip = False  # what follows runs for every matrix
         if Z is None:  # left the loop on a values-only iteration (MAX_OUTER): rotate once
             theta, X, Z = yield from self._rr(X)
@@ -972,7 +1054,7 @@ class RankRSolver:
         i = next(j for j, t in enumerate(self._bufs) if t is X)
         old = self.X
         if old is None or any(t is old for t in self._bufs):  # never two pool slots on one tensor
-            old = torch.empty((B, k, p), dtype=torch.float32, device=dev)
+            old = torch.empty((self.B, self.k, self.p), dtype=torch.float32, device=X.device)
         self._bufs[i], self.X = old, X
         self.theta = theta.clone()
         self._ends = ends
