@@ -32,6 +32,15 @@ bias 1: 9 <= 32, so the constant stands.
 x[0, 0], x[0, n - 1] and (T > 1) x[1, 0] carry the largest magnitude of the case's x (random
 cases), as in linear_cases.py.  At (33, 64, 8) row q < min(T, r) of rho follows the signs of x[q] and
 row q of l is k_L e_q, so y[q, q]'s factor term is one z~ without cancellation.
+
+Long-K decode cases ((48, 2600, 40) and (33, 8454, 40), see linear_cases.py): the exact ones take x
+from -1..1, which keeps |z~| <= 0.5 * 7 * 8454 = 29589 inside fp16 and the absolute sums below 2^24
+units; row 0 of x is all ones but x[0, 1] = 0 (z~[0, 0] stays zscale times an odd integer), and
+c[0, 8 CK + 1] = k so that "stale_x", which swaps x[0, 1] in there, shows at T = 1.  The random
+ones plant y[0, 0] as in linear_cases.py: over wave 0's second chunk row 0 of the layer's codes is
+k sign(x[0]) and row 0 of rho is k_R sign(x[0]) (0.3 sign(x[0]) for fp16 R), and row 0 of l is
+k_L e_0 (0.45 e_0 for fp16 L).  The loop faults "drop_chunk", "stale_x", "drop_R_chunk" and
+"stale_x_R" are those of linear_cases.py, with the z product's chunk 256 columns for 2-bit R.
 """
 from dataclasses import dataclass
 
@@ -76,9 +85,9 @@ class Case:
                 + self.T + {"exact": 0, "exact16": 1, "random": 2}[self.kind] * 7919)
 
 
-SHAPES = [(33, 64, 8), (48, 198, 40), (80, 898, 200), (48, 198, 264), (272, 512, 16)]
+SHAPES = [(33, 64, 8), (48, 198, 40), (80, 898, 200), (48, 198, 264), (272, 512, 16), (48, 2600, 40), (33, 8454, 40)]
 _T = {(33, 64, 8): (1, 5, 17), (48, 198, 40): (5, 16, 64), (80, 898, 200): (1, 16, 17), (48, 198, 264): (5, 16, 64),
-      (272, 512, 16): (16, 130)}
+      (272, 512, 16): (16, 130), (48, 2600, 40): (1, 16), (33, 8454, 40): (5, 16)}
 
 
 def _shapes():
@@ -91,6 +100,8 @@ def _shapes():
         for bits in ((4, 4, 4), (2, 2, 4), (2, 4, 16), (2, 16, 4)):
             for T in (16, 17 if shp[0] == 80 else 64):
                 out.append((*shp, *bits, T))
+    for bits in ((4, 4, 4), (2, 4, 16), (2, 16, 4)):  # decode K loops past one chunk per wave
+        out.append((33, 8454, 40, *bits, 16))
     return out
 
 
@@ -100,6 +111,16 @@ RANDOM = [Case("random", *s) for s in _shapes()] + [Case("random", 33, 64, 8, 2,
 ALL = EXACT + EXACT16 + RANDOM
 
 _CACHE = {}
+
+
+def _xa(case):
+    """The largest |x| of an exact case."""
+    return 4 if case.kind == "exact" and case.n <= LC.LONG_N else 1
+
+
+def _z_chunk(case):
+    """Columns of the second chunk of the z product's first slot, or None."""
+    return LC.second_chunk(case, case.rb, LC.DECODE_WAVES_Z * LC.DECODE_SPLIT_Z)
 
 
 def inputs(case: Case):
@@ -125,7 +146,7 @@ def inputs(case: Case):
     if random:
         x = rng.standard_normal((T, n)).astype(f16)
     else:
-        xa = 4 if case.kind == "exact" else 1
+        xa = _xa(case)
         x = rng.integers(-xa, xa + 1, (T, n)).astype(f16)
     l, sl = factor(case.lb, (m, r))
     rho, sr = factor(case.rb, (r, n))
@@ -142,14 +163,27 @@ def inputs(case: Case):
                 rho[q, :] = np.where(x[q].astype(f64) >= 0, case.kr, -case.kr)
                 l[q, :] = 0
                 l[q, q] = case.kl
+        if n > LC.LONG_N and T <= LC.DECODE_MAX_TOKENS:
+            # y[0, 0] hangs on wave 0's second chunk of both products without cancellation
+            lo, hi = LC.second_chunk(case, case.bits, LC.DECODE_WAVES)
+            c[0, lo:hi] = (case.k * LC._sign(x[0, lo:hi])).astype(np.int8)
+            l[0, :] = 0
+            l[0, 0] = case.kl if case.lb != 16 else f16(0.45)
+            zc = _z_chunk(case)
+            if zc:
+                sg = LC._sign(x[0, zc[0]:zc[1]])
+                rho[0, zc[0]:zc[1]] = ((case.kr * sg).astype(np.int8) if case.rb != 16
+                                       else (0.3 * sg).astype(f16))
     else:
         s, gs = f32(case.k / 2), f32(4.0)
         bias = (rng.integers(-8, 9, m) * 0.5).astype(f32) if case.bias else None
         if case.kind == "exact":   # z~[0, 0] = zscale * (an odd multiple of the largest rho), l[0, 0] != 0
             x[0, :] = xa
-            x[0, 0] = xa - 1
+            x[0, 0 if xa > 1 else 1] = xa - 1         # not x[0, 0] = 0: "flip_R" needs it at T = 1
             rho[0, :] = case.kr if case.rb != 16 else fa
             l[0, 0] = case.kl if case.lb != 16 else fa
+            if n > LC.LONG_N and T <= LC.DECODE_MAX_TOKENS:
+                c[0, LC.second_chunk(case, case.bits, LC.DECODE_WAVES)[0] + 1] = case.k
     out = dict(x=x, c=c, l=l, rho=rho, s=s, sl=sl, sr=sr, gs=gs, bias=bias)
     _CACHE[case] = out
     return out
@@ -168,7 +202,8 @@ def scales(case: Case, d=None):
     return sk, z
 
 
-FAULTS = ("flip_L", "flip_R", "L_transposed", "sl_for_skl", "drop_zscale", "pad_L", "z16")
+LOOP_FAULTS = ("drop_chunk", "stale_x", "drop_R_chunk", "stale_x_R")
+FAULTS = ("flip_L", "flip_R", "L_transposed", "sl_for_skl", "drop_zscale", "pad_L", "z16") + LOOP_FAULTS
 
 
 def fault_applies(case: Case, fault: str) -> bool:
@@ -176,6 +211,10 @@ def fault_applies(case: Case, fault: str) -> bool:
     random = case.kind == "random"
     if case.kind == "exact16":
         return False
+    if fault in ("drop_chunk", "stale_x"):      # a wave of the code product has a second chunk
+        return LC.second_chunk(case, case.bits, LC.DECODE_WAVES) is not None
+    if fault in ("drop_R_chunk", "stale_x_R"):  # ... of the z product
+        return _z_chunk(case) is not None
     if fault in ("flip_L", "L_transposed", "sl_for_skl", "pad_L") and case.lb == 16:
         return False
     if fault == "flip_R" and case.rb == 16:
@@ -196,7 +235,7 @@ def fault_applies(case: Case, fault: str) -> bool:
             return (case.m, case.n, case.r) == (33, 64, 8) and case.lb != 16 and case.rb != 16
         if case.rb == 16:
             return False
-        return case.kr * (case.n * 4 - 1) >= 2048   # z~[0, 0] / zscale: an odd integer, see inputs()
+        return case.kr * (case.n * _xa(case) - 1) >= 2048   # z~[0, 0] / zscale: an odd integer, see inputs()
     return True
 
 
@@ -209,7 +248,8 @@ def reference(case: Case, fault: str | None = None):
     fault: one planted error (FAULTS), for checking that the cases can see it.  "L_transposed"
     reads the (m, r) codes as if they lay in L^T order; "pad_L" models a nonzero code (k_L) in
     row 0's first pad column meeting a z pad column that holds z~ of the last R row (what a
-    row-clamped z product leaves there); "z16" rounds z~ once to fp16."""
+    row-clamped z product leaves there); "z16" rounds z~ once to fp16.  The loop faults act on
+    wave 0's second chunk as in linear_cases.py: row 0 of the layer's codes, all rows of rho."""
     d = inputs(case)
     x, c, l, rho = (d[key].astype(f64) for key in ("x", "c", "l", "rho"))
     sk, zscale = (f64(v) for v in scales(case, d))
@@ -225,13 +265,25 @@ def reference(case: Case, fault: str | None = None):
         zscale = f64(f32(d["sl"]) * (f32(d["sr"] / f32(case.kr)) if case.rb != 16 else f32(1.0)))
     elif fault == "drop_zscale":
         zscale = f64(1.0)
-    z = zscale * (x @ rho.T)
+    z = x @ rho.T
+    if fault in ("drop_R_chunk", "stale_x_R"):
+        lo, hi = _z_chunk(case)
+        z -= x[:, lo:hi] @ rho[:, lo:hi].T
+        if fault == "stale_x_R":
+            z += x[:, :hi - lo] @ rho[:, lo:hi].T
+    z = zscale * z
     if fault == "z16":
         z = z.astype(f16).astype(f64)
     lr = z @ l.T
     if fault == "pad_L":
         lr[:, 0] += z[:, -1] * case.kl
-    y = gs * (sk * (x @ c.T) + lr)
+    code = x @ c.T
+    if fault in ("drop_chunk", "stale_x"):
+        lo, hi = LC.second_chunk(case, case.bits, LC.DECODE_WAVES)
+        code[:, 0] -= x[:, lo:hi] @ c[0, lo:hi]
+        if fault == "stale_x":
+            code[:, 0] += x[:, :hi - lo] @ c[0, lo:hi]
+    y = gs * (sk * code + lr)
     if d["bias"] is not None:
         y = y + d["bias"].astype(f64)
     ax = np.abs(d["x"].astype(f64))

@@ -272,9 +272,34 @@ def test_module_survives_dtype_casts_of_the_model():
 @pytest.mark.parametrize("m,n", [(48, 198), (4000, 4096)])
 def test_decode_forward_in_a_captured_graph(m, n):
     """No allocation inside the entries and no synchronisation: a captured T = 1 forward replays
-    to the bits of the eager one."""
+    to the bits of the eager one.  (4000, 4096) is the one forward at a real layer's size (16 chunks
+    of 2-bit codes, two per wave), so there the eager result is also held against fp64: the fp32
+    forward of the same x under _bar, and the fp16 forward as that result rounded once.  At this
+    size _bar is wide (its 2^-11 term sums 4096 x 4096 magnitudes: a build whose waves multiply
+    their second chunk with the x of their first measured 0.59 of it), so the inner layer is also
+    checked on its own: its result on the fp16 x^ it receives, against fp64 under the bar of
+    linear_cases.py, output by output (that build: 102 bars)."""
     lin = _layer(m, n, 8, 2, bias=True)
     x = torch.randn(1, n, generator=torch.Generator().manual_seed(1)).half().to(DEV)
+    if n == 4096:
+        ref = torch.nn.functional.linear(x.double().cpu(), lin.dense_weight().double().cpu(),
+                                         lin.bias.double().cpu()).numpy()
+        y32 = lin(x.float())
+        frac = (np.abs(y32.double().cpu().numpy() - ref) / _bar(lin, x.double().cpu().numpy())).max()
+        print(f"m{m} n{n}: {frac:.4f} of the bar")
+        assert torch.isfinite(y32).all() and frac <= 1.0
+        assert torch.equal(lin(x), y32.half())
+        pr, pc = lin.padded_shape
+        xh = torch.empty((1, pc), dtype=torch.float16, device=DEV)
+        _K().hadamard_rows(x, xh, n_in=n, n_out=pc, P=pc)
+        c, L, R, sk, gs = _operands64(lin)
+        xh64 = xh.double().cpu().numpy()
+        ref_in = gs * (sk * (xh64 @ c.T) + (xh64 @ R.T) @ L.T)
+        A = gs * (sk * (np.abs(xh64) @ np.abs(c).T) + (np.abs(xh64) @ np.abs(R).T) @ np.abs(L).T)
+        frac_in = (np.abs(lin.inner(xh.float()).double().cpu().numpy() - ref_in)
+                   / ((pc + lin.inner.rank + 32) * u24 * A)).max()
+        print(f"m{m} n{n}: the inner layer {frac_in:.4f} of its bar")
+        assert frac_in <= 1.0
     xs = torch.zeros_like(x)
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())

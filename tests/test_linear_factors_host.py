@@ -31,6 +31,8 @@ def test_case_lists_cover_what_they_should():
         assert {(2, 4, 4), (2, 2, 2)} <= combos
     combos = {(c.bits, c.lb, c.rb) for c in FC.EXACT}
     assert {(4, 4, 4), (2, 2, 4), (2, 4, 16), (2, 16, 4)} <= combos
+    combos = {(c.bits, c.lb, c.rb) for c in FC.EXACT if (c.n, c.T) == (8454, 16)}      # the long-K decode shape
+    assert {(2, 4, 4), (2, 2, 2), (4, 4, 4), (2, 4, 16), (2, 16, 4)} <= combos
     assert {c.T for c in FC.EXACT} == {1, 5, 16, 17, 64, 130}
     assert any(c.bias for c in FC.EXACT) and any(c.bias for c in FC.RANDOM)
     assert len({c.id for c in FC.ALL}) == len(FC.ALL)

@@ -57,6 +57,65 @@ def test_planted_fault_exceeds_ten_bars_on_random_cases(case, fault):
     assert worst >= 10
 
 
+def _loop_pairs(cases):
+    return [pytest.param(c, f, id=f"{c.id}-{f}") for c in cases for f in LC.LOOP_FAULTS if LC.fault_applies(c, f)]
+
+
+@pytest.mark.parametrize("case,fault", _loop_pairs([c for c in LC.RANDOM if c.n > 512]))
+def test_loop_fault_exceeds_ten_bars_on_long_random_cases(case, fault):
+    """A wave's second chunk dropped, or multiplied with the x of its first, on the cases that have one."""
+    y, bar = LC.reference(case)
+    yf, _ = LC.reference(case, fault)
+    worst = (np.abs(yf - y) / bar).max()
+    print(f"{case.id} {fault}: {worst:.1f} bars")
+    assert worst >= 10
+
+
+def test_every_loop_fault_meets_exact_and_random_cases():
+    for cases in (LC.EXACT, LC.RANDOM):
+        assert {f for c in cases for f in LC.LOOP_FAULTS if LC.fault_applies(c, f)} == set(LC.LOOP_FAULTS)
+
+
+def _decode_split():
+    """(kDecodeWaves, kDecodeWavesZ, kDecodeSplitZ) as csrc/cq_linear.hip defines them."""
+    txt = open(os.path.join(ROOT, "ee274_convexcaldera_llm_quantization_amd", "csrc", "cq_linear.hip")).read()
+    return tuple(int(re.search(rf"constexpr int {name} = (\d+);", txt).group(1))
+                 for name in ("kDecodeWaves", "kDecodeWavesZ", "kDecodeSplitZ"))
+
+
+def test_decode_cases_reach_the_pipelined_loops():
+    """The decode kernels prefetch a wave's next chunk and rotate it in; that does something only
+    where a wave owns two chunks or more.  Under the split the kernel source has now, the decode
+    cases of both case files give some wave >= 2 chunks in each of the five loops, >= 3 (a chunk
+    that is neither first nor last) in the code loops and the fp16 / 4-bit z loop, and an uneven
+    split (another wave of the same launch takes fewer) in each of them."""
+    import linear_factor_cases as FC
+    split = _decode_split()
+    assert split == (LC.DECODE_WAVES, LC.DECODE_WAVES_Z, LC.DECODE_SPLIT_Z)
+    most, uneven, x_paths = {}, set(), set()
+    for case in LC.ALL + FC.ALL:
+        for loop, (hi, lo) in LC.decode_chunks(case, *split).items():
+            most[loop] = max(most.get(loop, 0), hi)
+            if hi >= 2 and lo < hi:
+                uneven.add(loop)
+            if hi >= 2 and loop.startswith("codes"):
+                x_paths.add((loop, case.n % 8 == 0))     # x rows 16-byte aligned (vector loads) or not
+    print(most, sorted(uneven))
+    assert x_paths == {(loop, al) for loop in ("codes2", "codes4") for al in (False, True)}
+    assert set(most) == {"codes2", "codes4", "z128", "z256", "L16"}
+    assert all(v >= 2 for v in most.values()), most
+    assert all(most[loop] >= 3 for loop in ("codes2", "codes4", "z128")), most
+    assert uneven == set(most)
+    # the restated split against the table it was written from
+    case = next(c for c in LC.EXACT if (c.n, c.bits, c.T) == (8454, 2, 16))
+    assert LC.decode_chunks(case, 8, 2, 16) == {"codes2": (5, 4), "z128": (3, 2), "L16": (1, 0)}
+    case = next(c for c in LC.EXACT if (c.n, c.bits, c.T) == (2600, 4, 1))
+    assert LC.decode_chunks(case, 8, 2, 16) == {"codes4": (3, 2), "z128": (1, 0), "L16": (1, 0)}
+    case = next(c for c in LC.EXACT if (c.r, c.bits, c.T) == (264, 2, 5))
+    assert LC.decode_chunks(case, 8, 2, 16) == {"codes2": (1, 0), "z128": (1, 0), "L16": (2, 1)}
+    assert LC.decode_chunks(next(c for c in LC.EXACT if c.T == 17)) == {}
+
+
 def test_single_fp16_rounding_of_z_fails_the_bar():
     """z rounded once to fp16 (what the contract forbids) is outside the bar at (33, 64, 8)."""
     for case in LC.RANDOM:
