@@ -103,6 +103,20 @@ class LinearPackedArgs(ctypes.Structure):
     ]
 
 
+class LinearBackwardArgs(ctypes.Structure):
+    _fields_ = [
+        ("dy", c_vp), ("lddy", c_i64),
+        ("tokens", c_i64), ("m", c_i64), ("n", c_i64), ("r", c_i64),
+        ("bits", c_int),
+        ("codes", c_vp), ("code_stride", c_i64),
+        ("qscale", c_float), ("gscale", c_float),
+        ("L", c_vp), ("ldl", c_i64),
+        ("R", c_vp), ("ldr", c_i64),
+        ("dx", c_vp), ("dx_dtype", c_int), ("lddx", c_i64),
+        ("u_out", c_vp), ("ldu", c_i64),
+    ]
+
+
 class HadamardArgs(ctypes.Structure):
     _fields_ = [
         ("x", c_vp), ("x_dtype", c_int), ("ldx", c_i64),
@@ -194,6 +208,8 @@ _SIGS = {
     "cq_linear_forward": (c_int, [ctypes.POINTER(LinearArgs), c_vp, c_size, c_vp]),
     "cq_linear_packed_workspace": (c_size, [ctypes.POINTER(LinearPackedArgs)]),
     "cq_linear_packed_forward": (c_int, [ctypes.POINTER(LinearPackedArgs), c_vp, c_size, c_vp]),
+    "cq_linear_backward_workspace": (c_size, [ctypes.POINTER(LinearBackwardArgs)]),
+    "cq_linear_backward_input": (c_int, [ctypes.POINTER(LinearBackwardArgs), c_vp, c_size, c_vp]),
     "cq_hadamard_rows": (c_int, [ctypes.POINTER(HadamardArgs), c_vp]),
     # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
     "cq_gemm_x3_skip": (c_int, [ctypes.POINTER(X3Args), c_vp]),
@@ -1346,6 +1362,59 @@ def linear_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, ws=No
         ws = workspace(lib.cq_linear_workspace(ctypes.byref(a)), x.device)
     _check(lib.cq_linear_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)), "cq_linear_forward")
     return y
+
+
+def linear_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, u_out=None) -> LinearBackwardArgs:
+    """cq_linear_backward_args for dy (T, m) fp16, inference-layout codes (m, row bytes) uint8,
+    L (m, r) / R (r, n) fp16 (None or r = 0: codes only), dx (T, n) fp32 / fp16 and u_out (T, r)
+    fp32 or None; dy, L, R, dx and u_out may be views with a row stride (unit column stride)."""
+    need = _linear_need
+    r = 0 if L is None else int(L.shape[1])
+    fp16 = (("L", L), ("R", R)) if r else ()
+    need(not r or R is not None, "L without R")
+    mats = (("dy", dy), ("codes", codes), ("dx", dx)) + fp16 + ((("u_out", u_out),) if r and u_out is not None else ())
+    for name, t in mats:
+        need(t.dim() == 2 and t.stride(1) == 1, f"{name} must be a matrix with unit column stride")
+    need(dy.dtype == torch.float16, f"dy must be fp16, got {dy.dtype}")
+    need(codes.dtype == torch.uint8 and codes.shape[0] == m, "codes must be uint8 with one row per output")
+    need(dy.shape[1] == m and tuple(dx.shape) == (dy.shape[0], n), f"dy {tuple(dy.shape)} / dx {tuple(dx.shape)} do not "
+         f"fit (tokens, {m}) / (tokens, {n})")
+    need(dx.dtype in (torch.float32, torch.float16), f"dx must be fp32 or fp16, got {dx.dtype}")
+    if fp16:
+        need(all(t.dtype == torch.float16 for _, t in fp16),
+             "L and R must be fp16, got " + ", ".join(str(t.dtype) for _, t in fp16))
+        need(tuple(L.shape) == (m, r) and tuple(R.shape) == (r, n),
+             f"L {tuple(L.shape)} / R {tuple(R.shape)} do not fit {(m, r)} / {(r, n)}")
+    a = LinearBackwardArgs()
+    a.dy, a.lddy = dy.data_ptr(), dy.stride(0)
+    a.tokens, a.m, a.n, a.r = dy.shape[0], m, n, r
+    a.bits = bits
+    a.codes, a.code_stride = codes.data_ptr(), codes.stride(0)
+    a.qscale, a.gscale = float(qscale), float(gscale)
+    for name, t in fp16:
+        setattr(a, name, t.data_ptr())
+        setattr(a, "ld" + name.lower(), t.stride(0))
+    a.dx, a.lddx = dx.data_ptr(), dx.stride(0)
+    a.dx_dtype = {torch.float32: CQ_F32, torch.float16: CQ_F16}[dx.dtype]
+    if r and u_out is not None:
+        need(u_out.dtype == torch.float32 and tuple(u_out.shape) == (dy.shape[0], r),
+             f"u_out must be fp32 (tokens, {r}), got {u_out.dtype} {tuple(u_out.shape)}")
+        a.u_out, a.ldu = u_out.data_ptr(), u_out.stride(0)
+    return a
+
+
+def linear_backward_input(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, u_out=None, ws=None):
+    """dx = dy (gs (Q + L R)) from the packed codes (cq_linear_backward_input); u_out (T, r) fp32
+    receives u = dy L (without gs).  ws: a uint8 workspace of at least
+    cq_linear_backward_workspace bytes (allocated here when None).  No host synchronisation."""
+    _require_hip(dy, codes, L, R, dx, u_out)
+    a = linear_backward_args(dy, codes, qscale, gscale, L, R, dx, m=m, n=n, bits=bits, u_out=u_out)
+    lib = load()
+    if ws is None:
+        ws = workspace(lib.cq_linear_backward_workspace(ctypes.byref(a)), dy.device)
+    _check(lib.cq_linear_backward_input(ctypes.byref(a), _p(ws), ws.numel(), _stream(dy.device)),
+           "cq_linear_backward_input")
+    return dx
 
 
 # ---------------------------------------------------------------------------- Hadamard transform

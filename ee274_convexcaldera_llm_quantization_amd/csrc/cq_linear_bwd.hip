@@ -1,0 +1,414 @@
+// Packed linear layer, input gradient (cq_linear_backward_input): dx = dy (gs (Q + L R)) straight
+// from the 2/4-bit codes and the fp16 factors, never forming the dense weight or its transpose.
+//
+//   dx[t, j] = gs * ((s / k) * sum_i dy[t, i] c[i, j] + sum_q u[t, q] R[q, j])
+//   u[t, q]  = sum_i dy[t, i] L[i, q]
+//
+// All three products contract over the ROWS of their weight operand (codes, L, R), which are
+// stored row-major along the other index, so the v_mfma_f32_16x16x32_f16 B fragment -- 8
+// consecutive rows at one column -- is a strided gather in memory.  The transposition is done on
+// chip: a workgroup takes a chunk of 32 weight rows x 128 columns with row loads (4 / 8 bytes of
+// codes or 32 bytes of fp16 per thread), expands codes with the forward's magic numbers, writes
+// the fp16 [row][column] tile to LDS and reads it back with ds_read_b64_tr_b16.  Rows past the
+// operand's end are written as zeros (pad, don't mask: the transposed read needs every lane).
+//
+// LDS image of a chunk: 8 blocks of 16 columns, each 32 rows of 32 bytes, block stride 1040
+// bytes.  Row i sits at position prow(i) = i with bits 2 and 3 swapped, so the two 4-row blocks
+// that a 32-lane half reads (rows 8g + 4h .. + 3 of lane groups g = 0, 1 resp. 2, 3) are 8
+// consecutive 32-byte rows: 64 distinct banks, conflict-free.  The 16 bytes past each block
+// spread a wave's 16-byte writes over all banks.  Two images form a ring: chunk c + 1 is
+// expanded and written, and chunk c + 2 loaded, under the MFMAs of chunk c; one barrier per chunk.
+//
+// Two launches of the same kernel: u = dy L (skipped for r = 0; writes the fp32 u_out and the
+// split fp16 halves), then codes, scaled by s / k in the accumulator, + the halves times R +
+// epilogue.  A wave owns TT tiles of 16 tokens x all 128 columns of its workgroup; tokens are the
+// A rows, read from memory with the forward's masked loader.  One dispatch branch: the summation
+// order of an output does not depend on the token count.
+#include <cmath>
+#include <cstdio>
+#include <type_traits>
+
+#include "cq_common.h"
+
+namespace cq {
+namespace {
+
+using h8 = __attribute__((ext_vector_type(8))) _Float16;
+using h4 = __attribute__((ext_vector_type(4))) _Float16;
+using h2 = __attribute__((ext_vector_type(2))) _Float16;
+using f4 = __attribute__((ext_vector_type(4))) float;
+using u4 = __attribute__((ext_vector_type(4))) uint32_t;
+using u2 = __attribute__((ext_vector_type(2))) uint32_t;
+
+constexpr int kWaves = 4;            // waves per workgroup, each with its own tokens
+constexpr int kBlocks = 8;           // 16-column blocks per workgroup: 128 columns
+constexpr int kCols = kBlocks * 16;
+constexpr int kRows = 32;            // weight rows per chunk: one MFMA k step
+constexpr int kBlockBytes = kRows * 32 + 16;
+constexpr int kImageBytes = kBlocks * kBlockBytes;
+constexpr int kTilesMain = 2;        // 16-token tiles per wave: codes + R
+constexpr int kTilesU = 1;           // ... the u product (r / 128 column tiles only: more workgroups)
+
+// elements k .. k + 7 of a row, zero at and beyond lim (lim = 0: nothing is read); restated from
+// cq_linear.hip, as pair / scale_off / expand below are
+__device__ __forceinline__ h8 ld8(const _Float16* row, int64_t k, int64_t lim, bool al) {
+    if (al && k + 8 <= lim) return *reinterpret_cast<const h8*>(row + k);
+    h8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (k < lim) {  // a ragged end or an unaligned row: element by element
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (k + j < lim) v[j] = row[k + j];
+    }
+    return v;
+}
+
+// fp16 magic numbers: 0x6400 | f is 1024 + f for a 10-bit field f, so a code field left where
+// it sits in the word (f = code << sh) becomes 1024 + (code << sh); one multiply by 2^-sh and
+// one subtraction of (1024 >> sh) + k, both exact in fp16, give code - k.
+__device__ __forceinline__ uint32_t pair(uint32_t uu, uint32_t mask) { return (uu & mask) | 0x64006400u; }
+__device__ __forceinline__ uint32_t scale_off(uint32_t p, h2 sc, h2 off) {
+    const h2 v = __builtin_bit_cast(h2, p) * sc + off;
+    return __builtin_bit_cast(uint32_t, v);
+}
+
+// 8 consecutive codes (offset-binary, MSB-first) as fp16: 2-bit from the low (hi = 0) or high 16
+// bits of `word`, 4-bit from all of it
+template <int BITS>
+__device__ __forceinline__ h8 expand(uint32_t word, int hi) {
+    u4 o;
+    if constexpr (BITS == 2) {
+        // both halves hold the fragment's two bytes
+        uint32_t uu = hi ? ((word >> 16) | (word & 0xffff0000u)) : ((word & 0xffffu) | (word << 16));
+        const h2 sa = {(_Float16)(1.0f / 64), (_Float16)(1.0f / 16)}, oa = {(_Float16)-17.0f, (_Float16)-65.0f};
+        const h2 sb = {(_Float16)0.25f, (_Float16)1.0f}, ob = {(_Float16)-257.0f, (_Float16)-1025.0f};
+        o[0] = scale_off(pair(uu, 0x003000C0u), sa, oa);
+        o[1] = scale_off(pair(uu, 0x0003000Cu), sb, ob);
+        uu >>= 8;
+        o[2] = scale_off(pair(uu, 0x003000C0u), sa, oa);
+        o[3] = scale_off(pair(uu, 0x0003000Cu), sb, ob);
+    } else {
+        const uint32_t u0 = (word & 0xffffu) | (word << 16), u1 = (word >> 16) | (word & 0xffff0000u);
+        const h2 sa = {(_Float16)(1.0f / 16), (_Float16)1.0f}, oa = {(_Float16)-71.0f, (_Float16)-1031.0f};
+        o[0] = scale_off(pair(u0, 0x000F00F0u), sa, oa);
+        o[1] = scale_off(pair(u0 >> 8, 0x000F00F0u), sa, oa);
+        o[2] = scale_off(pair(u1, 0x000F00F0u), sa, oa);
+        o[3] = scale_off(pair(u1 >> 8, 0x000F00F0u), sa, oa);
+    }
+    return __builtin_bit_cast(h8, o);
+}
+
+// a weight operand whose rows are contracted: W = 2 / 4 packed codes (stride in bytes), 16 = fp16
+// (stride in elements).  Rows >= rows and, for fp16, columns >= cols are not read and count as 0;
+// a code piece that starts inside cols lies inside the 16-byte padded row.
+struct Src {
+    const void* base; int64_t stride; int al;
+    int64_t rows, cols;
+};
+
+// what one thread holds of a chunk: 16 consecutive columns of one row, as loaded
+struct Raw { u4 a, b; };
+
+// FULL: the piece lies inside the operand and, for fp16, takes aligned 16-byte loads (the caller
+// knows): no branch
+template <int W, bool FULL>
+__device__ __forceinline__ Raw fetch(const Src& s, int64_t row, int64_t col) {
+    Raw w;
+    w.a = w.b = u4{0u, 0u, 0u, 0u};
+    if constexpr (FULL && W == 16) {
+        const u4* p = reinterpret_cast<const u4*>(reinterpret_cast<const _Float16*>(s.base) + row * s.stride + col);
+        w.a = p[0], w.b = p[1];
+    } else if constexpr (FULL) {
+        const uint8_t* p = reinterpret_cast<const uint8_t*>(s.base) + row * s.stride + col * W / 8;
+        if constexpr (W == 2) {
+            w.a[0] = *reinterpret_cast<const uint32_t*>(p);
+        } else {
+            const u2 v = *reinterpret_cast<const u2*>(p);
+            w.a[0] = v[0], w.a[1] = v[1];
+        }
+        w.b[0] = 1u;
+    } else if constexpr (W == 16) {
+        const _Float16* p = reinterpret_cast<const _Float16*>(s.base) + (row < s.rows ? row : 0) * s.stride;
+        const int64_t lim = row < s.rows ? s.cols : 0;
+        w.a = __builtin_bit_cast(u4, ld8(p, col, lim, s.al));
+        w.b = __builtin_bit_cast(u4, ld8(p, col + 8, lim, s.al));
+    } else if (row < s.rows && col < s.cols) {
+        const uint8_t* p = reinterpret_cast<const uint8_t*>(s.base) + row * s.stride + col * W / 8;
+        if constexpr (W == 2) {
+            w.a[0] = *reinterpret_cast<const uint32_t*>(p);
+        } else {
+            const u2 v = *reinterpret_cast<const u2*>(p);
+            w.a[0] = v[0], w.a[1] = v[1];
+        }
+        w.b[0] = 1u;  // loaded: all-zero bits are code -k, not 0
+    }
+    return w;
+}
+
+// position of row i in a block: bits 2 and 3 swapped
+__device__ __forceinline__ int prow(int i) { return (i & 0x13) | ((i & 4) << 1) | ((i & 8) >> 1); }
+
+template <int W>
+__device__ __forceinline__ void to_lds(const Raw& w, unsigned char* image, int row, int block) {
+    h8 lo, hi;
+    if constexpr (W == 16) {
+        lo = __builtin_bit_cast(h8, w.a), hi = __builtin_bit_cast(h8, w.b);
+    } else {
+        lo = expand<W>(w.a[0], 0), hi = W == 2 ? expand<W>(w.a[0], 1) : expand<W>(w.a[1], 0);
+        if (!w.b[0]) lo = hi = h8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    h8* dst = reinterpret_cast<h8*>(image + block * kBlockBytes + prow(row) * 32);
+    dst[0] = lo, dst[1] = hi;
+}
+
+// rows r .. r + 3 of the block at column (lane & 15), from the addresses of the 16-lane group
+__device__ __forceinline__ h4 tr_read(const unsigned char* p) {
+    typedef __fp16 raw4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+    return __builtin_bit_cast(h4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) raw4*)(p)));
+}
+
+// acc[tt][b] += A (tokens x rows of s) * s[:, col0 + 16 b ...] over all rows of s in chunks of 32.
+// load_a(c, tt, a, full): the NA A fragments (rows 32 c + 8 g ... + 7 of the lane's token) that are
+// multiplied, in order, with the same B fragment.  Every thread of the workgroup takes every
+// step (the barriers and the transposed reads need all lanes).
+//
+// The masked loaders branch per lane, and at the join of that control flow the compiler waits for
+// all loads in flight -- in front of the MFMAs of the chunk before the one they are for.  So the
+// chunks whose prefetches need no mask (afull: all the workgroup's tokens exist and their rows are
+// aligned; the tile's 128 columns inside the operand; whole chunks of rows) run in a loop of their
+// own, compiled without the masks (full = true_type); the masked loop takes the rest.
+template <int W, int TT, int NA, class LoadA>
+__device__ __forceinline__ void product(f4 (&acc)[TT][kBlocks], unsigned char (*lds)[kImageBytes], const Src& s,
+                                        int64_t col0, bool afull, LoadA load_a) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int li = lane & 15, g = lane >> 4;
+    const int frow = tid >> 3, fblock = tid & 7;  // the thread's piece of a chunk
+    const int64_t fcol = col0 + fblock * 16;
+    // transposed read: lane 4 q + p of group g supplies row 8 g + 4 h + q, columns 4 p ... + 3
+    const int roff = (((li >> 2) | ((g & 1) << 2) | ((g >> 1) << 4)) * 32) + (li & 3) * 8;
+    const int64_t nchunks = (s.rows + kRows - 1) / kRows;
+    const bool tile_full = afull && (W == 16 ? s.al && col0 + kCols <= s.cols : col0 + kCols - 16 < s.cols);
+    const int64_t nfull = tile_full ? s.rows / kRows : 0;  // whole chunks of a tile without masks
+
+    Raw w = fetch<W, false>(s, frow, fcol);
+    to_lds<W>(w, lds[0], frow, fblock);
+    if (nchunks > 1) w = fetch<W, false>(s, kRows + frow, fcol);
+    h8 a[TT][NA], an[TT][NA];
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) load_a(0, tt, a[tt], std::false_type{});
+    __syncthreads();
+    // chunks [cb, ce); full: chunks c + 1 and c + 2 exist and need no mask
+    auto run = [&](auto full, int64_t cb, int64_t ce) {
+        constexpr bool FULL = decltype(full)::value;
+        for (int64_t c = cb; c < ce; ++c) {
+            const unsigned char* cur = lds[c & 1];
+            if (FULL || c + 1 < nchunks) {
+                to_lds<W>(w, lds[(c + 1) & 1], frow, fblock);
+                if (FULL || c + 2 < nchunks) w = fetch<W, FULL>(s, (c + 2) * kRows + frow, fcol);
+#pragma unroll
+                for (int tt = 0; tt < TT; ++tt) load_a(c + 1, tt, an[tt], full);
+            }
+#pragma unroll
+            for (int b = 0; b < kBlocks; ++b) {
+                const h4 b0 = tr_read(cur + b * kBlockBytes + roff), b1 = tr_read(cur + b * kBlockBytes + roff + 256);
+                const h8 bf = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
+#pragma unroll
+                for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+                    for (int ia = 0; ia < NA; ++ia)
+                        acc[tt][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[tt][ia], bf, acc[tt][b], 0, 0, 0);
+            }
+            if (FULL || c + 1 < nchunks) {
+#pragma unroll
+                for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+                    for (int ia = 0; ia < NA; ++ia) a[tt][ia] = an[tt][ia];
+            }
+            __syncthreads();  // the image of chunk c is free for chunk c + 2, that of c + 1 complete
+        }
+    };
+    const int64_t cmid = nfull > 2 ? nfull - 2 : 0;
+    run(std::true_type{}, 0, cmid);
+    run(std::false_type{}, cmid, nchunks);
+}
+
+struct BwdP {
+    const _Float16* dy; int64_t lddy; int dy_al;
+    int64_t T, m, n, r, r32;
+    Src w;                                   // u product: L; else the codes
+    Src R;
+    _Float16* uh; _Float16* ul;              // [T][r32] halves of u: written by the u product, read by the other
+    float* u_out; int64_t ldu;
+    float sk, gs;
+    void* dx; int dx_f16; int64_t lddx;
+};
+
+// UK: the u product (W = 16: L's rows), else codes (W = 2 / 4) + R + epilogue
+template <int W, bool UK, int TT>
+__global__ __launch_bounds__(kWaves * 64) void linear_bwd_kernel(const BwdP p) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[2][kImageBytes];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, g = lane >> 4;
+    const int64_t tok0 = ((int64_t)blockIdx.x * kWaves + wave) * (TT * 16);
+    const int64_t col0 = (int64_t)blockIdx.y * kCols;
+
+    f4 acc[TT][kBlocks];
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+        for (int b = 0; b < kBlocks; ++b) acc[tt][b] = f4{0.f, 0.f, 0.f, 0.f};
+
+    // all of the workgroup's tokens exist (uniform)
+    const bool tokfull = ((int64_t)blockIdx.x + 1) * (kWaves * TT * 16) <= p.T;
+    // dy columns >= m and rows >= T are not read; full: a whole chunk of an existing, aligned row
+    auto load_dy = [&](int64_t c, int tt, h8 (&a)[1], auto full) {
+        const int64_t t = tok0 + tt * 16 + li;
+        if constexpr (decltype(full)::value)
+            a[0] = *reinterpret_cast<const h8*>(p.dy + t * p.lddy + c * kRows + g * 8);
+        else
+            a[0] = ld8(p.dy + (t < p.T ? t : 0) * p.lddy, c * kRows + g * 8, t < p.T ? p.m : 0, p.dy_al);
+    };
+    product<W, TT, 1>(acc, lds, p.w, col0, tokfull && p.dy_al, load_dy);
+
+    if constexpr (!UK) {
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+            for (int b = 0; b < kBlocks; ++b) acc[tt][b] = acc[tt][b] * p.sk;  // s / k once per output
+        if (p.r > 0) {  // uniform
+            // u as split halves, lo first as the forward's L product takes z; rows >= T read as zero
+            auto load_u = [&](int64_t c, int tt, h8 (&a)[2], auto full) {
+                const int64_t t = tok0 + tt * 16 + li;
+                const int64_t o = (t < p.T ? t : 0) * p.r32;
+                if constexpr (decltype(full)::value) {
+                    a[0] = *reinterpret_cast<const h8*>(p.ul + o + c * kRows + g * 8);
+                    a[1] = *reinterpret_cast<const h8*>(p.uh + o + c * kRows + g * 8);
+                } else {
+                    a[0] = ld8(p.ul + o, c * kRows + g * 8, t < p.T ? p.r32 : 0, true);
+                    a[1] = ld8(p.uh + o, c * kRows + g * 8, t < p.T ? p.r32 : 0, true);
+                }
+            };
+            product<16, TT, 2>(acc, lds, p.R, col0, tokfull, load_u);
+        }
+    }
+
+    // D tile: column = lane & 15, row (token) = 4 (lane >> 4) + register
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+#pragma unroll
+        for (int b = 0; b < kBlocks; ++b) {
+            const int64_t j = col0 + b * 16 + li;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t t = tok0 + tt * 16 + g * 4 + e;
+                if (t >= p.T) continue;
+                if constexpr (UK) {
+                    const float v = acc[tt][b][e];
+                    if (j < p.r && p.u_out) p.u_out[t * p.ldu + j] = v;
+                    if (j < p.r32) {  // columns r .. r32 are zero: L is not read there
+                        const _Float16 hi = (_Float16)v;
+                        p.uh[t * p.r32 + j] = hi;
+                        p.ul[t * p.r32 + j] = (_Float16)(v - (float)hi);
+                    }
+                } else if (j < p.n) {
+                    const float v = p.gs * acc[tt][b][e];
+                    if (p.dx_f16) reinterpret_cast<_Float16*>(p.dx)[t * p.lddx + j] = (_Float16)v;
+                    else reinterpret_cast<float*>(p.dx)[t * p.lddx + j] = v;
+                }
+            }
+        }
+    }
+}
+
+inline int64_t r32_of(int64_t r) { return ceil_div(r, 32) * 32; }
+inline bool al16(const void* ptr, int64_t ld_elems) {
+    return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld_elems % 8 == 0;
+}
+inline bool misaligned(const void* ptr, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(ptr) & mask) != 0; }
+
+// the halves of u: a function of tokens and r alone
+size_t workspace_bytes(int64_t tokens, int64_t r) {
+    if (r <= 0 || tokens <= 0) return 0;
+    return (size_t)(2 * tokens * r32_of(r)) * sizeof(uint16_t);
+}
+
+int validate(const cq_linear_backward_args* a) {
+    CQ_REQUIRE(a != nullptr, "cq_linear_backward_input: null args");
+    CQ_REQUIRE(a->bits == 2 || a->bits == 4, "cq_linear_backward_input: bits %d not in {2, 4}", a->bits);
+    CQ_REQUIRE(a->tokens >= 0 && a->m > 0 && a->n > 0 && a->r >= 0,
+               "cq_linear_backward_input: bad shape tokens=%lld m=%lld n=%lld r=%lld", (long long)a->tokens,
+               (long long)a->m, (long long)a->n, (long long)a->r);
+    CQ_REQUIRE(a->r <= CQ_LINEAR_MAX_RANK, "cq_linear_backward_input: rank %lld > %d", (long long)a->r,
+               CQ_LINEAR_MAX_RANK);
+    CQ_REQUIRE(a->tokens <= ((int64_t)1 << 31) && a->n <= (int64_t)65535 * kCols,
+               "cq_linear_backward_input: shape too large");
+    CQ_REQUIRE(a->dx_dtype == CQ_F32 || a->dx_dtype == CQ_F16, "cq_linear_backward_input: dx dtype %d not fp32 / fp16",
+               a->dx_dtype);
+    CQ_REQUIRE(a->dy && a->codes && a->dx, "cq_linear_backward_input: null dy / codes / dx");
+    CQ_REQUIRE(a->r == 0 || (a->L && a->R), "cq_linear_backward_input: null L / R with r = %lld", (long long)a->r);
+    CQ_REQUIRE(!misaligned(a->codes, 15) && a->code_stride % 16 == 0,
+               "cq_linear_backward_input: codes and their row stride must be 16-byte aligned (inference layout)");
+    CQ_REQUIRE(a->code_stride >= (a->n * a->bits + 7) / 8, "cq_linear_backward_input: code row stride %lld < %lld bytes",
+               (long long)a->code_stride, (long long)((a->n * a->bits + 7) / 8));
+    CQ_REQUIRE(!misaligned(a->dy, 1) && !misaligned(a->L, 1) && !misaligned(a->R, 1),
+               "cq_linear_backward_input: misaligned fp16 pointer");
+    CQ_REQUIRE(!misaligned(a->dx, a->dx_dtype == CQ_F16 ? 1 : 3) && !misaligned(a->u_out, 3),
+               "cq_linear_backward_input: misaligned dx / u_out pointer");
+    CQ_REQUIRE(a->lddy >= a->m && a->lddx >= a->n &&
+                   (a->r == 0 || (a->ldl >= a->r && a->ldr >= a->n && (a->u_out == nullptr || a->ldu >= a->r))),
+               "cq_linear_backward_input: leading dimension smaller than the row");
+    return CQ_OK;
+}
+
+template <int W, bool UK, int TT>
+void launch(const BwdP& p, int64_t cols, hipStream_t s) {
+    const dim3 grid((unsigned)ceil_div(p.T, kWaves * TT * 16), (unsigned)ceil_div(cols, kCols));
+    hipLaunchKernelGGL((linear_bwd_kernel<W, UK, TT>), grid, dim3(kWaves * 64), 0, s, p);
+}
+
+}  // namespace
+}  // namespace cq
+
+using namespace cq;
+
+extern "C" size_t cq_linear_backward_workspace(const cq_linear_backward_args* a) {
+    return a == nullptr ? 0 : workspace_bytes(a->tokens, a->r);
+}
+
+extern "C" int cq_linear_backward_input(const cq_linear_backward_args* a, void* ws, size_t ws_bytes, void* stream) {
+    const char* who = "cq_linear_backward_input";
+    if (int st = validate(a)) return st;
+    const size_t need = workspace_bytes(a->tokens, a->r);
+    if (need) {
+        CQ_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned",
+                   who);
+        CQ_REQUIRE(ws_bytes >= need, "%s: workspace %zu < %zu", who, ws_bytes, need);
+    }
+    if (a->tokens == 0) return CQ_OK;
+    hipStream_t s = as_stream(stream);
+    BwdP p{};
+    p.dy = reinterpret_cast<const _Float16*>(a->dy);
+    p.lddy = a->lddy;
+    p.dy_al = al16(a->dy, a->lddy);
+    p.T = a->tokens, p.m = a->m, p.n = a->n, p.r = a->r;
+    p.r32 = r32_of(a->r);
+    p.uh = reinterpret_cast<_Float16*>(ws);
+    p.ul = p.uh ? p.uh + a->tokens * p.r32 : nullptr;
+    if (a->r > 0) {  // u = dy L: fp32 to u_out, split halves to the workspace
+        BwdP u = p;
+        u.w = Src{a->L, a->ldl, al16(a->L, a->ldl), a->m, a->r};
+        u.u_out = a->u_out;
+        u.ldu = a->ldu;
+        launch<16, true, kTilesU>(u, p.r32, s);
+        if (int st = check_launch("cq_linear_backward_input (u)")) return st;
+    }
+    p.w = Src{a->codes, a->code_stride, 1, a->m, a->n};
+    p.R = Src{a->R, a->ldr, a->r > 0 && al16(a->R, a->ldr), a->r, a->n};
+    p.sk = a->qscale / (float)((1 << (a->bits - 1)) - 1);
+    p.gs = a->gscale;
+    p.dx = a->dx;
+    p.dx_f16 = a->dx_dtype == CQ_F16;
+    p.lddx = a->lddx;
+    if (a->bits == 2) launch<2, false, kTilesMain>(p, a->n, s);
+    else launch<4, false, kTilesMain>(p, a->n, s);
+    return check_launch(who);
+}

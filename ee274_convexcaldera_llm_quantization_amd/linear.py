@@ -65,6 +65,59 @@ def unpack_bytes(b: torch.Tensor, bits: int) -> torch.Tensor:
     return (u.to(torch.int16) - k).to(torch.int8)
 
 
+class _PackedLinearFunction(torch.autograd.Function):
+    """y = x (gs (Q + L R))^T (+ bias) with a graph: the forward is `CalderaLinear.forward`'s launch
+    (cq_linear_forward, the same bits), the backward gives dx from the packed codes
+    (cq_linear_backward_input) and, for trainable factors, dL = gs dy^T (x R^T) and dR = gs (dy L)^T x.
+    The codes and the bias are frozen.  L, R: the layer's fp16 buffers or its master parameters,
+    rounded to fp16 for the kernels; their gradient passes straight through that rounding."""
+
+    @staticmethod
+    def forward(ctx, x, L, R, lin):
+        m, n = lin.out_features, lin.in_features
+        x2 = x.reshape(-1, n).to(torch.float16)
+        if x2.stride(1) != 1:
+            x2 = x2.contiguous()
+        L16 = None if L is None else L.detach().to(torch.float16)
+        R16 = None if R is None else R.detach().to(torch.float16)
+        ydt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
+        y = torch.empty((x2.shape[0], m), dtype=ydt, device=x.device)
+        K.linear_forward(x2, lin.codes, lin.qscale, lin.gscale, L16, R16, lin.bias, y, m=m, n=n, bits=lin.bits)
+        ctx.lin, ctx.x_shape, ctx.x_dtype = lin, x.shape, x.dtype
+        ctx.factor_dtypes = (None if L is None else L.dtype, None if R is None else R.dtype)
+        ctx.save_for_backward(x2, L16, R16)
+        return y.to(x.dtype).reshape(*x.shape[:-1], m)
+
+    @staticmethod
+    def backward(ctx, gy):
+        lin = ctx.lin
+        x2, L16, R16 = ctx.saved_tensors
+        m, n, r, gs = lin.out_features, lin.in_features, lin.rank, lin.gscale
+        need_x, need_L, need_R = ctx.needs_input_grad[:3]
+        dy16 = gy.reshape(-1, m).to(torch.float16)  # once: every gradient uses these values
+        if dy16.stride(1) != 1 or (dy16.shape[0] > 1 and dy16.stride(0) < m):
+            dy16 = dy16.contiguous()
+        T = dy16.shape[0]
+        dx = dL = dR = u = None
+        if need_x:
+            dxdt = ctx.x_dtype if ctx.x_dtype in (torch.float16, torch.float32) else torch.float32
+            dx2 = torch.empty((T, n), dtype=dxdt, device=gy.device)
+            if r and need_R:
+                u = torch.empty((T, r), dtype=torch.float32, device=gy.device)
+            K.linear_backward_input(dy16, lin.codes, lin.qscale, gs, L16, R16, dx2, m=m, n=n, bits=lin.bits, u_out=u)
+            dx = dx2.to(ctx.x_dtype).reshape(ctx.x_shape)
+        # the factor gradients are T-reductions of T m r and T r n flops (r / n of the code term):
+        # torch matmul in fp32, z and u kept in fp32
+        if need_L:
+            z = x2.float() @ R16.float().t()
+            dL = ((dy16.float().t() @ z) * gs).to(ctx.factor_dtypes[0])
+        if need_R:
+            if u is None:
+                u = dy16.float() @ L16.float()
+            dR = ((u.t() @ x2.float()) * gs).to(ctx.factor_dtypes[1])
+        return dx, dL, dR, None
+
+
 class CalderaLinear(torch.nn.Module):
     """One compressed layer.  Buffers (so `state_dict()` carries them): `codes` (out_features,
     row_bytes) uint8 inference layout, `L` (out_features, rank) and `R` (rank, in_features) fp16,
@@ -76,7 +129,14 @@ class CalderaLinear(torch.nn.Module):
 
     forward(x): any leading dimensions, last = in_features, on a HIP device (there is no CPU
     path).  x is cast to fp16 and the result returned in x's dtype: bf16 activations beyond
-    fp16's range (|x| > 65504) would overflow, as would |x R^T|."""
+    fp16's range (|x| > 65504) would overflow, as would |x R^T|.
+
+    Training: with grad mode on and x requiring grad (or the factors trainable, see
+    `enable_factor_training`) a layer with fp16 factors returns a result with a graph; the
+    backward gives dx = dy (gs (Q + L R)) from the packed codes (cq_linear_backward_input) and the
+    factors' gradients.  The incoming gradient is cast to fp16 once, so |dy| <= 65504 (and
+    |dy L|), and gradients below fp16's subnormals (6e-8) vanish: use the usual loss scaling.
+    The codes and the bias stay frozen; a layer with coded factors gets no graph."""
 
     def __init__(self, codes, L, R, bias=None, *, qscale, gscale, bits, in_features, out_features, L_codes=None,
                  R_codes=None):
@@ -234,8 +294,8 @@ class CalderaLinear(torch.nn.Module):
         extra = {"n_padded": npad} if npad != n else {}
         dev = self.codes.device
         # a coded factor: its codes as they are (inference layout) and an fp32 array of zero rows
-        L = self.L.float() if self.L_codes is None else torch.zeros((0, self.rank), device=dev)
-        R = self.R.float() if self.R_codes is None else torch.zeros((0, n), device=dev)
+        L = self.L.detach().float() if self.L_codes is None else torch.zeros((0, self.rank), device=dev)
+        R = self.R.detach().float() if self.R_codes is None else torch.zeros((0, n), device=dev)
         return MatrixResult(name, m, n, self.rank, self.bits, codes, self.qscale, L, R, self.gscale, {}, extra,
                             L_codes=self.L_codes, R_codes=self.R_codes, L_scale=self.lscale, R_scale=self.rscale,
                             L_bits=self.L_bits, R_bits=self.R_bits)
@@ -268,8 +328,9 @@ class CalderaLinear(torch.nn.Module):
         def deq(codes, scale, bits, cols):
             c = unpack_bytes(codes, bits)[:, :cols].float()
             return c * (torch.tensor(scale, dtype=torch.float32) / torch.tensor(float(_k(bits)), dtype=torch.float32))
-        L = self.L.float() if self.L_codes is None else deq(self.L_codes, self.lscale, self.L_bits, self.rank)
-        R = self.R.float() if self.R_codes is None else deq(self.R_codes, self.rscale, self.R_bits, self.in_features)
+        L = self.L.detach().float() if self.L_codes is None else deq(self.L_codes, self.lscale, self.L_bits, self.rank)
+        R = (self.R.detach().float() if self.R_codes is None
+             else deq(self.R_codes, self.rscale, self.R_bits, self.in_features))
         return L, R
 
     def dense_weight(self) -> torch.Tensor:
@@ -281,12 +342,51 @@ class CalderaLinear(torch.nn.Module):
         L, R = self.factors()
         return self.gscale * (c * sk + L @ R)
 
+    # ------------------------------------------------------------------ fine-tuning
+    @property
+    def factors_trainable(self) -> bool:
+        """True between `enable_factor_training` and `freeze_factors`."""
+        return "L" in self._parameters
+
+    def enable_factor_training(self, master_dtype=torch.float32):
+        """Replace the fp16 buffers `L` and `R` by `nn.Parameter`s of the same names (state-dict keys
+        unchanged), widened exactly to master_dtype, and return them.  Every forward rounds them to
+        fp16 for the kernel; the gradient passes straight through that rounding, in master_dtype.
+        The codes and the bias stay frozen buffers."""
+        if self.L_codes is not None or self.R_codes is not None:
+            raise ValueError("CalderaLinear.enable_factor_training: a coded factor has no gradient "
+                             f"(L_bits={self.L_bits}, R_bits={self.R_bits})")
+        if self.rank == 0:
+            raise ValueError("CalderaLinear.enable_factor_training: rank 0, no factors to train")
+        if not self.factors_trainable:
+            for name in ("L", "R"):
+                master = getattr(self, name).detach().to(master_dtype)
+                delattr(self, name)
+                self.register_parameter(name, torch.nn.Parameter(master))
+        return [self.L, self.R]
+
+    def freeze_factors(self):
+        """Round the master factors to fp16 (nearest even) and keep them as buffers again: the
+        layer is the inference layer `to_result`, `packed_bytes` and `state_dict` know."""
+        if self.factors_trainable:
+            for name in ("L", "R"):
+                stored = getattr(self, name).detach().to(torch.float16).contiguous()
+                delattr(self, name)
+                self.register_buffer(name, stored)
+        return self
+
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if not x.is_cuda or not self.codes.is_cuda:
             raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
         if x.shape[-1] != self.in_features:
             raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {self.in_features}")
+        trainable = self.factors_trainable
+        if (self.L_codes is None and self.R_codes is None and torch.is_grad_enabled()
+                and (x.requires_grad or (trainable and (self.L.requires_grad or self.R.requires_grad)))):
+            return _PackedLinearFunction.apply(x, self.L if self.rank else None, self.R if self.rank else None, self)
+        # no graph: the inference launch (on the masters rounded to fp16 while the factors train)
+        L, R = (self.L.detach().to(torch.float16), self.R.detach().to(torch.float16)) if trainable else (self.L, self.R)
         x2 = x.reshape(-1, self.in_features).to(torch.float16)
         if x2.stride(1) != 1:
             x2 = x2.contiguous()
@@ -299,8 +399,8 @@ class CalderaLinear(torch.nn.Module):
                 L_codes=None if self.L_codes is None else (self.L_codes, self.lscale, self.L_bits),
                 R_codes=None if self.R_codes is None else (self.R_codes, self.rscale, self.R_bits))
         else:
-            K.linear_forward(x2, self.codes, self.qscale, self.gscale, self.L if self.rank else None,
-                             self.R if self.rank else None, self.bias, y, m=self.out_features, n=self.in_features,
+            K.linear_forward(x2, self.codes, self.qscale, self.gscale, L if self.rank else None,
+                             R if self.rank else None, self.bias, y, m=self.out_features, n=self.in_features,
                              bits=self.bits)
         return y.to(x.dtype).reshape(*x.shape[:-1], self.out_features)
 

@@ -352,3 +352,39 @@ def apply_packed_results(model: torch.nn.Module, results, device=None) -> list:
         _set_module(model, res.name, lin.to(w.device if device is None else device))
         done.append(res.name)
     return done
+
+
+def prepare_factor_finetuning(model: torch.nn.Module, master_dtype=torch.float32) -> list:
+    """Make the low-rank factors of every packed layer trainable over its frozen codes (CALDERA's
+    W ~ Q + L R with Q fixed, adapted LoRA-style with the factors already in place): calls
+    `CalderaLinear.enable_factor_training(master_dtype)` on every `linear.CalderaLinear` with fp16
+    factors and rank > 0 and returns the new parameters, for the optimiser.  ValueError, before
+    anything is changed, naming the packed layers that cannot back-propagate: a layer with coded
+    factors, a `linear.HadamardCalderaLinear`."""
+    from .linear import CalderaLinear, HadamardCalderaLinear
+    inner = {id(mod.inner) for mod in model.modules() if isinstance(mod, HadamardCalderaLinear)}
+    bad, layers = [], []
+    for name, mod in model.named_modules():
+        if isinstance(mod, HadamardCalderaLinear):
+            bad.append(f"{name or '<model>'} (Hadamard basis)")
+        elif isinstance(mod, CalderaLinear) and id(mod) not in inner:
+            if mod.L_codes is not None or mod.R_codes is not None:
+                bad.append(f"{name or '<model>'} (coded factors)")
+            elif mod.rank > 0:
+                layers.append(mod)
+    if bad:
+        raise ValueError("prepare_factor_finetuning: packed layers without a backward: " + ", ".join(bad))
+    params = []
+    for mod in layers:
+        params += mod.enable_factor_training(master_dtype)
+    return params
+
+
+def finish_factor_finetuning(model: torch.nn.Module) -> torch.nn.Module:
+    """Round every trained factor back to its fp16 buffer (`CalderaLinear.freeze_factors`): the
+    packed layers are inference layers again."""
+    from .linear import CalderaLinear
+    for mod in model.modules():
+        if isinstance(mod, CalderaLinear):
+            mod.freeze_factors()
+    return model

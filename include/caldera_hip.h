@@ -688,6 +688,54 @@ typedef struct cq_linear_packed_args {
 size_t cq_linear_packed_workspace(const cq_linear_packed_args* a);
 int cq_linear_packed_forward(const cq_linear_packed_args* a, void* ws, size_t ws_bytes, void* stream);
 
+/* Input gradient of the packed linear layer with fp16 factors: dx = dy (gs (Q + L R)), for
+ * fine-tuning L and R over the frozen codes.  For dy (tokens x m fp16, row stride lddy):
+ *
+ *   dx[t, j] = gs * ((s / k) * sum_i dy[t, i] c[i, j] + sum_q u[t, q] R[q, j])      j < n
+ *   u[t, q]  = sum_i dy[t, i] L[i, q]
+ *
+ * codes / code_stride are the inference layout cq_linear_forward takes, unchanged; L (m x r, row
+ * stride ldl) and R (r x n, row stride ldr) are fp16 in their stored orientation.  The
+ * contraction runs over the code rows, so the kernel transposes 32-row chunks on chip (LDS,
+ * ds_read_b64_tr_b16).
+ *
+ * Contract (cq_linear_forward's, mirrored):
+ *   - the code sum accumulates unscaled in fp32 and is exact; s / k is one fp32 division, applied
+ *     once per output, and the u R product continues on the scaled accumulator;
+ *   - u crosses between the two products as split fp16 halves (hi = f16(u), lo = f16(u - hi)), so
+ *     |u| and |dy| must stay below 65504; u_out (tokens x r fp32, row stride ldu, may be NULL)
+ *     receives the complete fp32 sum, without gs, so that a caller forms dR = gs u^T x without a
+ *     second dy L;
+ *   - dx (fp32 | fp16, row stride lddx) is the fp32 result, for fp16 rounded once;
+ *   - no float atomics and a fixed summation order: the same input gives the same bits; row t of
+ *     dx depends on row t of dy alone and not on `tokens` (one dispatch branch, no decode variant);
+ *   - nothing is read outside the operands' logical extent: dy is not read at columns >= m, the
+ *     codes and L not at rows >= m, R not at j >= n; the codes' pad columns contribute nothing
+ *     whatever they hold; dx is written only in [0, n) and u_out only in [0, r);
+ *   - stream-ordered, no allocation, no host synchronisation (graph-capturable);
+ *   - no image of the codes or of the dequantised weight in device memory: the workspace
+ *     (cq_linear_backward_workspace bytes, 16-byte aligned) holds the halves of u and is a function
+ *     of tokens and r alone;
+ *   - r = 0: codes only (L, R, u_out may be NULL); tokens = 0 returns 0 without a launch.
+ * CQ_EINVAL, before any HIP call: bits not 2 / 4, r > CQ_LINEAR_MAX_RANK, codes or code_stride
+ * not 16-byte aligned, an fp16 / fp32 pointer not aligned to its element, a row stride below its
+ * row (lddy < m, lddx < n, ldu < r, ldl < r, ldr < n), an unknown dx_dtype, a workspace that is
+ * too small. */
+typedef struct cq_linear_backward_args {
+    const uint16_t* dy; int64_t lddy;
+    int64_t tokens, m, n, r;
+    int bits;
+    const uint8_t* codes; int64_t code_stride;
+    float qscale, gscale;
+    const uint16_t* L; int64_t ldl;
+    const uint16_t* R; int64_t ldr;
+    void* dx; int dx_dtype; int64_t lddx;
+    float* u_out; int64_t ldu;
+} cq_linear_backward_args;
+
+size_t cq_linear_backward_workspace(const cq_linear_backward_args* a);
+int cq_linear_backward_input(const cq_linear_backward_args* a, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------
  * Row-wise normalised Sylvester-Hadamard transform (fast Walsh-Hadamard transform), the
  * transform around a packed layer that was decomposed in the Hadamard basis (main.py:108-133,
