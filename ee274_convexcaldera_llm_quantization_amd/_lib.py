@@ -117,6 +117,15 @@ class LinearBackwardArgs(ctypes.Structure):
     ]
 
 
+class LinearPackedBackwardArgs(ctypes.Structure):
+    _fields_ = LinearBackwardArgs._fields_ + [
+        ("l_bits", c_int), ("r_bits", c_int),
+        ("L_codes", c_vp), ("l_code_stride", c_i64),
+        ("R_codes", c_vp), ("r_code_stride", c_i64),
+        ("lscale", c_float), ("rscale", c_float),
+    ]
+
+
 class HadamardArgs(ctypes.Structure):
     _fields_ = [
         ("x", c_vp), ("x_dtype", c_int), ("ldx", c_i64),
@@ -210,6 +219,8 @@ _SIGS = {
     "cq_linear_packed_forward": (c_int, [ctypes.POINTER(LinearPackedArgs), c_vp, c_size, c_vp]),
     "cq_linear_backward_workspace": (c_size, [ctypes.POINTER(LinearBackwardArgs)]),
     "cq_linear_backward_input": (c_int, [ctypes.POINTER(LinearBackwardArgs), c_vp, c_size, c_vp]),
+    "cq_linear_packed_backward_workspace": (c_size, [ctypes.POINTER(LinearPackedBackwardArgs)]),
+    "cq_linear_packed_backward_input": (c_int, [ctypes.POINTER(LinearPackedBackwardArgs), c_vp, c_size, c_vp]),
     "cq_hadamard_rows": (c_int, [ctypes.POINTER(HadamardArgs), c_vp]),
     # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
     "cq_gemm_x3_skip": (c_int, [ctypes.POINTER(X3Args), c_vp]),
@@ -1368,10 +1379,18 @@ def linear_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, u_o
     """cq_linear_backward_args for dy (T, m) fp16, inference-layout codes (m, row bytes) uint8,
     L (m, r) / R (r, n) fp16 (None or r = 0: codes only), dx (T, n) fp32 / fp16 and u_out (T, r)
     fp32 or None; dy, L, R, dx and u_out may be views with a row stride (unit column stride)."""
-    need = _linear_need
     r = 0 if L is None else int(L.shape[1])
-    fp16 = (("L", L), ("R", R)) if r else ()
-    need(not r or R is not None, "L without R")
+    _linear_need(not r or R is not None, "L without R")
+    return _fill_linear_backward_args(LinearBackwardArgs(), dy, codes, qscale, gscale, L, R, dx, m=m, n=n, bits=bits,
+                                      r=r, u_out=u_out)
+
+
+def _fill_linear_backward_args(a, dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, r, u_out, L_coded=False,
+                               R_coded=False):
+    """The fields cq_linear_backward_args and cq_linear_packed_backward_args share; a coded
+    factor's fp16 operand is not looked at."""
+    need = _linear_need
+    fp16 = ((("L", L),) if r and not L_coded else ()) + ((("R", R),) if r and not R_coded else ())
     mats = (("dy", dy), ("codes", codes), ("dx", dx)) + fp16 + ((("u_out", u_out),) if r and u_out is not None else ())
     for name, t in mats:
         need(t.dim() == 2 and t.stride(1) == 1, f"{name} must be a matrix with unit column stride")
@@ -1383,9 +1402,8 @@ def linear_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, u_o
     if fp16:
         need(all(t.dtype == torch.float16 for _, t in fp16),
              "L and R must be fp16, got " + ", ".join(str(t.dtype) for _, t in fp16))
-        need(tuple(L.shape) == (m, r) and tuple(R.shape) == (r, n),
-             f"L {tuple(L.shape)} / R {tuple(R.shape)} do not fit {(m, r)} / {(r, n)}")
-    a = LinearBackwardArgs()
+        need(all(tuple(t.shape) == ((m, r) if name == "L" else (r, n)) for name, t in fp16),
+             " / ".join(f"{name} {tuple(t.shape)}" for name, t in fp16) + f" do not fit {(m, r)} / {(r, n)}")
     a.dy, a.lddy = dy.data_ptr(), dy.stride(0)
     a.tokens, a.m, a.n, a.r = dy.shape[0], m, n, r
     a.bits = bits
@@ -1414,6 +1432,56 @@ def linear_backward_input(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, u_
         ws = workspace(lib.cq_linear_backward_workspace(ctypes.byref(a)), dy.device)
     _check(lib.cq_linear_backward_input(ctypes.byref(a), _p(ws), ws.numel(), _stream(dy.device)),
            "cq_linear_backward_input")
+    return dx
+
+
+def linear_packed_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, r=None, L_codes=None,
+                                R_codes=None, u_out=None) -> LinearPackedBackwardArgs:
+    """cq_linear_packed_backward_args: `linear_backward_args` with either factor given by its codes
+    instead of fp16.  L_codes / R_codes: (uint8 inference-layout codes with one row per m resp. r,
+    scale, bits in {2, 4}); the fp16 L / R of a coded factor is None.  r: the rank, needed when both
+    factors are coded (else taken from the fp16 one)."""
+    need = _linear_need
+    if r is None:
+        need(L is not None or R is not None or (L_codes is None and R_codes is None),
+             "r is needed when both factors are coded")
+        r = L.shape[1] if L is not None else R.shape[0] if R is not None else 0
+    r = int(r)
+    if r:
+        need((L is None) != (L_codes is None), "give exactly one of L and L_codes")
+        need((R is None) != (R_codes is None), "give exactly one of R and R_codes")
+    a = _fill_linear_backward_args(LinearPackedBackwardArgs(), dy, codes, qscale, gscale, L, R, dx, m=m, n=n,
+                                   bits=bits, r=r, u_out=u_out, L_coded=L_codes is not None,
+                                   R_coded=R_codes is not None)
+    a.l_bits = a.r_bits = 16
+    for what, spec, rows in (("L", L_codes, m), ("R", R_codes, r)):
+        if spec is None or not r:
+            continue
+        t, scale, fbits = spec
+        need(t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.uint8 and t.shape[0] == rows,
+             f"{what}_codes must be a uint8 matrix with {rows} rows and unit column stride")
+        setattr(a, what.lower() + "_bits", int(fbits))
+        setattr(a, what + "_codes", t.data_ptr())
+        setattr(a, what.lower() + "_code_stride", t.stride(0))
+        setattr(a, what.lower() + "scale", float(scale))
+    return a
+
+
+def linear_packed_backward_input(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, r=None, L_codes=None,
+                                 R_codes=None, u_out=None, ws=None):
+    """dx = dy (gs (Q + L R)) with either factor applied from its packed 2/4-bit codes
+    (cq_linear_packed_backward_input); operands as `linear_packed_backward_args`.  u_out (T, r) fp32
+    receives u~ = uscale dy lam, which carries a coded R's scale.  ws as `linear_backward_input`.  No
+    host synchronisation."""
+    _require_hip(dy, codes, L, R, dx, u_out, None if L_codes is None else L_codes[0],
+                 None if R_codes is None else R_codes[0])
+    a = linear_packed_backward_args(dy, codes, qscale, gscale, L, R, dx, m=m, n=n, bits=bits, r=r, L_codes=L_codes,
+                                    R_codes=R_codes, u_out=u_out)
+    lib = load()
+    if ws is None:
+        ws = workspace(lib.cq_linear_packed_backward_workspace(ctypes.byref(a)), dy.device)
+    _check(lib.cq_linear_packed_backward_input(ctypes.byref(a), _p(ws), ws.numel(), _stream(dy.device)),
+           "cq_linear_packed_backward_input")
     return dx
 
 

@@ -24,6 +24,16 @@
 // epilogue.  A wave owns TT tiles of 16 tokens x all 128 columns of its workgroup; tokens are the
 // A rows, read from memory with the forward's masked loader.  One dispatch branch: the summation
 // order of an output does not depend on the token count.
+//
+// Factor codes (cq_linear_packed_backward_input): L and / or R as packed 2/4-bit codes with one
+// scale each, in the inference layout of the layer's own codes.  Both are contracted over their rows
+// like the Q codes, so they take the same chunk walk: W = 2 / 4 in the u product (rows m, columns
+// r), and a second width for the main kernel's R stage (rows r, columns n).  u~ = uscale * sum_i dy
+// lam with uscale the fp32 product of the coded factors' scale / k, applied once to the complete
+// fp32 sum in the u epilogue before the split; a 16-column piece of L codes that straddles r expands
+// whatever the tail holds, so that epilogue writes zero halves for q >= r, and R's rows >= r are
+// written to LDS as zeros like any row past an operand's end.  cq_linear_backward_input is this path
+// with fp16 factors and uscale = 1.
 #include <cmath>
 #include <cstdio>
 #include <type_traits>
@@ -239,11 +249,13 @@ struct BwdP {
     _Float16* uh; _Float16* ul;              // [T][r32] halves of u: written by the u product, read by the other
     float* u_out; int64_t ldu;
     float sk, gs;
+    float uscale;                            // on the complete u sum, before it is split (1 without factor codes)
     void* dx; int dx_f16; int64_t lddx;
 };
 
-// UK: the u product (W = 16: L's rows), else codes (W = 2 / 4) + R + epilogue
-template <int W, bool UK, int TT>
+// UK: the u product (W: L's rows, fp16 or codes), else codes (W = 2 / 4) + R (WR: fp16 or codes) +
+// epilogue
+template <int W, int WR, bool UK, int TT>
 __global__ __launch_bounds__(kWaves * 64) void linear_bwd_kernel(const BwdP p) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2][kImageBytes];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -287,7 +299,7 @@ __global__ __launch_bounds__(kWaves * 64) void linear_bwd_kernel(const BwdP p) {
                     a[1] = ld8(p.uh + o, c * kRows + g * 8, t < p.T ? p.r32 : 0, true);
                 }
             };
-            product<16, TT, 2>(acc, lds, p.R, col0, tokfull, load_u);
+            product<WR, TT, 2>(acc, lds, p.R, col0, tokfull, load_u);
         }
     }
 
@@ -302,9 +314,11 @@ __global__ __launch_bounds__(kWaves * 64) void linear_bwd_kernel(const BwdP p) {
                 const int64_t t = tok0 + tt * 16 + g * 4 + e;
                 if (t >= p.T) continue;
                 if constexpr (UK) {
-                    const float v = acc[tt][b][e];
+                    float v = acc[tt][b][e] * p.uscale;  // once, on the complete sum
+                    // a piece of L codes that straddles r has expanded the row's tail
+                    if constexpr (W != 16) v = j < p.r ? v : 0.f;
                     if (j < p.r && p.u_out) p.u_out[t * p.ldu + j] = v;
-                    if (j < p.r32) {  // columns r .. r32 are zero: L is not read there
+                    if (j < p.r32) {  // columns r .. r32 are zero: fp16 L is not read there
                         const _Float16 hi = (_Float16)v;
                         p.uh[t * p.r32 + j] = hi;
                         p.ul[t * p.r32 + j] = (_Float16)(v - (float)hi);
@@ -331,38 +345,136 @@ size_t workspace_bytes(int64_t tokens, int64_t r) {
     return (size_t)(2 * tokens * r32_of(r)) * sizeof(uint16_t);
 }
 
-int validate(const cq_linear_backward_args* a) {
-    CQ_REQUIRE(a != nullptr, "cq_linear_backward_input: null args");
-    CQ_REQUIRE(a->bits == 2 || a->bits == 4, "cq_linear_backward_input: bits %d not in {2, 4}", a->bits);
-    CQ_REQUIRE(a->tokens >= 0 && a->m > 0 && a->n > 0 && a->r >= 0,
-               "cq_linear_backward_input: bad shape tokens=%lld m=%lld n=%lld r=%lld", (long long)a->tokens,
-               (long long)a->m, (long long)a->n, (long long)a->r);
-    CQ_REQUIRE(a->r <= CQ_LINEAR_MAX_RANK, "cq_linear_backward_input: rank %lld > %d", (long long)a->r,
-               CQ_LINEAR_MAX_RANK);
-    CQ_REQUIRE(a->tokens <= ((int64_t)1 << 31) && a->n <= (int64_t)65535 * kCols,
-               "cq_linear_backward_input: shape too large");
-    CQ_REQUIRE(a->dx_dtype == CQ_F32 || a->dx_dtype == CQ_F16, "cq_linear_backward_input: dx dtype %d not fp32 / fp16",
-               a->dx_dtype);
-    CQ_REQUIRE(a->dy && a->codes && a->dx, "cq_linear_backward_input: null dy / codes / dx");
-    CQ_REQUIRE(a->r == 0 || (a->L && a->R), "cq_linear_backward_input: null L / R with r = %lld", (long long)a->r);
-    CQ_REQUIRE(!misaligned(a->codes, 15) && a->code_stride % 16 == 0,
-               "cq_linear_backward_input: codes and their row stride must be 16-byte aligned (inference layout)");
-    CQ_REQUIRE(a->code_stride >= (a->n * a->bits + 7) / 8, "cq_linear_backward_input: code row stride %lld < %lld bytes",
-               (long long)a->code_stride, (long long)((a->n * a->bits + 7) / 8));
-    CQ_REQUIRE(!misaligned(a->dy, 1) && !misaligned(a->L, 1) && !misaligned(a->R, 1),
-               "cq_linear_backward_input: misaligned fp16 pointer");
-    CQ_REQUIRE(!misaligned(a->dx, a->dx_dtype == CQ_F16 ? 1 : 3) && !misaligned(a->u_out, 3),
-               "cq_linear_backward_input: misaligned dx / u_out pointer");
-    CQ_REQUIRE(a->lddy >= a->m && a->lddx >= a->n &&
-                   (a->r == 0 || (a->ldl >= a->r && a->ldr >= a->n && (a->u_out == nullptr || a->ldu >= a->r))),
-               "cq_linear_backward_input: leading dimension smaller than the row");
+inline bool coded(int bits) { return bits == 2 || bits == 4; }
+inline float kmax(int bits) { return (float)((1 << (bits - 1)) - 1); }
+
+// one factor's codes: rows of `cols` codes in the inference layout, one finite scale >= 0
+// (cq_linear_packed_forward's cases)
+int validate_factor(const char* who, const char* name, int bits, const uint8_t* codes, int64_t stride, int64_t cols,
+                    float scale) {
+    CQ_REQUIRE(codes != nullptr, "%s: null %s codes with %s bits = %d", who, name, name, bits);
+    CQ_REQUIRE(!misaligned(codes, 15) && stride % 16 == 0,
+               "%s: %s codes and their row stride must be 16-byte aligned (inference layout)", who, name);
+    CQ_REQUIRE(stride >= (cols * bits + 7) / 8, "%s: %s code row stride %lld < %lld bytes", who, name, (long long)stride,
+               (long long)((cols * bits + 7) / 8));
+    CQ_REQUIRE(std::isfinite(scale) && scale >= 0.f, "%s: %s scale %g is not finite and >= 0", who, name, (double)scale);
     return CQ_OK;
 }
 
-template <int W, bool UK, int TT>
+int validate(const cq_linear_packed_backward_args* a, const char* who) {
+    CQ_REQUIRE(a != nullptr, "%s: null args", who);
+    CQ_REQUIRE(a->bits == 2 || a->bits == 4, "%s: bits %d not in {2, 4}", who, a->bits);
+    CQ_REQUIRE((coded(a->l_bits) || a->l_bits == 16) && (coded(a->r_bits) || a->r_bits == 16),
+               "%s: factor bits L %d / R %d not in {2, 4, 16}", who, a->l_bits, a->r_bits);
+    const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
+    CQ_REQUIRE(a->tokens >= 0 && a->m > 0 && a->n > 0 && a->r >= 0, "%s: bad shape tokens=%lld m=%lld n=%lld r=%lld", who,
+               (long long)a->tokens, (long long)a->m, (long long)a->n, (long long)a->r);
+    CQ_REQUIRE(a->r <= CQ_LINEAR_MAX_RANK, "%s: rank %lld > %d", who, (long long)a->r, CQ_LINEAR_MAX_RANK);
+    CQ_REQUIRE(a->tokens <= ((int64_t)1 << 31) && a->n <= (int64_t)65535 * kCols, "%s: shape too large", who);
+    CQ_REQUIRE(a->dx_dtype == CQ_F32 || a->dx_dtype == CQ_F16, "%s: dx dtype %d not fp32 / fp16", who, a->dx_dtype);
+    CQ_REQUIRE(a->dy && a->codes && a->dx, "%s: null dy / codes / dx", who);
+    CQ_REQUIRE(a->r == 0 || ((lcoded || a->L) && (rcoded || a->R)), "%s: null L / R with r = %lld", who, (long long)a->r);
+    if (lcoded)
+        if (int st = validate_factor(who, "L", a->l_bits, a->L_codes, a->l_code_stride, a->r, a->lscale)) return st;
+    if (rcoded)
+        if (int st = validate_factor(who, "R", a->r_bits, a->R_codes, a->r_code_stride, a->n, a->rscale)) return st;
+    CQ_REQUIRE(!misaligned(a->codes, 15) && a->code_stride % 16 == 0,
+               "%s: codes and their row stride must be 16-byte aligned (inference layout)", who);
+    CQ_REQUIRE(a->code_stride >= (a->n * a->bits + 7) / 8, "%s: code row stride %lld < %lld bytes", who,
+               (long long)a->code_stride, (long long)((a->n * a->bits + 7) / 8));
+    // a coded factor's fp16 pointer and leading dimension are not looked at
+    CQ_REQUIRE(!misaligned(a->dy, 1) && (lcoded || !misaligned(a->L, 1)) && (rcoded || !misaligned(a->R, 1)),
+               "%s: misaligned fp16 pointer", who);
+    CQ_REQUIRE(!misaligned(a->dx, a->dx_dtype == CQ_F16 ? 1 : 3) && !misaligned(a->u_out, 3),
+               "%s: misaligned dx / u_out pointer", who);
+    CQ_REQUIRE(a->lddy >= a->m && a->lddx >= a->n &&
+                   (a->r == 0 || ((lcoded || a->ldl >= a->r) && (rcoded || a->ldr >= a->n) &&
+                                  (a->u_out == nullptr || a->ldu >= a->r))),
+               "%s: leading dimension smaller than the row", who);
+    return CQ_OK;
+}
+
+// cq_linear_backward_args is the leading part of cq_linear_packed_backward_args: the same layer
+// with fp16 factors
+cq_linear_packed_backward_args with_fp16_factors(const cq_linear_backward_args* a) {
+    cq_linear_packed_backward_args b{};
+    b.dy = a->dy, b.lddy = a->lddy;
+    b.tokens = a->tokens, b.m = a->m, b.n = a->n, b.r = a->r;
+    b.bits = a->bits;
+    b.codes = a->codes, b.code_stride = a->code_stride;
+    b.qscale = a->qscale, b.gscale = a->gscale;
+    b.L = a->L, b.ldl = a->ldl;
+    b.R = a->R, b.ldr = a->ldr;
+    b.dx = a->dx, b.dx_dtype = a->dx_dtype, b.lddx = a->lddx;
+    b.u_out = a->u_out, b.ldu = a->ldu;
+    b.l_bits = b.r_bits = 16;
+    return b;
+}
+
+template <int W, int WR, bool UK, int TT>
 void launch(const BwdP& p, int64_t cols, hipStream_t s) {
     const dim3 grid((unsigned)ceil_div(p.T, kWaves * TT * 16), (unsigned)ceil_div(cols, kCols));
-    hipLaunchKernelGGL((linear_bwd_kernel<W, UK, TT>), grid, dim3(kWaves * 64), 0, s, p);
+    hipLaunchKernelGGL((linear_bwd_kernel<W, WR, UK, TT>), grid, dim3(kWaves * 64), 0, s, p);
+}
+
+template <int W>
+void launch_main(const BwdP& p, int r_bits, hipStream_t s) {
+    if (r_bits == 2) launch<W, 2, false, kTilesMain>(p, p.n, s);
+    else if (r_bits == 4) launch<W, 4, false, kTilesMain>(p, p.n, s);
+    else launch<W, 16, false, kTilesMain>(p, p.n, s);
+}
+
+int backward(const cq_linear_packed_backward_args* a, void* ws, size_t ws_bytes, void* stream, const char* who) {
+    if (int st = validate(a, who)) return st;
+    const size_t need = workspace_bytes(a->tokens, a->r);
+    if (need) {
+        CQ_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned",
+                   who);
+        CQ_REQUIRE(ws_bytes >= need, "%s: workspace %zu < %zu", who, ws_bytes, need);
+    }
+    if (a->tokens == 0) return CQ_OK;
+    const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
+    hipStream_t s = as_stream(stream);
+    BwdP p{};
+    p.dy = reinterpret_cast<const _Float16*>(a->dy);
+    p.lddy = a->lddy;
+    p.dy_al = al16(a->dy, a->lddy);
+    p.T = a->tokens, p.m = a->m, p.n = a->n, p.r = a->r;
+    p.r32 = r32_of(a->r);
+    p.uh = reinterpret_cast<_Float16*>(ws);
+    p.ul = p.uh ? p.uh + a->tokens * p.r32 : nullptr;
+    // the coded factors' scale / k (one fp32 division each), multiplied in fp32
+    p.uscale = 1.0f;
+    if (lcoded) p.uscale = a->lscale / kmax(a->l_bits);
+    if (rcoded) p.uscale = lcoded ? p.uscale * (a->rscale / kmax(a->r_bits)) : a->rscale / kmax(a->r_bits);
+    if (a->r > 0) {  // u~ = uscale dy lam: fp32 to u_out, split halves to the workspace
+        BwdP u = p;
+        u.u_out = a->u_out;
+        u.ldu = a->ldu;
+        if (lcoded) {
+            u.w = Src{a->L_codes, a->l_code_stride, 1, a->m, a->r};
+            if (a->l_bits == 2) launch<2, 16, true, kTilesU>(u, p.r32, s);
+            else launch<4, 16, true, kTilesU>(u, p.r32, s);
+        } else {
+            u.w = Src{a->L, a->ldl, al16(a->L, a->ldl), a->m, a->r};
+            launch<16, 16, true, kTilesU>(u, p.r32, s);
+        }
+        char what[64];
+        snprintf(what, sizeof what, "%s (u)", who);
+        if (int st = check_launch(what)) return st;
+    }
+    p.w = Src{a->codes, a->code_stride, 1, a->m, a->n};
+    if (rcoded) p.R = Src{a->R_codes, a->r_code_stride, 1, a->r, a->n};
+    else p.R = Src{a->R, a->ldr, a->r > 0 && al16(a->R, a->ldr), a->r, a->n};
+    p.sk = a->qscale / kmax(a->bits);
+    p.gs = a->gscale;
+    p.dx = a->dx;
+    p.dx_f16 = a->dx_dtype == CQ_F16;
+    p.lddx = a->lddx;
+    const int r_bits = rcoded ? a->r_bits : 16;
+    if (a->bits == 2) launch_main<2>(p, r_bits, s);
+    else launch_main<4>(p, r_bits, s);
+    return check_launch(who);
 }
 
 }  // namespace
@@ -374,41 +486,18 @@ extern "C" size_t cq_linear_backward_workspace(const cq_linear_backward_args* a)
     return a == nullptr ? 0 : workspace_bytes(a->tokens, a->r);
 }
 
-extern "C" int cq_linear_backward_input(const cq_linear_backward_args* a, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "cq_linear_backward_input";
-    if (int st = validate(a)) return st;
-    const size_t need = workspace_bytes(a->tokens, a->r);
-    if (need) {
-        CQ_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned",
-                   who);
-        CQ_REQUIRE(ws_bytes >= need, "%s: workspace %zu < %zu", who, ws_bytes, need);
-    }
-    if (a->tokens == 0) return CQ_OK;
-    hipStream_t s = as_stream(stream);
-    BwdP p{};
-    p.dy = reinterpret_cast<const _Float16*>(a->dy);
-    p.lddy = a->lddy;
-    p.dy_al = al16(a->dy, a->lddy);
-    p.T = a->tokens, p.m = a->m, p.n = a->n, p.r = a->r;
-    p.r32 = r32_of(a->r);
-    p.uh = reinterpret_cast<_Float16*>(ws);
-    p.ul = p.uh ? p.uh + a->tokens * p.r32 : nullptr;
-    if (a->r > 0) {  // u = dy L: fp32 to u_out, split halves to the workspace
-        BwdP u = p;
-        u.w = Src{a->L, a->ldl, al16(a->L, a->ldl), a->m, a->r};
-        u.u_out = a->u_out;
-        u.ldu = a->ldu;
-        launch<16, true, kTilesU>(u, p.r32, s);
-        if (int st = check_launch("cq_linear_backward_input (u)")) return st;
-    }
-    p.w = Src{a->codes, a->code_stride, 1, a->m, a->n};
-    p.R = Src{a->R, a->ldr, a->r > 0 && al16(a->R, a->ldr), a->r, a->n};
-    p.sk = a->qscale / (float)((1 << (a->bits - 1)) - 1);
-    p.gs = a->gscale;
-    p.dx = a->dx;
-    p.dx_f16 = a->dx_dtype == CQ_F16;
-    p.lddx = a->lddx;
-    if (a->bits == 2) launch<2, false, kTilesMain>(p, a->n, s);
-    else launch<4, false, kTilesMain>(p, a->n, s);
-    return check_launch(who);
+extern "C" size_t cq_linear_packed_backward_workspace(const cq_linear_packed_backward_args* a) {
+    return a == nullptr ? 0 : workspace_bytes(a->tokens, a->r);
 }
+
+extern "C" int cq_linear_backward_input(const cq_linear_backward_args* a, void* ws, size_t ws_bytes, void* stream) {
+    CQ_REQUIRE(a != nullptr, "cq_linear_backward_input: null args");
+    const cq_linear_packed_backward_args b = with_fp16_factors(a);
+    return backward(&b, ws, ws_bytes, stream, "cq_linear_backward_input");
+}
+
+extern "C" int cq_linear_packed_backward_input(const cq_linear_packed_backward_args* a, void* ws, size_t ws_bytes,
+                                               void* stream) {
+    return backward(a, ws, ws_bytes, stream, "cq_linear_packed_backward_input");
+}
+

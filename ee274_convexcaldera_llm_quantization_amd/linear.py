@@ -13,6 +13,11 @@ factor is kept as its packed codes in the same inference layout (`L_codes`: out_
 of rank codes, `R_codes`: rank rows of in_features codes) with `lscale` / `rscale`, has no
 fp16 buffer, and is applied by cq_linear_packed_forward: a quarter (4-bit) or an eighth
 (2-bit) of the fp16 factor's bytes, and no second rounding of (c / k) s to fp16.
+
+Every layer back-propagates dx from its packed form (csrc/cq_linear_bwd.hip:
+cq_linear_backward_input, with a coded factor cq_linear_packed_backward_input), and
+HadamardCalderaLinear around it with cq_hadamard_rows on dy and dx; fp16 factors can be
+trained over the frozen codes, coded ones stay frozen.
 """
 from __future__ import annotations
 
@@ -65,12 +70,78 @@ def unpack_bytes(b: torch.Tensor, bits: int) -> torch.Tensor:
     return (u.to(torch.int16) - k).to(torch.int8)
 
 
+def _launch_packed(lin, x2: torch.Tensor, y: torch.Tensor, L16=None, R16=None):
+    """The entry `CalderaLinear.forward` takes for this layer, on given fp16 x2 (T, in_features)
+    and y (T, out_features): cq_linear_packed_forward with a coded factor, else cq_linear_forward.
+    L16 / R16: the fp16 factors to use instead of the layer's buffers (masters rounded to fp16)."""
+    L = lin.L if L16 is None else L16
+    R = lin.R if R16 is None else R16
+    if lin.rank and (lin.L_codes is not None or lin.R_codes is not None):
+        K.linear_packed_forward(
+            x2, lin.codes, lin.qscale, lin.gscale, L, R, lin.bias, y, m=lin.out_features,
+            n=lin.in_features, bits=lin.bits, r=lin.rank,
+            L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
+            R_codes=None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits))
+    else:
+        K.linear_forward(x2, lin.codes, lin.qscale, lin.gscale, L if lin.rank else None,
+                         R if lin.rank else None, lin.bias, y, m=lin.out_features, n=lin.in_features,
+                         bits=lin.bits)
+    return y
+
+
+def _fp16_factors(L, R):
+    """The kernels' fp16 operands of the fp16 factors L, R (buffers or masters; None: coded or rank 0)."""
+    return (None if L is None else L.detach().to(torch.float16), None if R is None else R.detach().to(torch.float16))
+
+
+def _packed_backward(lin, dy16, x2, L16, R16, needs, dx_dtype, factor_dtypes):
+    """(dx2, dL, dR) of one packed layer for dy16 (T, m) fp16 and the saved fp16 x2 (T, n): dx2 (T, n)
+    in dx_dtype (fp32 | fp16) from the packed codes -- cq_linear_packed_backward_input with a coded
+    factor, else cq_linear_backward_input -- and, for trainable (hence fp16) factors,
+    dL = gs dy^T (x R^T) and dR = gs (dy L)^T x."""
+    m, n, r, gs = lin.out_features, lin.in_features, lin.rank, lin.gscale
+    need_x, need_L, need_R = needs
+    T = dy16.shape[0]
+    dx2 = dL = dR = u = None
+    if need_x:
+        dx2 = torch.empty((T, n), dtype=dx_dtype, device=dy16.device)
+        if r and (lin.L_codes is not None or lin.R_codes is not None):
+            K.linear_packed_backward_input(
+                dy16, lin.codes, lin.qscale, gs, L16, R16, dx2, m=m, n=n, bits=lin.bits, r=r,
+                L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
+                R_codes=None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits))
+        else:
+            if r and need_R:
+                u = torch.empty((T, r), dtype=torch.float32, device=dy16.device)
+            K.linear_backward_input(dy16, lin.codes, lin.qscale, gs, L16, R16, dx2, m=m, n=n, bits=lin.bits, u_out=u)
+    # the factor gradients are T-reductions of T m r and T r n flops (r / n of the code term):
+    # torch matmul in fp32, z and u kept in fp32
+    if need_L:
+        z = x2.float() @ R16.float().t()
+        dL = ((dy16.float().t() @ z) * gs).to(factor_dtypes[0])
+    if need_R:
+        if u is None:
+            u = dy16.float() @ L16.float()
+        dR = ((u.t() @ x2.float()) * gs).to(factor_dtypes[1])
+    return dx2, dL, dR
+
+
+def _rows(t, cols):
+    """t as a (T, cols) matrix with unit column stride whose rows do not overlap."""
+    t2 = t.reshape(-1, cols)
+    if t2.stride(1) != 1 or (t2.shape[0] > 1 and t2.stride(0) < cols):
+        t2 = t2.contiguous()
+    return t2
+
+
 class _PackedLinearFunction(torch.autograd.Function):
     """y = x (gs (Q + L R))^T (+ bias) with a graph: the forward is `CalderaLinear.forward`'s launch
-    (cq_linear_forward, the same bits), the backward gives dx from the packed codes
-    (cq_linear_backward_input) and, for trainable factors, dL = gs dy^T (x R^T) and dR = gs (dy L)^T x.
-    The codes and the bias are frozen.  L, R: the layer's fp16 buffers or its master parameters,
-    rounded to fp16 for the kernels; their gradient passes straight through that rounding."""
+    (cq_linear_forward, or cq_linear_packed_forward with a coded factor: the same bits), the
+    backward gives dx from the packed codes (cq_linear_backward_input resp.
+    cq_linear_packed_backward_input) and, for trainable factors, dL = gs dy^T (x R^T) and
+    dR = gs (dy L)^T x.  The codes, the bias and a coded factor are frozen.  L, R: the layer's fp16
+    buffers or its master parameters, rounded to fp16 for the kernels (their gradient passes
+    straight through that rounding); None for a coded factor."""
 
     @staticmethod
     def forward(ctx, x, L, R, lin):
@@ -78,11 +149,10 @@ class _PackedLinearFunction(torch.autograd.Function):
         x2 = x.reshape(-1, n).to(torch.float16)
         if x2.stride(1) != 1:
             x2 = x2.contiguous()
-        L16 = None if L is None else L.detach().to(torch.float16)
-        R16 = None if R is None else R.detach().to(torch.float16)
+        L16, R16 = _fp16_factors(L, R)
         ydt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
         y = torch.empty((x2.shape[0], m), dtype=ydt, device=x.device)
-        K.linear_forward(x2, lin.codes, lin.qscale, lin.gscale, L16, R16, lin.bias, y, m=m, n=n, bits=lin.bits)
+        _launch_packed(lin, x2, y, L16, R16)
         ctx.lin, ctx.x_shape, ctx.x_dtype = lin, x.shape, x.dtype
         ctx.factor_dtypes = (None if L is None else L.dtype, None if R is None else R.dtype)
         ctx.save_for_backward(x2, L16, R16)
@@ -92,29 +162,53 @@ class _PackedLinearFunction(torch.autograd.Function):
     def backward(ctx, gy):
         lin = ctx.lin
         x2, L16, R16 = ctx.saved_tensors
-        m, n, r, gs = lin.out_features, lin.in_features, lin.rank, lin.gscale
-        need_x, need_L, need_R = ctx.needs_input_grad[:3]
-        dy16 = gy.reshape(-1, m).to(torch.float16)  # once: every gradient uses these values
-        if dy16.stride(1) != 1 or (dy16.shape[0] > 1 and dy16.stride(0) < m):
-            dy16 = dy16.contiguous()
-        T = dy16.shape[0]
-        dx = dL = dR = u = None
-        if need_x:
-            dxdt = ctx.x_dtype if ctx.x_dtype in (torch.float16, torch.float32) else torch.float32
-            dx2 = torch.empty((T, n), dtype=dxdt, device=gy.device)
-            if r and need_R:
-                u = torch.empty((T, r), dtype=torch.float32, device=gy.device)
-            K.linear_backward_input(dy16, lin.codes, lin.qscale, gs, L16, R16, dx2, m=m, n=n, bits=lin.bits, u_out=u)
+        dy16 = _rows(gy, lin.out_features).to(torch.float16)  # once: every gradient uses these values
+        dxdt = ctx.x_dtype if ctx.x_dtype in (torch.float16, torch.float32) else torch.float32
+        dx2, dL, dR = _packed_backward(lin, dy16, x2, L16, R16, ctx.needs_input_grad[:3], dxdt, ctx.factor_dtypes)
+        dx = None if dx2 is None else dx2.to(ctx.x_dtype).reshape(ctx.x_shape)
+        return dx, dL, dR, None
+
+
+class _HadamardLinearFunction(torch.autograd.Function):
+    """`HadamardCalderaLinear.forward` with a graph: the inference path's three launch groups (the same
+    bits), and a backward that mirrors them.  H is symmetric, so dy goes through cq_hadamard_rows
+    with n_in and n_out swapped (out_features -> pr, written as the fp16 dy^ the inner backward
+    takes), the inner layer's backward gives the fp32 dx^ from the packed codes, and dx^ goes through
+    cq_hadamard_rows (pc -> in_features) into x's dtype; no torch arithmetic on that path.  The
+    inner factors' gradients come from the saved x^ and dy^: in the Hadamard basis, the one the
+    factors live in.  The bias is frozen.
+
+    One function and not three chained ones: autograd casts the gradient of an input to that
+    input's dtype, so across an edge the fp32 dx^ of the fp16 x^ would be rounded to fp16 (and the
+    fp16 dy^ of the fp32 inner output widened and narrowed again)."""
+
+    @staticmethod
+    def forward(ctx, x, L, R, had):
+        L16, R16 = _fp16_factors(L, R)
+        x2, xh, y = had._forward_launches(x, L16, R16)
+        ctx.had, ctx.x_shape, ctx.x_dtype, ctx.x2_dtype = had, x.shape, x.dtype, x2.dtype
+        ctx.factor_dtypes = (None if L is None else L.dtype, None if R is None else R.dtype)
+        ctx.save_for_backward(xh, L16, R16)
+        return y.to(x.dtype).reshape(*x.shape[:-1], had.out_features)
+
+    @staticmethod
+    def backward(ctx, gy):
+        had = ctx.had
+        xh, L16, R16 = ctx.saved_tensors
+        pr, pc = had.padded_shape
+        gy2 = _rows(gy, had.out_features)
+        if gy2.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            gy2 = gy2.float()
+        T = gy2.shape[0]
+        dyh = torch.empty((T, pr), dtype=torch.float16, device=gy.device)
+        K.hadamard_rows(gy2, dyh, n_in=had.out_features, n_out=pr, P=pr)
+        dxh, dL, dR = _packed_backward(had.inner, dyh, xh, L16, R16, ctx.needs_input_grad[:3], torch.float32,
+                                       ctx.factor_dtypes)
+        dx = None
+        if dxh is not None:
+            dx2 = torch.empty((T, had.in_features), dtype=ctx.x2_dtype, device=gy.device)
+            K.hadamard_rows(dxh, dx2, n_in=pc, n_out=had.in_features, P=pc)
             dx = dx2.to(ctx.x_dtype).reshape(ctx.x_shape)
-        # the factor gradients are T-reductions of T m r and T r n flops (r / n of the code term):
-        # torch matmul in fp32, z and u kept in fp32
-        if need_L:
-            z = x2.float() @ R16.float().t()
-            dL = ((dy16.float().t() @ z) * gs).to(ctx.factor_dtypes[0])
-        if need_R:
-            if u is None:
-                u = dy16.float() @ L16.float()
-            dR = ((u.t() @ x2.float()) * gs).to(ctx.factor_dtypes[1])
         return dx, dL, dR, None
 
 
@@ -132,11 +226,13 @@ class CalderaLinear(torch.nn.Module):
     fp16's range (|x| > 65504) would overflow, as would |x R^T|.
 
     Training: with grad mode on and x requiring grad (or the factors trainable, see
-    `enable_factor_training`) a layer with fp16 factors returns a result with a graph; the
-    backward gives dx = dy (gs (Q + L R)) from the packed codes (cq_linear_backward_input) and the
-    factors' gradients.  The incoming gradient is cast to fp16 once, so |dy| <= 65504 (and
-    |dy L|), and gradients below fp16's subnormals (6e-8) vanish: use the usual loss scaling.
-    The codes and the bias stay frozen; a layer with coded factors gets no graph."""
+    `enable_factor_training`) the layer returns a result with a graph, whatever the factor
+    format; the backward gives dx = dy (gs (Q + L R)) from the packed codes
+    (cq_linear_backward_input; cq_linear_packed_backward_input with a coded factor) and the
+    gradients of trainable factors.  The incoming gradient is cast to fp16 once, so |dy| <= 65504
+    (and |dy L|), and gradients below fp16's subnormals (6e-8) vanish: use the usual loss scaling.
+    The codes and the bias stay frozen, and so does a coded factor (a buffer without a gradient)
+    and the fp16 factor beside it: only a layer with two fp16 factors trains them."""
 
     def __init__(self, codes, L, R, bias=None, *, qscale, gscale, bits, in_features, out_features, L_codes=None,
                  R_codes=None):
@@ -382,43 +478,19 @@ class CalderaLinear(torch.nn.Module):
         if x.shape[-1] != self.in_features:
             raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {self.in_features}")
         trainable = self.factors_trainable
-        if (self.L_codes is None and self.R_codes is None and torch.is_grad_enabled()
-                and (x.requires_grad or (trainable and (self.L.requires_grad or self.R.requires_grad)))):
+        if torch.is_grad_enabled() and (x.requires_grad
+                                        or (trainable and (self.L.requires_grad or self.R.requires_grad))):
+            # a coded factor has no fp16 operand (None); rank 0 has none at all
             return _PackedLinearFunction.apply(x, self.L if self.rank else None, self.R if self.rank else None, self)
         # no graph: the inference launch (on the masters rounded to fp16 while the factors train)
-        L, R = (self.L.detach().to(torch.float16), self.R.detach().to(torch.float16)) if trainable else (self.L, self.R)
+        L16, R16 = _fp16_factors(self.L, self.R) if trainable else (None, None)
         x2 = x.reshape(-1, self.in_features).to(torch.float16)
         if x2.stride(1) != 1:
             x2 = x2.contiguous()
         ydt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
         y = torch.empty((x2.shape[0], self.out_features), dtype=ydt, device=x.device)
-        if self.rank and (self.L_codes is not None or self.R_codes is not None):
-            K.linear_packed_forward(
-                x2, self.codes, self.qscale, self.gscale, self.L, self.R, self.bias, y, m=self.out_features,
-                n=self.in_features, bits=self.bits, r=self.rank,
-                L_codes=None if self.L_codes is None else (self.L_codes, self.lscale, self.L_bits),
-                R_codes=None if self.R_codes is None else (self.R_codes, self.rscale, self.R_bits))
-        else:
-            K.linear_forward(x2, self.codes, self.qscale, self.gscale, L if self.rank else None,
-                             R if self.rank else None, self.bias, y, m=self.out_features, n=self.in_features,
-                             bits=self.bits)
+        _launch_packed(self, x2, y, L16, R16)
         return y.to(x.dtype).reshape(*x.shape[:-1], self.out_features)
-
-
-def _launch_packed(lin: CalderaLinear, x2: torch.Tensor, y: torch.Tensor):
-    """The entry `CalderaLinear.forward` takes for this layer, on given fp16 x2 (T, in_features)
-    and y (T, out_features): cq_linear_packed_forward with a coded factor, else cq_linear_forward."""
-    if lin.rank and (lin.L_codes is not None or lin.R_codes is not None):
-        K.linear_packed_forward(
-            x2, lin.codes, lin.qscale, lin.gscale, lin.L, lin.R, lin.bias, y, m=lin.out_features,
-            n=lin.in_features, bits=lin.bits, r=lin.rank,
-            L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
-            R_codes=None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits))
-    else:
-        K.linear_forward(x2, lin.codes, lin.qscale, lin.gscale, lin.L if lin.rank else None,
-                         lin.R if lin.rank else None, lin.bias, y, m=lin.out_features, n=lin.in_features,
-                         bits=lin.bits)
-    return y
 
 
 def _next_pow2(n: int) -> int:
@@ -437,7 +509,12 @@ class HadamardCalderaLinear(torch.nn.Module):
     its own dtype, written as the fp16 the inner layer takes), the inner layer's packed forward
     into an fp32 buffer, cq_hadamard_rows on that (+ bias) written in x's dtype.  `inner` may
     use any Q / factor format CalderaLinear supports and has no bias; `bias` (out_features,)
-    fp32 or None is added by the output transform.  Extra state: in_features, out_features."""
+    fp32 or None is added by the output transform.  Extra state: in_features, out_features.
+
+    Training: with grad mode on and x requiring grad (or the inner factors trainable) forward
+    runs the same launches with a graph (`_HadamardLinearFunction`); the backward transforms dy
+    and dx with cq_hadamard_rows around the inner layer's input gradient, and the inner fp16
+    factors train in the Hadamard basis (`enable_factor_training`).  The bias stays frozen."""
 
     def __init__(self, inner: CalderaLinear, in_features: int, out_features: int, bias=None):
         super().__init__()
@@ -524,12 +601,26 @@ class HadamardCalderaLinear(torch.nn.Module):
         H1, H2 = normalized_hadamard(pr, Wt.device), normalized_hadamard(pc, Wt.device)
         return (H1 @ Wt @ H2)[:self.out_features, :self.in_features].contiguous()
 
+    # ------------------------------------------------------------------ fine-tuning
+    @property
+    def factors_trainable(self) -> bool:
+        """`inner.factors_trainable`."""
+        return self.inner.factors_trainable
+
+    def enable_factor_training(self, master_dtype=torch.float32):
+        """`inner.enable_factor_training`: the parameters are `inner.L` and `inner.R`, factors of the
+        weight in the Hadamard basis, and their gradients are taken in that basis."""
+        return self.inner.enable_factor_training(master_dtype)
+
+    def freeze_factors(self):
+        self.inner.freeze_factors()
+        return self
+
     # ------------------------------------------------------------------ forward
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if not x.is_cuda or not self.inner.codes.is_cuda:
-            raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
-        if x.shape[-1] != self.in_features:
-            raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {self.in_features}")
+    def _forward_launches(self, x, L16=None, R16=None):
+        """The three launch groups on x: (x2, x^, y) with x2 the (T, in_features) view they read, x^
+        the fp16 (T, pc) transform the inner layer takes and y (T, out_features) in x2's dtype.
+        L16 / R16: the inner layer's fp16 factors when they are not its buffers."""
         pr, pc = self.padded_shape
         x2 = x.reshape(-1, self.in_features)
         if x2.dtype not in (torch.float16, torch.bfloat16, torch.float32):
@@ -540,7 +631,23 @@ class HadamardCalderaLinear(torch.nn.Module):
         xh = torch.empty((T, pc), dtype=torch.float16, device=x.device)
         K.hadamard_rows(x2, xh, n_in=self.in_features, n_out=pc, P=pc)
         y32 = torch.empty((T, pr), dtype=torch.float32, device=x.device)
-        _launch_packed(self.inner, xh, y32)
+        _launch_packed(self.inner, xh, y32, L16, R16)
         y = torch.empty((T, self.out_features), dtype=x2.dtype, device=x.device)
         K.hadamard_rows(y32, y, n_in=pr, n_out=self.out_features, P=pr, bias=self.bias)
+        return x2, xh, y
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not x.is_cuda or not self.inner.codes.is_cuda:
+            raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
+        if x.shape[-1] != self.in_features:
+            raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {self.in_features}")
+        inner = self.inner
+        trainable = inner.factors_trainable
+        if torch.is_grad_enabled() and (x.requires_grad
+                                        or (trainable and (inner.L.requires_grad or inner.R.requires_grad))):
+            return _HadamardLinearFunction.apply(x, inner.L if inner.rank else None, inner.R if inner.rank else None,
+                                                 self)
+        # no graph: the inference launches (on the masters rounded to fp16 while the factors train)
+        L16, R16 = _fp16_factors(inner.L, inner.R) if trainable else (None, None)
+        y = self._forward_launches(x, L16, R16)[2]
         return y.to(x.dtype).reshape(*x.shape[:-1], self.out_features)

@@ -354,24 +354,41 @@ def apply_packed_results(model: torch.nn.Module, results, device=None) -> list:
     return done
 
 
-def prepare_factor_finetuning(model: torch.nn.Module, master_dtype=torch.float32) -> list:
+def prepare_factor_finetuning(model: torch.nn.Module, master_dtype=torch.float32, *, hadamard=False,
+                              coded_factors="refuse") -> list:
     """Make the low-rank factors of every packed layer trainable over its frozen codes (CALDERA's
     W ~ Q + L R with Q fixed, adapted LoRA-style with the factors already in place): calls
     `CalderaLinear.enable_factor_training(master_dtype)` on every `linear.CalderaLinear` with fp16
-    factors and rank > 0 and returns the new parameters, for the optimiser.  ValueError, before
-    anything is changed, naming the packed layers that cannot back-propagate: a layer with coded
-    factors, a `linear.HadamardCalderaLinear`."""
+    factors and rank > 0 and returns the new parameters, for the optimiser.
+
+    hadamard=True: a `linear.HadamardCalderaLinear` whose inner layer has fp16 factors is made
+    trainable too; its parameters are `<name>.inner.L` and `<name>.inner.R`, factors of the weight
+    in the Hadamard basis.  coded_factors="freeze": a layer with coded factors (a Hadamard layer
+    whose inner has them counts as one) is left as it is: it back-propagates dx and trains nothing.
+
+    ValueError, before anything is changed, naming the packed layers the keywords do not admit
+    (the defaults: every layer with coded factors, every `linear.HadamardCalderaLinear`), or for
+    a coded_factors that is neither "refuse" nor "freeze"."""
     from .linear import CalderaLinear, HadamardCalderaLinear
+    if coded_factors not in ("refuse", "freeze"):
+        raise ValueError(f"prepare_factor_finetuning: coded_factors {coded_factors!r} not in ('refuse', 'freeze')")
     inner = {id(mod.inner) for mod in model.modules() if isinstance(mod, HadamardCalderaLinear)}
     bad, layers = [], []
     for name, mod in model.named_modules():
         if isinstance(mod, HadamardCalderaLinear):
-            bad.append(f"{name or '<model>'} (Hadamard basis)")
+            lin, what = mod.inner, "Hadamard basis"
+            if not hadamard:
+                bad.append(f"{name or '<model>'} (Hadamard basis)")
+                continue
         elif isinstance(mod, CalderaLinear) and id(mod) not in inner:
-            if mod.L_codes is not None or mod.R_codes is not None:
-                bad.append(f"{name or '<model>'} (coded factors)")
-            elif mod.rank > 0:
-                layers.append(mod)
+            lin, what = mod, ""
+        else:
+            continue
+        if lin.L_codes is not None or lin.R_codes is not None:
+            if coded_factors == "refuse":
+                bad.append(f"{name or '<model>'} ({what + ', ' if what else ''}coded factors)")
+        elif lin.rank > 0:
+            layers.append(lin)
     if bad:
         raise ValueError("prepare_factor_finetuning: packed layers without a backward: " + ", ".join(bad))
     params = []
@@ -381,8 +398,9 @@ def prepare_factor_finetuning(model: torch.nn.Module, master_dtype=torch.float32
 
 
 def finish_factor_finetuning(model: torch.nn.Module) -> torch.nn.Module:
-    """Round every trained factor back to its fp16 buffer (`CalderaLinear.freeze_factors`): the
-    packed layers are inference layers again."""
+    """Round every trained factor back to its fp16 buffer (`CalderaLinear.freeze_factors`; the
+    inner layer of a `linear.HadamardCalderaLinear` is one of `model.modules()`): the packed
+    layers are inference layers again."""
     from .linear import CalderaLinear
     for mod in model.modules():
         if isinstance(mod, CalderaLinear):

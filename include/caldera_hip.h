@@ -736,6 +736,54 @@ typedef struct cq_linear_backward_args {
 size_t cq_linear_backward_workspace(const cq_linear_backward_args* a);
 int cq_linear_backward_input(const cq_linear_backward_args* a, void* ws, size_t ws_bytes, void* stream);
 
+/* The same input gradient with low-bit factors: dx from the packed codes of Q, L and R, for a
+ * layer that cq_linear_packed_forward runs.  The maths mirrors the forward's zscale:
+ *
+ *   u~[t, q] = uscale * sum_i dy[t, i] lam[i, q]
+ *   dx[t, j] = gs * ((s / k) * sum_i dy[t, i] c[i, j] + sum_q u~[t, q] rho[q, j])      j < n
+ *
+ * lam is the L codes (l_bits 2 | 4) or the fp16 L (l_bits 16), rho the R codes or the fp16 R
+ * (r_bits).  uscale is the fp32 product of the coded factors' scale / k -- lscale / k_L and
+ * rscale / k_R, each one fp32 division -- and 1.0f when neither factor is coded.  l_bits, r_bits,
+ * L_codes, l_code_stride, R_codes, r_code_stride, lscale and rscale mean exactly what they mean in
+ * cq_linear_packed_args: inference layout, L codes as m rows of r codes, R codes as r rows of n
+ * codes.
+ *
+ * Contract, beside everything cq_linear_backward_input's holds to:
+ *   - both code sums accumulate unscaled in fp32; uscale is applied once, to the complete fp32 u
+ *     sum, before it is split into fp16 halves, so the halves must stay in fp16 range while the
+ *     unscaled sum need not; the rho product continues on the accumulator already scaled by s / k;
+ *   - u_out receives u~, the value whose halves the second product consumes: with R coded it
+ *     carries R's scale (u~ = (rscale / k_R) dy L for an fp16 L), so it is dy L only when R is fp16;
+ *   - pad columns of the L codes (q >= r) and of the R codes (j >= n) contribute nothing whatever
+ *     the tails hold, and nothing is read past the last row of either;
+ *   - a coded factor's fp16 pointer and leading dimension are ignored (may be NULL / 0), an fp16
+ *     factor's code pointer, stride and scale likewise; with l_bits = r_bits = 16 the result has
+ *     the bits of cq_linear_backward_input, which is this entry with those values;
+ *   - the workspace (cq_linear_packed_backward_workspace bytes) is the same function of tokens and
+ *     r alone.
+ * CQ_EINVAL, before any HIP call, beside cq_linear_backward_input's: l_bits / r_bits not in
+ * {2, 4, 16}; for a coded factor a NULL or not 16-byte aligned code pointer, a stride that is not a
+ * multiple of 16 or is below ceil(row codes * bits / 8), a scale that is not finite or is negative. */
+typedef struct cq_linear_packed_backward_args {
+    const uint16_t* dy; int64_t lddy;
+    int64_t tokens, m, n, r;
+    int bits;
+    const uint8_t* codes; int64_t code_stride;
+    float qscale, gscale;
+    const uint16_t* L; int64_t ldl;
+    const uint16_t* R; int64_t ldr;
+    void* dx; int dx_dtype; int64_t lddx;
+    float* u_out; int64_t ldu;
+    int l_bits, r_bits;
+    const uint8_t* L_codes; int64_t l_code_stride;
+    const uint8_t* R_codes; int64_t r_code_stride;
+    float lscale, rscale;
+} cq_linear_packed_backward_args;
+
+size_t cq_linear_packed_backward_workspace(const cq_linear_packed_backward_args* a);
+int cq_linear_packed_backward_input(const cq_linear_packed_backward_args* a, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------
  * Row-wise normalised Sylvester-Hadamard transform (fast Walsh-Hadamard transform), the
  * transform around a packed layer that was decomposed in the Hadamard basis (main.py:108-133,
