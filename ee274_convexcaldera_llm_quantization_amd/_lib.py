@@ -126,6 +126,15 @@ class LinearPackedBackwardArgs(ctypes.Structure):
     ]
 
 
+class LinearCodebookArgs(ctypes.Structure):
+    """cq_linear_codebook_args: the packed struct, then q_format."""
+    _fields_ = [("p", LinearPackedArgs), ("q_format", c_int)]
+
+
+class LinearCodebookBackwardArgs(ctypes.Structure):
+    _fields_ = [("p", LinearPackedBackwardArgs), ("q_format", c_int)]
+
+
 class HadamardArgs(ctypes.Structure):
     _fields_ = [
         ("x", c_vp), ("x_dtype", c_int), ("ldx", c_i64),
@@ -221,6 +230,10 @@ _SIGS = {
     "cq_linear_backward_input": (c_int, [ctypes.POINTER(LinearBackwardArgs), c_vp, c_size, c_vp]),
     "cq_linear_packed_backward_workspace": (c_size, [ctypes.POINTER(LinearPackedBackwardArgs)]),
     "cq_linear_packed_backward_input": (c_int, [ctypes.POINTER(LinearPackedBackwardArgs), c_vp, c_size, c_vp]),
+    "cq_linear_codebook_workspace": (c_size, [ctypes.POINTER(LinearCodebookArgs)]),
+    "cq_linear_codebook_forward": (c_int, [ctypes.POINTER(LinearCodebookArgs), c_vp, c_size, c_vp]),
+    "cq_linear_codebook_backward_workspace": (c_size, [ctypes.POINTER(LinearCodebookBackwardArgs)]),
+    "cq_linear_codebook_backward_input": (c_int, [ctypes.POINTER(LinearCodebookBackwardArgs), c_vp, c_size, c_vp]),
     "cq_hadamard_rows": (c_int, [ctypes.POINTER(HadamardArgs), c_vp]),
     # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
     "cq_gemm_x3_skip": (c_int, [ctypes.POINTER(X3Args), c_vp]),
@@ -1315,11 +1328,11 @@ def _fill_linear_args(a, x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits,
 
 
 def linear_packed_args(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, r=None, L_codes=None,
-                       R_codes=None) -> LinearPackedArgs:
+                       R_codes=None, into=None) -> LinearPackedArgs:
     """cq_linear_packed_args: `linear_args` with either factor given by its codes instead of fp16.
     L_codes / R_codes: (uint8 inference-layout codes with one row per m resp. r, scale, bits in
     {2, 4}); the fp16 L / R of a coded factor is None.  r: the rank, needed when both factors are
-    coded (else taken from the fp16 one)."""
+    coded (else taken from the fp16 one).  into: the struct to fill (a codebook struct's `p`)."""
     need = _linear_need
     if r is None:
         need(L is not None or R is not None or (L_codes is None and R_codes is None),
@@ -1329,8 +1342,8 @@ def linear_packed_args(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, r
     if r:
         need((L is None) != (L_codes is None), "give exactly one of L and L_codes")
         need((R is None) != (R_codes is None), "give exactly one of R and R_codes")
-    a = _fill_linear_args(LinearPackedArgs(), x, codes, qscale, gscale, L, R, bias, y, m=m, n=n, bits=bits, r=r,
-                          L_coded=L_codes is not None, R_coded=R_codes is not None)
+    a = _fill_linear_args(LinearPackedArgs() if into is None else into, x, codes, qscale, gscale, L, R, bias, y, m=m,
+                          n=n, bits=bits, r=r, L_coded=L_codes is not None, R_coded=R_codes is not None)
     a.l_bits = a.r_bits = 16
     for what, spec, rows in (("L", L_codes, m), ("R", R_codes, r)):
         if spec is None or not r:
@@ -1359,6 +1372,50 @@ def linear_packed_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits
         ws = workspace(lib.cq_linear_packed_workspace(ctypes.byref(a)), x.device)
     _check(lib.cq_linear_packed_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)),
            "cq_linear_packed_forward")
+    return y
+
+
+QFMT_UNIFORM = 0  # include/caldera_hip.h CQ_QFMT_UNIFORM: offset-binary uniform codes
+QFMT_NF = 1       # CQ_QFMT_NF: NF4 / NF2 level indices
+# the integer levels I = D level of the codebook contract (include/caldera_hip.h), by bits
+NF_LEVELS = {4: (-1334, -1000, -784, -617, -476, -347, -226, -112, 0, 112, 226, 347, 476, 617, 784, 1000),
+             2: (-8165, -3333, 3333, 8165)}
+NF_DENOM = {4: 1000.0, 2: 10000.0}
+
+
+def _check_q_format(q_format, qscale):
+    _linear_need(q_format in (QFMT_UNIFORM, QFMT_NF), f"unknown q_format {q_format!r}")
+    if q_format == QFMT_NF:
+        s = float(qscale)
+        _linear_need(s >= 0.0 and s != float("inf"), f"NF scale {s} is not finite and >= 0")
+
+
+def linear_codebook_args(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, q_format, r=None, L_codes=None,
+                         R_codes=None) -> LinearCodebookArgs:
+    """cq_linear_codebook_args: `linear_packed_args` (the same host-side checks) plus q_format
+    (QFMT_UNIFORM: offset-binary codes; QFMT_NF: `codes` holds NF4 / NF2 level indices, qscale the
+    matrix scale)."""
+    _check_q_format(q_format, qscale)
+    a = LinearCodebookArgs()
+    linear_packed_args(x, codes, qscale, gscale, L, R, bias, y, m=m, n=n, bits=bits, r=r, L_codes=L_codes,
+                       R_codes=R_codes, into=a.p)
+    a.q_format = int(q_format)
+    return a
+
+
+def linear_codebook_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, q_format, r=None, L_codes=None,
+                            R_codes=None, ws=None):
+    """y = x (gs (Q + L R))^T (+ bias) with Q in q_format (cq_linear_codebook_forward); operands as
+    `linear_codebook_args`, ws as `linear_forward`.  No host synchronisation."""
+    _require_hip(x, codes, L, R, bias, y, None if L_codes is None else L_codes[0],
+                 None if R_codes is None else R_codes[0])
+    a = linear_codebook_args(x, codes, qscale, gscale, L, R, bias, y, m=m, n=n, bits=bits, q_format=q_format, r=r,
+                             L_codes=L_codes, R_codes=R_codes)
+    lib = load()
+    if ws is None:
+        ws = workspace(lib.cq_linear_codebook_workspace(ctypes.byref(a)), x.device)
+    _check(lib.cq_linear_codebook_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)),
+           "cq_linear_codebook_forward")
     return y
 
 
@@ -1436,11 +1493,11 @@ def linear_backward_input(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, u_
 
 
 def linear_packed_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, r=None, L_codes=None,
-                                R_codes=None, u_out=None) -> LinearPackedBackwardArgs:
+                                R_codes=None, u_out=None, into=None) -> LinearPackedBackwardArgs:
     """cq_linear_packed_backward_args: `linear_backward_args` with either factor given by its codes
     instead of fp16.  L_codes / R_codes: (uint8 inference-layout codes with one row per m resp. r,
     scale, bits in {2, 4}); the fp16 L / R of a coded factor is None.  r: the rank, needed when both
-    factors are coded (else taken from the fp16 one)."""
+    factors are coded (else taken from the fp16 one).  into: the struct to fill (a codebook struct's `p`)."""
     need = _linear_need
     if r is None:
         need(L is not None or R is not None or (L_codes is None and R_codes is None),
@@ -1450,8 +1507,8 @@ def linear_packed_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bi
     if r:
         need((L is None) != (L_codes is None), "give exactly one of L and L_codes")
         need((R is None) != (R_codes is None), "give exactly one of R and R_codes")
-    a = _fill_linear_backward_args(LinearPackedBackwardArgs(), dy, codes, qscale, gscale, L, R, dx, m=m, n=n,
-                                   bits=bits, r=r, u_out=u_out, L_coded=L_codes is not None,
+    a = _fill_linear_backward_args(LinearPackedBackwardArgs() if into is None else into, dy, codes, qscale, gscale, L,
+                                   R, dx, m=m, n=n, bits=bits, r=r, u_out=u_out, L_coded=L_codes is not None,
                                    R_coded=R_codes is not None)
     a.l_bits = a.r_bits = 16
     for what, spec, rows in (("L", L_codes, m), ("R", R_codes, r)):
@@ -1482,6 +1539,35 @@ def linear_packed_backward_input(dy, codes, qscale, gscale, L, R, dx, *, m, n, b
         ws = workspace(lib.cq_linear_packed_backward_workspace(ctypes.byref(a)), dy.device)
     _check(lib.cq_linear_packed_backward_input(ctypes.byref(a), _p(ws), ws.numel(), _stream(dy.device)),
            "cq_linear_packed_backward_input")
+    return dx
+
+
+def linear_codebook_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, q_format, r=None, L_codes=None,
+                                  R_codes=None, u_out=None) -> LinearCodebookBackwardArgs:
+    """cq_linear_codebook_backward_args: `linear_packed_backward_args` (the same host-side checks)
+    plus q_format, as `linear_codebook_args`."""
+    _check_q_format(q_format, qscale)
+    a = LinearCodebookBackwardArgs()
+    linear_packed_backward_args(dy, codes, qscale, gscale, L, R, dx, m=m, n=n, bits=bits, r=r, L_codes=L_codes,
+                                R_codes=R_codes, u_out=u_out, into=a.p)
+    a.q_format = int(q_format)
+    return a
+
+
+def linear_codebook_backward_input(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, q_format, r=None,
+                                   L_codes=None, R_codes=None, u_out=None, ws=None):
+    """dx = dy (gs (Q + L R)) with Q in q_format (cq_linear_codebook_backward_input); operands as
+    `linear_codebook_backward_args`, u_out and ws as `linear_packed_backward_input`.  No host
+    synchronisation."""
+    _require_hip(dy, codes, L, R, dx, u_out, None if L_codes is None else L_codes[0],
+                 None if R_codes is None else R_codes[0])
+    a = linear_codebook_backward_args(dy, codes, qscale, gscale, L, R, dx, m=m, n=n, bits=bits, q_format=q_format,
+                                      r=r, L_codes=L_codes, R_codes=R_codes, u_out=u_out)
+    lib = load()
+    if ws is None:
+        ws = workspace(lib.cq_linear_codebook_backward_workspace(ctypes.byref(a)), dy.device)
+    _check(lib.cq_linear_codebook_backward_input(ctypes.byref(a), _p(ws), ws.numel(), _stream(dy.device)),
+           "cq_linear_codebook_backward_input")
     return dx
 
 

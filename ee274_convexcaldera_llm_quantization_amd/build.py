@@ -33,7 +33,7 @@ STAMP = OUT + ".srchash"  # content hash of the sources the .so was built from
 
 
 def _deps():
-    return ([os.path.join(CSRC, s) for s in SOURCES + ["cq_common.h", "cq_x3.h", "cq_x3_tile.h"]]
+    return ([os.path.join(CSRC, s) for s in SOURCES + ["cq_common.h", "cq_x3.h", "cq_x3_tile.h", "cq_nf.h"]]
             + [os.path.join(HERE, "..", "include", "caldera_hip.h")])
 
 

@@ -32,10 +32,20 @@
 // (the z kernel's epilogue in prefill; after the ordered add of the partial z in decode); the L
 // product then multiplies the halves with the integer L codes, a lane's 16-byte load holding its B
 // fragments of 4 / 8 k steps.  cq_linear_forward is this path with fp16 factors and zscale = 1.
+//
+// Codebook Q (cq_linear_codebook_forward, CQ_QFMT_NF): the layer's own codes are NF4 / NF2 level
+// indices in the same layout, the Q term (s / D) * sum_j x[t, j] I[idx[i, j]] with I = D level an
+// integer (D = 1000 resp. 10000).  A level table is not affine, so the magic numbers do not apply:
+// the workgroup fills a byte-indexed LDS table once (256 entries holding the 2 resp. 4 fp16 integers
+// of a byte's indices; cq_nf.h) and `expand_nf` looks a fragment's bytes up (4 ds_read_b32 resp. 2
+// ds_read_b64).  NF2's 8165 and 3333 are not fp16 values: the table holds the hi plane (8164 / 3332,
+// signed), the lo plane (+-1, the level's sign) is made from it in registers, and both planes are
+// multiplied into the same accumulator, hi first.  Everything around the expansion is unchanged.
 #include <cmath>
 #include <cstdio>
 
 #include "cq_common.h"
+#include "cq_nf.h"
 
 namespace cq {
 namespace {
@@ -122,10 +132,26 @@ __device__ __forceinline__ h8 expand(const u4 q, int jj) {
 // weight rows are R's, fp16 or codes; writes partial z or split halves), else the layer's codes
 // (+ the L product and the output epilogue) with LB: L as fp16 rows (16) or packed 2 / 4-bit
 // codes.  A wave owns RG groups of 16 weight rows x TT tiles of 16 tokens.  NW: waves per
-// workgroup; KSPLIT: they split K over one 16-row group (else each owns its own rows).
-template <int WT, int LB, bool ZP, int TT, int RG, int NW, bool KSPLIT>
-__global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
+// workgroup; KSPLIT: they split K over one 16-row group (else each owns its own rows).  QF: the
+// layer's codes are offset-binary uniform codes (CQ_QFMT_UNIFORM) or NF level indices (CQ_QFMT_NF).
+// The NF4 prefill tile keeps 16 table reads in flight and would take 172 VGPRs + 92 AGPRs, one
+// workgroup per CU where the uniform tile has two; asked for two waves per SIMD it fits 220 VGPRs
+// without scratch.  Every other instantiation states a minimum of one wave per SIMD, which
+// is what its launch bounds imply already: their code is the same with and without the attribute.
+template <int WT, int QF, int LB, bool ZP, int TT, int RG, int NW, bool KSPLIT>
+__global__ __launch_bounds__(NW * 64)
+__attribute__((amdgpu_waves_per_eu(QF == CQ_QFMT_NF && WT == 4 && TT > 1 ? 2 : 1))) void linear_kernel(const LinP p) {
     constexpr bool CODES = WT != 16;
+    constexpr bool NF = QF == CQ_QFMT_NF;
+    static_assert(!NF || (CODES && !ZP), "only the layer's own codes are level indices");
+    constexpr bool PLANES2 = NF && WT == 2;
+    const uint32_t* nftab = nullptr;
+    if constexpr (NF) {  // before any wave leaves
+        __shared__ uint32_t tab[WT == 4 ? 256 : 512];
+        fill_nf_table<WT>(tab, threadIdx.x, NW * 64);
+        __syncthreads();
+        nftab = tab;
+    }
     static_assert(!ZP || LB == 16, "the z product has no L");
     static_assert(ZP || CODES, "the layer's own weight is always codes");
     constexpr int WV = CODES ? 1 : 4;                   // 16-byte weight loads per lane and chunk
@@ -182,7 +208,8 @@ __global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
         return w;
     };
     auto frag = [&](const WR& w, int jj) -> h8 {
-        if constexpr (CODES) return expand<WT>(w.v[0], jj);
+        if constexpr (NF) return expand_nf<WT>(nftab, WT == 4 ? w.v[0][jj & 3] : w.v[0][jj >> 1], jj & 1);
+        else if constexpr (CODES) return expand<WT>(w.v[0], jj);
         else return __builtin_bit_cast(h8, w.v[jj]);
     };
     auto load_x = [&](int64_t c, int jj, int tt) -> h8 {
@@ -227,8 +254,12 @@ __global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
 #pragma unroll
             for (int jj = 0; jj < NM; ++jj) {
 #pragma unroll
-                for (int rg = 0; rg < RG; ++rg)
-                    acc[rg][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[jj], frag(q[rg], jj), acc[rg][0], 0, 0, 0);
+                for (int rg = 0; rg < RG; ++rg) {
+                    const h8 b = frag(q[rg], jj);
+                    acc[rg][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[jj], b, acc[rg][0], 0, 0, 0);
+                    if constexpr (PLANES2)
+                        acc[rg][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[jj], nf2_lo(b), acc[rg][0], 0, 0, 0);
+                }
             }
 #pragma unroll
             for (int rg = 0; rg < RG; ++rg) q[rg] = qn[rg];
@@ -266,6 +297,12 @@ __global__ __launch_bounds__(NW * 64) void linear_kernel(const LinP p) {
 #pragma unroll
                     for (int tt = 0; tt < TT; ++tt)
                         acc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[tt], b, acc[rg][tt], 0, 0, 0);
+                    if constexpr (PLANES2) {
+                        const h8 bl = nf2_lo(b);
+#pragma unroll
+                        for (int tt = 0; tt < TT; ++tt)
+                            acc[rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[tt], bl, acc[rg][tt], 0, 0, 0);
+                    }
                 }
 #pragma unroll
                 for (int tt = 0; tt < TT; ++tt) a[tt] = an[tt];
@@ -428,25 +465,25 @@ inline bool al16(const void* ptr, int64_t ld_elems) {
     return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld_elems % 8 == 0;
 }
 
-template <int WT, int LB, bool ZP>
+template <int WT, int QF, int LB, bool ZP>
 void launch(const LinP& p, hipStream_t s) {
     const int64_t groups = ceil_div(ZP ? p.r32 : p.rows, 16);
     if (p.T <= kDecodeMax) {
         constexpr int NW = ZP ? kDecodeWavesZ : kDecodeWaves;
         const dim3 grid((unsigned)groups, ZP ? kDecodeSplitZ : 1);
-        hipLaunchKernelGGL((linear_kernel<WT, LB, ZP, 1, 1, NW, true>), grid, dim3(NW * 64), 0, s, p);
+        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, 1, 1, NW, true>), grid, dim3(NW * 64), 0, s, p);
     } else {
         constexpr int NW = ZP ? 1 : 4, RG = ZP ? 1 : kPrefillGroups;
         const dim3 grid((unsigned)ceil_div(groups, NW * RG), (unsigned)ceil_div(p.T, kPrefillTiles * 16));
-        hipLaunchKernelGGL((linear_kernel<WT, LB, ZP, kPrefillTiles, RG, NW, false>), grid, dim3(NW * 64), 0, s, p);
+        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, kPrefillTiles, RG, NW, false>), grid, dim3(NW * 64), 0, s, p);
     }
 }
 
-template <int WT>
+template <int WT, int QF>
 void launch_layer(const LinP& p, int l_bits, hipStream_t s) {
-    if (l_bits == 2) launch<WT, 2, false>(p, s);
-    else if (l_bits == 4) launch<WT, 4, false>(p, s);
-    else launch<WT, 16, false>(p, s);
+    if (l_bits == 2) launch<WT, QF, 2, false>(p, s);
+    else if (l_bits == 4) launch<WT, QF, 4, false>(p, s);
+    else launch<WT, QF, 16, false>(p, s);
 }
 
 inline bool coded(int bits) { return bits == 2 || bits == 4; }
@@ -519,8 +556,12 @@ cq_linear_packed_args with_fp16_factors(const cq_linear_args* a) {
     return b;
 }
 
-int forward(const cq_linear_packed_args* a, void* ws, size_t ws_bytes, void* stream, const char* who) {
+int forward(const cq_linear_packed_args* a, int q_format, void* ws, size_t ws_bytes, void* stream, const char* who) {
     if (int st = validate(a)) return st;
+    CQ_REQUIRE(q_format == CQ_QFMT_UNIFORM || q_format == CQ_QFMT_NF, "%s: unknown q_format %d", who, q_format);
+    const bool nf = q_format == CQ_QFMT_NF;
+    CQ_REQUIRE(!nf || (std::isfinite(a->qscale) && a->qscale >= 0.f), "%s: NF scale %g is not finite and >= 0", who,
+               (double)a->qscale);
     if (a->tokens == 0) return CQ_OK;
     const size_t need = workspace_bytes(a->tokens, a->r);
     if (need) {
@@ -553,13 +594,13 @@ int forward(const cq_linear_packed_args* a, void* ws, size_t ws_bytes, void* str
         if (rcoded) {
             z.w = a->R_codes;
             z.wstride = a->r_code_stride;
-            if (a->r_bits == 2) launch<2, 16, true>(z, s);
-            else launch<4, 16, true>(z, s);
+            if (a->r_bits == 2) launch<2, CQ_QFMT_UNIFORM, 16, true>(z, s);
+            else launch<4, CQ_QFMT_UNIFORM, 16, true>(z, s);
         } else {
             z.w = reinterpret_cast<const uint8_t*>(a->R);
             z.wstride = a->ldr;
             z.w_al = al16(a->R, a->ldr);
-            launch<16, 16, true>(z, s);
+            launch<16, CQ_QFMT_UNIFORM, 16, true>(z, s);
         }
         char what[64];
         snprintf(what, sizeof what, "%s (z)", who);
@@ -579,15 +620,21 @@ int forward(const cq_linear_packed_args* a, void* ws, size_t ws_bytes, void* str
     p.zp = reinterpret_cast<const float*>(ws);
     p.zh = zh;
     p.zl = zl;
-    p.sk = a->qscale / kmax(a->bits);
+    // one fp32 division: s / k, or s / D with the level table's denominator
+    p.sk = a->qscale / (nf ? (a->bits == 4 ? kNF4D : kNF2D) : kmax(a->bits));
     p.gs = a->gscale;
     p.bias = a->bias;
     p.y = a->y;
     p.y_f16 = a->y_dtype == CQ_F16;
     p.ldy = a->ldy;
     const int l_bits = lcoded ? a->l_bits : 16;
-    if (a->bits == 2) launch_layer<2>(p, l_bits, s);
-    else launch_layer<4>(p, l_bits, s);
+    if (nf) {
+        if (a->bits == 2) launch_layer<2, CQ_QFMT_NF>(p, l_bits, s);
+        else launch_layer<4, CQ_QFMT_NF>(p, l_bits, s);
+    } else {
+        if (a->bits == 2) launch_layer<2, CQ_QFMT_UNIFORM>(p, l_bits, s);
+        else launch_layer<4, CQ_QFMT_UNIFORM>(p, l_bits, s);
+    }
     return check_launch(who);
 }
 
@@ -607,9 +654,18 @@ extern "C" size_t cq_linear_packed_workspace(const cq_linear_packed_args* a) {
 extern "C" int cq_linear_forward(const cq_linear_args* a, void* ws, size_t ws_bytes, void* stream) {
     CQ_REQUIRE(a != nullptr, "cq_linear: null args");
     const cq_linear_packed_args b = with_fp16_factors(a);
-    return forward(&b, ws, ws_bytes, stream, "cq_linear_forward");
+    return forward(&b, CQ_QFMT_UNIFORM, ws, ws_bytes, stream, "cq_linear_forward");
 }
 
 extern "C" int cq_linear_packed_forward(const cq_linear_packed_args* a, void* ws, size_t ws_bytes, void* stream) {
-    return forward(a, ws, ws_bytes, stream, "cq_linear_packed_forward");
+    return forward(a, CQ_QFMT_UNIFORM, ws, ws_bytes, stream, "cq_linear_packed_forward");
+}
+
+extern "C" size_t cq_linear_codebook_workspace(const cq_linear_codebook_args* a) {
+    return a == nullptr ? 0 : workspace_bytes(a->p.tokens, a->p.r);
+}
+
+extern "C" int cq_linear_codebook_forward(const cq_linear_codebook_args* a, void* ws, size_t ws_bytes, void* stream) {
+    CQ_REQUIRE(a != nullptr, "cq_linear_codebook_forward: null args");
+    return forward(&a->p, a->q_format, ws, ws_bytes, stream, "cq_linear_codebook_forward");
 }

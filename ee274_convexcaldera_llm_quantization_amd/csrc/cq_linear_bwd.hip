@@ -34,11 +34,19 @@
 // whatever the tail holds, so that epilogue writes zero halves for q >= r, and R's rows >= r are
 // written to LDS as zeros like any row past an operand's end.  cq_linear_backward_input is this path
 // with fp16 factors and uscale = 1.
+//
+// Codebook Q (cq_linear_codebook_backward_input, CQ_QFMT_NF): the layer's codes are NF4 / NF2 level
+// indices, the Q term (s / D) * sum_i dy[t, i] I[idx[i, j]] (cq_linear.hip's header).  The chunk walk
+// is the same; `to_lds` expands a piece through the byte-indexed LDS level table of cq_nf.h (shared with the forward) instead
+// of the magic numbers.  NF2: the image holds the hi plane; the lo plane (+-1, the level's sign) is
+// made from the transposed fragment in registers and multiplied into the same accumulator after
+// it.  A zero row past the operand's end becomes +1 there and meets dy's zero.
 #include <cmath>
 #include <cstdio>
 #include <type_traits>
 
 #include "cq_common.h"
+#include "cq_nf.h"
 
 namespace cq {
 namespace {
@@ -157,11 +165,16 @@ __device__ __forceinline__ Raw fetch(const Src& s, int64_t row, int64_t col) {
 // position of row i in a block: bits 2 and 3 swapped
 __device__ __forceinline__ int prow(int i) { return (i & 0x13) | ((i & 4) << 1) | ((i & 8) >> 1); }
 
-template <int W>
-__device__ __forceinline__ void to_lds(const Raw& w, unsigned char* image, int row, int block) {
+// nftab: the level table when the codes are level indices (NF), else unused
+template <int W, bool NF>
+__device__ __forceinline__ void to_lds(const Raw& w, unsigned char* image, int row, int block, const uint32_t* nftab) {
     h8 lo, hi;
     if constexpr (W == 16) {
         lo = __builtin_bit_cast(h8, w.a), hi = __builtin_bit_cast(h8, w.b);
+    } else if constexpr (NF) {
+        lo = expand_nf<W>(nftab, w.a[0], 0);
+        hi = W == 2 ? expand_nf<W>(nftab, w.a[0], 1) : expand_nf<W>(nftab, w.a[1], 0);
+        if (!w.b[0]) lo = hi = h8{0, 0, 0, 0, 0, 0, 0, 0};
     } else {
         lo = expand<W>(w.a[0], 0), hi = W == 2 ? expand<W>(w.a[0], 1) : expand<W>(w.a[1], 0);
         if (!w.b[0]) lo = hi = h8{0, 0, 0, 0, 0, 0, 0, 0};
@@ -186,9 +199,10 @@ __device__ __forceinline__ h4 tr_read(const unsigned char* p) {
 // chunks whose prefetches need no mask (afull: all the workgroup's tokens exist and their rows are
 // aligned; the tile's 128 columns inside the operand; whole chunks of rows) run in a loop of their
 // own, compiled without the masks (full = true_type); the masked loop takes the rest.
-template <int W, int TT, int NA, class LoadA>
+// NF: s holds NF level indices, expanded through nftab (W = 2: two planes per B fragment).
+template <int W, int TT, int NA, bool NF, class LoadA>
 __device__ __forceinline__ void product(f4 (&acc)[TT][kBlocks], unsigned char (*lds)[kImageBytes], const Src& s,
-                                        int64_t col0, bool afull, LoadA load_a) {
+                                        int64_t col0, bool afull, LoadA load_a, const uint32_t* nftab = nullptr) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int li = lane & 15, g = lane >> 4;
     const int frow = tid >> 3, fblock = tid & 7;  // the thread's piece of a chunk
@@ -200,7 +214,7 @@ __device__ __forceinline__ void product(f4 (&acc)[TT][kBlocks], unsigned char (*
     const int64_t nfull = tile_full ? s.rows / kRows : 0;  // whole chunks of a tile without masks
 
     Raw w = fetch<W, false>(s, frow, fcol);
-    to_lds<W>(w, lds[0], frow, fblock);
+    to_lds<W, NF>(w, lds[0], frow, fblock, nftab);
     if (nchunks > 1) w = fetch<W, false>(s, kRows + frow, fcol);
     h8 a[TT][NA], an[TT][NA];
 #pragma unroll
@@ -212,7 +226,7 @@ __device__ __forceinline__ void product(f4 (&acc)[TT][kBlocks], unsigned char (*
         for (int64_t c = cb; c < ce; ++c) {
             const unsigned char* cur = lds[c & 1];
             if (FULL || c + 1 < nchunks) {
-                to_lds<W>(w, lds[(c + 1) & 1], frow, fblock);
+                to_lds<W, NF>(w, lds[(c + 1) & 1], frow, fblock, nftab);
                 if (FULL || c + 2 < nchunks) w = fetch<W, FULL>(s, (c + 2) * kRows + frow, fcol);
 #pragma unroll
                 for (int tt = 0; tt < TT; ++tt) load_a(c + 1, tt, an[tt], full);
@@ -226,6 +240,14 @@ __device__ __forceinline__ void product(f4 (&acc)[TT][kBlocks], unsigned char (*
 #pragma unroll
                     for (int ia = 0; ia < NA; ++ia)
                         acc[tt][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[tt][ia], bf, acc[tt][b], 0, 0, 0);
+                if constexpr (NF && W == 2) {
+                    const h8 bl = nf2_lo(bf);
+#pragma unroll
+                    for (int tt = 0; tt < TT; ++tt)
+#pragma unroll
+                        for (int ia = 0; ia < NA; ++ia)
+                            acc[tt][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[tt][ia], bl, acc[tt][b], 0, 0, 0);
+                }
             }
             if (FULL || c + 1 < nchunks) {
 #pragma unroll
@@ -254,10 +276,19 @@ struct BwdP {
 };
 
 // UK: the u product (W: L's rows, fp16 or codes), else codes (W = 2 / 4) + R (WR: fp16 or codes) +
-// epilogue
-template <int W, int WR, bool UK, int TT>
+// epilogue; QF: the layer's codes are uniform codes or NF level indices
+template <int W, int QF, int WR, bool UK, int TT>
 __global__ __launch_bounds__(kWaves * 64) void linear_bwd_kernel(const BwdP p) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[2][kImageBytes];
+    constexpr bool NF = QF == CQ_QFMT_NF;
+    static_assert(!NF || (!UK && W != 16), "only the layer's own codes are level indices");
+    const uint32_t* nftab = nullptr;
+    if constexpr (NF) {  // complete before the first chunk is expanded
+        __shared__ uint32_t tab[W == 4 ? 256 : 512];
+        fill_nf_table<W>(tab, threadIdx.x, kWaves * 64);
+        __syncthreads();
+        nftab = tab;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, g = lane >> 4;
     const int64_t tok0 = ((int64_t)blockIdx.x * kWaves + wave) * (TT * 16);
@@ -279,7 +310,7 @@ __global__ __launch_bounds__(kWaves * 64) void linear_bwd_kernel(const BwdP p) {
         else
             a[0] = ld8(p.dy + (t < p.T ? t : 0) * p.lddy, c * kRows + g * 8, t < p.T ? p.m : 0, p.dy_al);
     };
-    product<W, TT, 1>(acc, lds, p.w, col0, tokfull && p.dy_al, load_dy);
+    product<W, TT, 1, NF>(acc, lds, p.w, col0, tokfull && p.dy_al, load_dy, nftab);
 
     if constexpr (!UK) {
 #pragma unroll
@@ -299,7 +330,7 @@ __global__ __launch_bounds__(kWaves * 64) void linear_bwd_kernel(const BwdP p) {
                     a[1] = ld8(p.uh + o, c * kRows + g * 8, t < p.T ? p.r32 : 0, true);
                 }
             };
-            product<WR, TT, 2>(acc, lds, p.R, col0, tokfull, load_u);
+            product<WR, TT, 2, false>(acc, lds, p.R, col0, tokfull, load_u);
         }
     }
 
@@ -411,21 +442,26 @@ cq_linear_packed_backward_args with_fp16_factors(const cq_linear_backward_args* 
     return b;
 }
 
-template <int W, int WR, bool UK, int TT>
+template <int W, int QF, int WR, bool UK, int TT>
 void launch(const BwdP& p, int64_t cols, hipStream_t s) {
     const dim3 grid((unsigned)ceil_div(p.T, kWaves * TT * 16), (unsigned)ceil_div(cols, kCols));
-    hipLaunchKernelGGL((linear_bwd_kernel<W, WR, UK, TT>), grid, dim3(kWaves * 64), 0, s, p);
+    hipLaunchKernelGGL((linear_bwd_kernel<W, QF, WR, UK, TT>), grid, dim3(kWaves * 64), 0, s, p);
 }
 
-template <int W>
+template <int W, int QF>
 void launch_main(const BwdP& p, int r_bits, hipStream_t s) {
-    if (r_bits == 2) launch<W, 2, false, kTilesMain>(p, p.n, s);
-    else if (r_bits == 4) launch<W, 4, false, kTilesMain>(p, p.n, s);
-    else launch<W, 16, false, kTilesMain>(p, p.n, s);
+    if (r_bits == 2) launch<W, QF, 2, false, kTilesMain>(p, p.n, s);
+    else if (r_bits == 4) launch<W, QF, 4, false, kTilesMain>(p, p.n, s);
+    else launch<W, QF, 16, false, kTilesMain>(p, p.n, s);
 }
 
-int backward(const cq_linear_packed_backward_args* a, void* ws, size_t ws_bytes, void* stream, const char* who) {
+int backward(const cq_linear_packed_backward_args* a, int q_format, void* ws, size_t ws_bytes, void* stream,
+             const char* who) {
     if (int st = validate(a, who)) return st;
+    CQ_REQUIRE(q_format == CQ_QFMT_UNIFORM || q_format == CQ_QFMT_NF, "%s: unknown q_format %d", who, q_format);
+    const bool nf = q_format == CQ_QFMT_NF;
+    CQ_REQUIRE(!nf || (std::isfinite(a->qscale) && a->qscale >= 0.f), "%s: NF scale %g is not finite and >= 0", who,
+               (double)a->qscale);
     const size_t need = workspace_bytes(a->tokens, a->r);
     if (need) {
         CQ_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned",
@@ -453,11 +489,11 @@ int backward(const cq_linear_packed_backward_args* a, void* ws, size_t ws_bytes,
         u.ldu = a->ldu;
         if (lcoded) {
             u.w = Src{a->L_codes, a->l_code_stride, 1, a->m, a->r};
-            if (a->l_bits == 2) launch<2, 16, true, kTilesU>(u, p.r32, s);
-            else launch<4, 16, true, kTilesU>(u, p.r32, s);
+            if (a->l_bits == 2) launch<2, CQ_QFMT_UNIFORM, 16, true, kTilesU>(u, p.r32, s);
+            else launch<4, CQ_QFMT_UNIFORM, 16, true, kTilesU>(u, p.r32, s);
         } else {
             u.w = Src{a->L, a->ldl, al16(a->L, a->ldl), a->m, a->r};
-            launch<16, 16, true, kTilesU>(u, p.r32, s);
+            launch<16, CQ_QFMT_UNIFORM, 16, true, kTilesU>(u, p.r32, s);
         }
         char what[64];
         snprintf(what, sizeof what, "%s (u)", who);
@@ -466,14 +502,20 @@ int backward(const cq_linear_packed_backward_args* a, void* ws, size_t ws_bytes,
     p.w = Src{a->codes, a->code_stride, 1, a->m, a->n};
     if (rcoded) p.R = Src{a->R_codes, a->r_code_stride, 1, a->r, a->n};
     else p.R = Src{a->R, a->ldr, a->r > 0 && al16(a->R, a->ldr), a->r, a->n};
-    p.sk = a->qscale / kmax(a->bits);
+    // one fp32 division: s / k, or s / D with the level table's denominator
+    p.sk = a->qscale / (nf ? (a->bits == 4 ? kNF4D : kNF2D) : kmax(a->bits));
     p.gs = a->gscale;
     p.dx = a->dx;
     p.dx_f16 = a->dx_dtype == CQ_F16;
     p.lddx = a->lddx;
     const int r_bits = rcoded ? a->r_bits : 16;
-    if (a->bits == 2) launch_main<2>(p, r_bits, s);
-    else launch_main<4>(p, r_bits, s);
+    if (nf) {
+        if (a->bits == 2) launch_main<2, CQ_QFMT_NF>(p, r_bits, s);
+        else launch_main<4, CQ_QFMT_NF>(p, r_bits, s);
+    } else {
+        if (a->bits == 2) launch_main<2, CQ_QFMT_UNIFORM>(p, r_bits, s);
+        else launch_main<4, CQ_QFMT_UNIFORM>(p, r_bits, s);
+    }
     return check_launch(who);
 }
 
@@ -493,11 +535,20 @@ extern "C" size_t cq_linear_packed_backward_workspace(const cq_linear_packed_bac
 extern "C" int cq_linear_backward_input(const cq_linear_backward_args* a, void* ws, size_t ws_bytes, void* stream) {
     CQ_REQUIRE(a != nullptr, "cq_linear_backward_input: null args");
     const cq_linear_packed_backward_args b = with_fp16_factors(a);
-    return backward(&b, ws, ws_bytes, stream, "cq_linear_backward_input");
+    return backward(&b, CQ_QFMT_UNIFORM, ws, ws_bytes, stream, "cq_linear_backward_input");
 }
 
 extern "C" int cq_linear_packed_backward_input(const cq_linear_packed_backward_args* a, void* ws, size_t ws_bytes,
                                                void* stream) {
-    return backward(a, ws, ws_bytes, stream, "cq_linear_packed_backward_input");
+    return backward(a, CQ_QFMT_UNIFORM, ws, ws_bytes, stream, "cq_linear_packed_backward_input");
 }
 
+extern "C" size_t cq_linear_codebook_backward_workspace(const cq_linear_codebook_backward_args* a) {
+    return a == nullptr ? 0 : workspace_bytes(a->p.tokens, a->p.r);
+}
+
+extern "C" int cq_linear_codebook_backward_input(const cq_linear_codebook_backward_args* a, void* ws, size_t ws_bytes,
+                                                 void* stream) {
+    CQ_REQUIRE(a != nullptr, "cq_linear_codebook_backward_input: null args");
+    return backward(&a->p, a->q_format, ws, ws_bytes, stream, "cq_linear_codebook_backward_input");
+}

@@ -1272,6 +1272,20 @@ class CalderaEngine:
         self.last_packed = [dict(codes=best.Qc[b], Q_scale=qs[b], L=best.L[b], R=best.R[b], global_scale=gsl[b],
                                  errors={k: v[b] for k, v in errors.items()})
                             for b in range(B)]
+        if best.dense_q and p.method_Q in ("nf4", "nf2") and any(best.flag_Q):
+            # NF Q with a kept iterate: the level indices packed in the storage layout of the
+            # uniform codes (MSB-first, flat over the (m, n) grid) with the matrix's one scale, so
+            # the compact form carries Q (torch ops at the end of a run: not on the hot path)
+            bits = qlog.code_bits(p.method_Q, p.Q_bits)
+            per = 8 // bits
+            kept = [b for b in range(B) if best.flag_Q[b]]
+            scales = torch.cat([best.q_items[b][1].reshape(1) for b in kept]).tolist()
+            for b, sc in zip(kept, scales):
+                idx = best.q_items[b][0].reshape(-1, per)
+                codes = torch.zeros(idx.shape[0], dtype=torch.uint8, device=idx.device)
+                for i in range(per):
+                    codes |= idx[:, i] << (bits * (per - 1 - i))
+                self.last_packed[b].update(codes=codes, Q_scale=sc, Q_method=p.method_Q)
         if torch.is_tensor(best.L_idxs):
             # uniform L, R with a kept iterate: the factors' integer codes, (m, r) and (r, n), and
             # their scales -- L = (L_codes / k_L) L_scale exactly, so a consumer need not store

@@ -18,6 +18,11 @@ Every layer back-propagates dx from its packed form (csrc/cq_linear_bwd.hip:
 cq_linear_backward_input, with a coded factor cq_linear_packed_backward_input), and
 HadamardCalderaLinear around it with cq_hadamard_rows on dy and dx; fp16 factors can be
 trained over the frozen codes, coded ones stay frozen.
+
+Q may also be an NF4 / NF2 codebook (`q_format` = Q_FORMAT_NF): `codes` then holds the level
+indices in the same layout, `qscale` the matrix scale, and the layer runs through
+cq_linear_codebook_forward / cq_linear_codebook_backward_input with
+Q = I[idx] (s / D), I the integer levels (include/caldera_hip.h).  Factors stay fp16 or uniform.
 """
 from __future__ import annotations
 
@@ -26,6 +31,29 @@ import torch
 from . import _lib as K
 
 SUPPORTED_BITS = (2, 4)
+Q_FORMAT_UNIFORM, Q_FORMAT_NF = K.QFMT_UNIFORM, K.QFMT_NF
+# Q quantiser methods with packed codes -> (q_format, bits)
+Q_METHODS = {"uniform": (Q_FORMAT_UNIFORM, None), "nf4": (Q_FORMAT_NF, 4), "nf2": (Q_FORMAT_NF, 2)}
+NF_TAIL_INDEX = {4: 8, 2: 0}  # the index a row's tail holds (NF4: level 0; NF2 has no zero level)
+
+
+def q_method_format(Q_method: str, Q_bits: int) -> int:
+    """The q_format of a Q quantiser method at Q_bits; raises for a method without packed codes
+    (bbint*) and for nf4 / nf2 at other bits than 4 / 2."""
+    method = str(Q_method).lower()
+    if method in ("bbint4", "bbint2"):
+        raise ValueError(f"CalderaLinear: Q method {method!r} has no packed form: its codes are affine per block "
+                         "(one minimum and one scale per block) plus an outlier list, not one scale per matrix")
+    if method not in Q_METHODS:
+        raise ValueError(f"CalderaLinear: unknown Q method {Q_method!r} (uniform, nf4, nf2)")
+    fmt, bits = Q_METHODS[method]
+    if bits is not None and bits != Q_bits:
+        raise ValueError(f"CalderaLinear: Q method {method!r} needs Q_bits = {bits}, got {Q_bits}")
+    return fmt
+
+
+def q_method_name(q_format: int, bits: int) -> str:
+    return "uniform" if q_format == Q_FORMAT_UNIFORM else f"nf{bits}"
 
 
 def _k(bits: int) -> int:
@@ -70,13 +98,41 @@ def unpack_bytes(b: torch.Tensor, bits: int) -> torch.Tensor:
     return (u.to(torch.int16) - k).to(torch.int8)
 
 
+def pack_index_rows(idx: torch.Tensor, bits: int) -> torch.Tensor:
+    """(m, n) NF level indices in [0, 2^bits) -> (m, row_bytes) uint8 inference layout (the index
+    itself, MSB-first, the row's tail filled with NF_TAIL_INDEX)."""
+    per = 8 // bits
+    m, n = idx.shape
+    rb = row_bytes(n, bits)
+    u = torch.full((m, rb * per), NF_TAIL_INDEX[bits], dtype=torch.uint8, device=idx.device)
+    u[:, :n] = idx.to(torch.uint8)
+    u = u.view(m, rb, per)
+    out = torch.zeros((m, rb), dtype=torch.uint8, device=idx.device)
+    for i in range(per):
+        out |= u[:, :, i] << (bits * (per - 1 - i))
+    return out
+
+
+def unpack_index_bytes(b: torch.Tensor, bits: int) -> torch.Tensor:
+    """uint8 (..., nbytes) packed level indices -> uint8 (..., nbytes * 8 / bits) indices."""
+    per = 8 // bits
+    parts = [((b >> (bits * (per - 1 - i))) & (2 ** bits - 1)) for i in range(per)]
+    return torch.stack(parts, dim=-1).reshape(*b.shape[:-1], b.shape[-1] * per)
+
+
 def _launch_packed(lin, x2: torch.Tensor, y: torch.Tensor, L16=None, R16=None):
     """The entry `CalderaLinear.forward` takes for this layer, on given fp16 x2 (T, in_features)
     and y (T, out_features): cq_linear_packed_forward with a coded factor, else cq_linear_forward.
     L16 / R16: the fp16 factors to use instead of the layer's buffers (masters rounded to fp16)."""
     L = lin.L if L16 is None else L16
     R = lin.R if R16 is None else R16
-    if lin.rank and (lin.L_codes is not None or lin.R_codes is not None):
+    if lin.q_format != Q_FORMAT_UNIFORM:
+        K.linear_codebook_forward(
+            x2, lin.codes, lin.qscale, lin.gscale, L if lin.rank else None, R if lin.rank else None, lin.bias, y,
+            m=lin.out_features, n=lin.in_features, bits=lin.bits, q_format=lin.q_format, r=lin.rank,
+            L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
+            R_codes=None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits))
+    elif lin.rank and (lin.L_codes is not None or lin.R_codes is not None):
         K.linear_packed_forward(
             x2, lin.codes, lin.qscale, lin.gscale, L, R, lin.bias, y, m=lin.out_features,
             n=lin.in_features, bits=lin.bits, r=lin.rank,
@@ -105,7 +161,15 @@ def _packed_backward(lin, dy16, x2, L16, R16, needs, dx_dtype, factor_dtypes):
     dx2 = dL = dR = u = None
     if need_x:
         dx2 = torch.empty((T, n), dtype=dx_dtype, device=dy16.device)
-        if r and (lin.L_codes is not None or lin.R_codes is not None):
+        if lin.q_format != Q_FORMAT_UNIFORM:
+            if r and need_R and lin.R_codes is None:
+                u = torch.empty((T, r), dtype=torch.float32, device=dy16.device)
+            K.linear_codebook_backward_input(
+                dy16, lin.codes, lin.qscale, gs, L16 if r else None, R16 if r else None, dx2, m=m, n=n, bits=lin.bits,
+                q_format=lin.q_format, r=r, u_out=u,
+                L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
+                R_codes=None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits))
+        elif r and (lin.L_codes is not None or lin.R_codes is not None):
             K.linear_packed_backward_input(
                 dy16, lin.codes, lin.qscale, gs, L16, R16, dx2, m=m, n=n, bits=lin.bits, r=r,
                 L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
@@ -219,7 +283,9 @@ class CalderaLinear(torch.nn.Module):
     (out_features, row_bytes(rank, L_bits)) resp. `R_codes` (rank, row_bytes(in_features, R_bits))
     uint8 instead, with `lscale` / `rscale`, and its fp16 buffer is None.  Plain attributes:
     qscale, gscale, bits, in_features, out_features, rank, lscale, rscale, L_bits, R_bits (16 =
-    fp16 factor), also carried as the state dict's extra state.
+    fp16 factor), q_format (Q_FORMAT_UNIFORM: `codes` are offset-binary uniform codes;
+    Q_FORMAT_NF: NF4 / NF2 level indices, qscale the matrix scale; no buffer of its own), also
+    carried as the state dict's extra state.
 
     forward(x): any leading dimensions, last = in_features, on a HIP device (there is no CPU
     path).  x is cast to fp16 and the result returned in x's dtype: bf16 activations beyond
@@ -235,11 +301,16 @@ class CalderaLinear(torch.nn.Module):
     and the fp16 factor beside it: only a layer with two fp16 factors trains them."""
 
     def __init__(self, codes, L, R, bias=None, *, qscale, gscale, bits, in_features, out_features, L_codes=None,
-                 R_codes=None):
+                 R_codes=None, q_format=Q_FORMAT_UNIFORM):
         """L_codes / R_codes: (uint8 inference-layout codes, scale, bits) of a coded factor,
         whose fp16 L / R is then None."""
         super().__init__()
         _check_bits(bits)
+        if q_format not in (Q_FORMAT_UNIFORM, Q_FORMAT_NF):
+            raise ValueError(f"CalderaLinear: unknown q_format {q_format!r}")
+        if q_format == Q_FORMAT_NF and not (float(qscale) >= 0.0 and float(qscale) != float("inf")):
+            raise ValueError(f"CalderaLinear: NF scale {float(qscale)} is not finite and >= 0")
+        self.q_format = int(q_format)
         m, n = int(out_features), int(in_features)
         if codes.dtype != torch.uint8 or tuple(codes.shape) != (m, row_bytes(n, bits)):
             raise ValueError(f"CalderaLinear: codes must be uint8 {(m, row_bytes(n, bits))} (inference layout), "
@@ -296,12 +367,20 @@ class CalderaLinear(torch.nn.Module):
 
     # ------------------------------------------------------------------ constructors
     @classmethod
-    def from_codes(cls, c, L, R, bias=None, *, qscale, gscale, bits, L_codes=None, R_codes=None):
-        """From (m, n) integer codes in [-k, k].  L_codes = (cL, sL, bits) / R_codes = (cR, sR,
+    def from_codes(cls, c, L, R, bias=None, *, qscale, gscale, bits, L_codes=None, R_codes=None,
+                   q_format=Q_FORMAT_UNIFORM):
+        """From (m, n) integer codes in [-k, k]; with q_format = Q_FORMAT_NF from an (m, n) integer
+        matrix of NF level indices in [0, 2^bits).  L_codes = (cL, sL, bits) / R_codes = (cR, sR,
         bits): a factor as (m, r) resp. (r, n) integer codes in [-k, k] with its scale, i.e.
         L = (cL / k) sL; its fp16 L / R is then None."""
         _check_bits(bits)
         m, n = c.shape
+        if q_format == Q_FORMAT_NF:
+            if c.dtype.is_floating_point or (c.numel() and (int(c.min()) < 0 or int(c.max()) >= 2 ** bits)):
+                raise ValueError(f"CalderaLinear.from_codes: NF indices must be an integer matrix in [0, {2 ** bits})")
+            qcodes = pack_index_rows(c, bits)
+        else:
+            qcodes = pack_rows(c, bits)
 
         def packed(spec, what):
             if spec is None:
@@ -313,8 +392,8 @@ class CalderaLinear(torch.nn.Module):
                                  f"[-{_k(fbits)}, {_k(fbits)}]")
             return pack_rows(cf, fbits), scale, fbits
 
-        return cls(pack_rows(c, bits), L, R, bias, qscale=qscale, gscale=gscale, bits=bits, in_features=n,
-                   out_features=m, L_codes=packed(L_codes, "L"), R_codes=packed(R_codes, "R"))
+        return cls(qcodes, L, R, bias, qscale=qscale, gscale=gscale, bits=bits, in_features=n,
+                   out_features=m, L_codes=packed(L_codes, "L"), R_codes=packed(R_codes, "R"), q_format=q_format)
 
     @classmethod
     def from_result(cls, res, bias=None):
@@ -327,34 +406,46 @@ class CalderaLinear(torch.nn.Module):
         flat = res.codes.reshape(-1)
         if flat.dtype != torch.uint8 or flat.numel() != nbytes or (m * npad * res.Q_bits) % 8:
             raise ValueError(f"CalderaLinear.from_result: {res.name}: codes are not {nbytes} packed bytes")
-        c = unpack_bytes(flat, res.Q_bits).view(m, npad)[:, :n]
+        # an NF result stores the level index as it is, in the same storage layout
+        q_format = q_method_format(getattr(res, "Q_method", "uniform"), res.Q_bits)
+        if q_format == Q_FORMAT_NF:
+            qcodes = pack_index_rows(unpack_index_bytes(flat, res.Q_bits).view(m, npad)[:, :n], res.Q_bits)
+        else:
+            qcodes = pack_rows(unpack_bytes(flat, res.Q_bits).view(m, npad)[:, :n], res.Q_bits)
         # a coded factor travels in the inference layout already (its fp32 array has zero rows)
         Lc = getattr(res, "L_codes", None)
         Rc = getattr(res, "R_codes", None)
-        return cls(pack_rows(c, res.Q_bits), None if Lc is not None else res.L,
+        return cls(qcodes, None if Lc is not None else res.L,
                    None if Rc is not None else res.R[:, :n], bias, qscale=res.Q_scale, gscale=res.global_scale,
                    bits=res.Q_bits, in_features=n, out_features=m,
                    L_codes=None if Lc is None else (Lc, res.L_scale, res.L_bits),
-                   R_codes=None if Rc is None else (Rc, res.R_scale, res.R_bits))
+                   R_codes=None if Rc is None else (Rc, res.R_scale, res.R_bits), q_format=q_format)
 
     @classmethod
-    def from_decomposition(cls, dec, Q_bits, bias=None, *, L_bits=None, R_bits=None):
+    def from_decomposition(cls, dec, Q_bits, bias=None, *, L_bits=None, R_bits=None, Q_method="uniform"):
         """From a CalderaDecomposition with uniform Q: packs `Q_idxs` (the reference's int codes,
         (1, m n)) with `Q_scale`; L, R are rounded to fp16.  L_bits / R_bits (2 | 4; None: fp16):
         that factor was quantised uniformly at those bits and is kept as its codes instead --
         `L_idxs` ((1, r m), in L^T order) with `L_scale`, `R_idxs` ((1, r n)) with `R_scale`,
-        each one scale."""
+        each one scale.  Q_method "nf4" / "nf2" (the decomposition does not say how Q was
+        quantised, so it must be passed): `Q_idxs` is the uint8 level indices, `Q_scale` the one
+        scale of the matrix; Q_method must agree with Q_bits.  bbint methods have no packed form."""
         _check_bits(Q_bits)
+        q_format = q_method_format(Q_method, Q_bits)
         for what, fbits in (("L", L_bits), ("R", R_bits)):
             if fbits is not None:
                 _check_factor_bits(fbits, what)
         if dec.Q_idxs is None or dec.Q is None:
             raise ValueError("CalderaLinear.from_decomposition: the decomposition has no Q")
         qs = dec.Q_scale
-        if (not torch.is_tensor(dec.Q_idxs) or dec.Q_idxs.dtype != torch.int8
-                or (torch.is_tensor(qs) and qs.numel() != 1) or isinstance(qs, (tuple, list, dict))):
+        one_scale = not ((torch.is_tensor(qs) and qs.numel() != 1) or isinstance(qs, (tuple, list, dict)))
+        if q_format == Q_FORMAT_NF:
+            if not torch.is_tensor(dec.Q_idxs) or dec.Q_idxs.dtype != torch.uint8 or not one_scale:
+                raise ValueError(f"CalderaLinear.from_decomposition: Q_method {Q_method!r} needs uint8 level indices "
+                                 "and one scale (the NF quantiser with one block per matrix)")
+        elif not torch.is_tensor(dec.Q_idxs) or dec.Q_idxs.dtype != torch.int8 or not one_scale:
             raise ValueError("CalderaLinear.from_decomposition: Q is not uniformly quantised with one scale "
-                             "(nf / bbint codebooks have no packed codes)")
+                             "(nf / bbint codebooks have no packed codes unless Q_method names nf4 / nf2)")
         m, n = dec.Q.shape
         if dec.Q_idxs.numel() != m * n:
             raise ValueError("CalderaLinear.from_decomposition: Q_idxs does not hold m x n codes")
@@ -377,7 +468,8 @@ class CalderaLinear(torch.nn.Module):
         Lc = factor("L", L_bits, m, r, True)
         Rc = factor("R", R_bits, r, n, False)
         return cls.from_codes(dec.Q_idxs.reshape(m, n), None if Lc else dec.L, None if Rc else dec.R, bias,
-                              qscale=qscale, gscale=float(dec.global_scale), bits=Q_bits, L_codes=Lc, R_codes=Rc)
+                              qscale=qscale, gscale=float(dec.global_scale), bits=Q_bits, L_codes=Lc, R_codes=Rc,
+                              q_format=q_format)
 
     def to_result(self, name: str):
         """The layer as a `sharding.MatrixResult` (storage layout: codes on the (m, n padded to
@@ -394,23 +486,24 @@ class CalderaLinear(torch.nn.Module):
         R = self.R.detach().float() if self.R_codes is None else torch.zeros((0, n), device=dev)
         return MatrixResult(name, m, n, self.rank, self.bits, codes, self.qscale, L, R, self.gscale, {}, extra,
                             L_codes=self.L_codes, R_codes=self.R_codes, L_scale=self.lscale, R_scale=self.rscale,
-                            L_bits=self.L_bits, R_bits=self.R_bits)
+                            L_bits=self.L_bits, R_bits=self.R_bits, Q_method=q_method_name(self.q_format, self.bits))
 
     # ------------------------------------------------------------------ state
     def get_extra_state(self):
         return {"qscale": self.qscale, "gscale": self.gscale, "bits": self.bits, "in_features": self.in_features,
                 "out_features": self.out_features, "rank": self.rank, "lscale": self.lscale, "rscale": self.rscale,
-                "L_bits": self.L_bits, "R_bits": self.R_bits}
+                "L_bits": self.L_bits, "R_bits": self.R_bits, "q_format": self.q_format}
 
     def set_extra_state(self, state):
-        """A state saved before factor codes existed has no lscale / rscale / L_bits / R_bits: the
-        layer keeps its own (an fp16-factor layer's defaults)."""
+        """A state saved before factor codes existed has no lscale / rscale / L_bits / R_bits, one
+        saved before codebook Q no q_format: the layer keeps its own (the defaults)."""
         for key, v in state.items():
             setattr(self, key, v)
 
     def extra_repr(self):
         fac = "" if self.L_bits == self.R_bits == 16 else f", L_bits={self.L_bits}, R_bits={self.R_bits}"
-        return (f"in_features={self.in_features}, out_features={self.out_features}, bits={self.bits}, "
+        fmt = "" if self.q_format == Q_FORMAT_UNIFORM else f", q_format={q_method_name(self.q_format, self.bits)}"
+        return (f"in_features={self.in_features}, out_features={self.out_features}, bits={self.bits}{fmt}, "
                 f"rank={self.rank}{fac}, bias={self.bias is not None}")
 
     def packed_bytes(self) -> int:
@@ -431,9 +524,15 @@ class CalderaLinear(torch.nn.Module):
 
     def dense_weight(self) -> torch.Tensor:
         """gs (Q + L R) as a dense fp32 (out_features, in_features) tensor, by torch ops (checks
-        and baselines only): Q = c (s / k), a coded factor likewise."""
-        k = _k(self.bits)
-        c = unpack_bytes(self.codes, self.bits)[:, :self.in_features].float()
+        and baselines only): Q = c (s / k), a coded factor likewise; an NF layer's Q = I[idx] (s / D)
+        with the integer levels I and the fp32 division the kernel makes."""
+        if self.q_format == Q_FORMAT_NF:
+            idx = unpack_index_bytes(self.codes, self.bits)[:, :self.in_features].long()
+            c = torch.tensor(K.NF_LEVELS[self.bits], dtype=torch.float32, device=idx.device)[idx]
+            k = K.NF_DENOM[self.bits]
+        else:
+            k = _k(self.bits)
+            c = unpack_bytes(self.codes, self.bits)[:, :self.in_features].float()
         sk = (torch.tensor(self.qscale, dtype=torch.float32) / torch.tensor(float(k), dtype=torch.float32)).item()
         L, R = self.factors()
         return self.gscale * (c * sk + L @ R)
@@ -549,14 +648,14 @@ class HadamardCalderaLinear(torch.nn.Module):
 
     # ------------------------------------------------------------------ constructors
     @classmethod
-    def from_decomposition(cls, dec, Q_bits, original_shape, bias=None, L_bits=None, R_bits=None):
+    def from_decomposition(cls, dec, Q_bits, original_shape, bias=None, L_bits=None, R_bits=None, Q_method="uniform"):
         """From the CalderaDecomposition of H1 pad(W) H2 (as `CalderaLinear.from_decomposition`
-        takes it) and W's own shape (out_features, in_features)."""
+        takes it, Q_method included) and W's own shape (out_features, in_features)."""
         m, n = (int(v) for v in original_shape)
         if max(_next_pow2(m), _next_pow2(n)) > K.HADAMARD_MAX_N:
             raise ValueError(f"HadamardCalderaLinear: padded shape {(_next_pow2(m), _next_pow2(n))} exceeds "
                              f"{K.HADAMARD_MAX_N} (cq_hadamard_rows' largest transform)")
-        inner = CalderaLinear.from_decomposition(dec, Q_bits, None, L_bits=L_bits, R_bits=R_bits)
+        inner = CalderaLinear.from_decomposition(dec, Q_bits, None, L_bits=L_bits, R_bits=R_bits, Q_method=Q_method)
         return cls(inner, n, m, bias)
 
     @classmethod

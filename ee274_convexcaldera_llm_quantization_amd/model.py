@@ -203,7 +203,9 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
     packed: a layer that passes the error gate is replaced by a `linear.CalderaLinear` built
       from its decomposition (2/4-bit codes + fp16 factors, applied by cq_linear_forward)
       instead of receiving the dense `out`; the gate and the counters are unchanged.  Needs
-      uniform 2- or 4-bit Q; not with `hadamard` (the layer would need the transforms around
+      uniform 2- or 4-bit Q, or nf4 / nf2 Q (taken from `quant_params.quant_factory_Q.method`:
+      the layer then holds the level indices); a bbint Q raises ValueError before anything is
+      decomposed (per-block affine codes plus an outlier list have no packed form); not with `hadamard` (the layer would need the transforms around
       it) and not with `scale_W=True`: like main.py, the gate and the dense write-back use
       Q + L R of the scaled W without its global scale, while a packed layer applies
       gs (Q + L R), so the two would be different models and the gate would judge a weight
@@ -231,6 +233,7 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
     if packed and scale_W:
         raise ValueError("apply_caldera_quantization: packed=True cannot be combined with scale_W=True (the gate "
                          "and the write-back use Q + L R without the global scale; the packed layer applies it)")
+    q_method = str(getattr(getattr(qp, "quant_factory_Q", None), "method", "uniform")).lower()
     if packed_factors:
         if not packed:
             raise ValueError("apply_caldera_quantization: packed_factors=True needs packed=True")
@@ -241,6 +244,11 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
         if getattr(qp, "L_bits", None) not in (2, 4) or getattr(qp, "R_bits", None) not in (2, 4):
             raise ValueError(f"apply_caldera_quantization: packed_factors=True needs L_bits / R_bits in (2, 4), got "
                              f"{getattr(qp, 'L_bits', None)} / {getattr(qp, 'R_bits', None)}")
+    if packed:
+        # the Q quantiser must have a packed form (uniform, nf4, nf2: bbint raises), before
+        # anything is decomposed
+        from .linear import q_method_format
+        q_method_format(q_method, getattr(qp, "Q_bits", None))
     say = log or (lambda *a: None)
     jobs, rep = select_layers(model, hessians, selection, say)
     transform = hadamard or packed_hadamard  # decompose H1 pad(W) H2
@@ -301,9 +309,10 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                     fbits = dict(L_bits=qp.L_bits, R_bits=qp.R_bits) if packed_factors else {}
                     bias = getattr(module, "bias", None)
                     if packed_hadamard:
-                        lin = HadamardCalderaLinear.from_decomposition(dec, qp.Q_bits, shapes[i], bias=bias, **fbits)
+                        lin = HadamardCalderaLinear.from_decomposition(dec, qp.Q_bits, shapes[i], bias=bias,
+                                                                       Q_method=q_method, **fbits)
                     else:
-                        lin = CalderaLinear.from_decomposition(dec, qp.Q_bits, bias=bias, **fbits)
+                        lin = CalderaLinear.from_decomposition(dec, qp.Q_bits, bias=bias, Q_method=q_method, **fbits)
                     _set_module(model, name, lin.to(W.device))
                     rep.quantized_param_count += W.numel()
                     say(f"Applied CALDERA (packed{', Hadamard' if packed_hadamard else ''}) to {name}.weight, shape: "

@@ -80,6 +80,9 @@ class MatrixResult:
     R_scale: float = 1.0
     L_bits: int = 16
     R_bits: int = 16
+    # the Q quantiser: "uniform" (offset-binary codes), or "nf4" / "nf2" (`codes` holds the level
+    # indices in the same storage layout, Q_scale the matrix scale)
+    Q_method: str = "uniform"
 
 
 def _pad(nbytes: int) -> int:
@@ -100,6 +103,8 @@ def pack_results(results: list[MatrixResult], device=None) -> torch.Tensor:
         entry = {"name": r.name, "m": r.m, "n": r.n, "rank": r.rank, "Q_bits": r.Q_bits,
                  "Q_scale": float(r.Q_scale), "global_scale": float(r.global_scale),
                  "errors": r.errors, "extra": r.extra, "arrays": {}}
+        if r.Q_method != "uniform":  # an optional meta key (a plain result's key set is unchanged)
+            entry["Q_method"] = str(r.Q_method)
         arrays = [("codes", r.codes), ("L", r.L), ("R", r.R)]
         # factor codes: optional arrays and meta keys (a payload without them reads as before)
         for key, t, scale, bits in (("L", r.L_codes, r.L_scale, r.L_bits), ("R", r.R_codes, r.R_scale, r.R_bits)):
@@ -146,7 +151,7 @@ def unpack_results(buf: torch.Tensor) -> list[MatrixResult]:
                                 e["Q_scale"], arrs["L"], arrs["R"], e["global_scale"], e["errors"],
                                 e.get("extra", {}), arrs.get("L_codes"), arrs.get("R_codes"),
                                 e.get("L_scale", 1.0), e.get("R_scale", 1.0), e.get("L_bits", 16),
-                                e.get("R_bits", 16)))
+                                e.get("R_bits", 16), e.get("Q_method", "uniform")))
     return out
 
 
@@ -242,6 +247,8 @@ def _blob(results, dev):
         entry = {"name": r.name, "m": r.m, "n": r.n, "rank": r.rank, "Q_bits": r.Q_bits,
                  "Q_scale": float(r.Q_scale), "global_scale": float(r.global_scale),
                  "errors": r.errors, "extra": r.extra, "arrays": {}}
+        if r.Q_method != "uniform":  # an optional meta key (a plain result's key set is unchanged)
+            entry["Q_method"] = str(r.Q_method)
         arrays = [("codes", r.codes), ("L", r.L), ("R", r.R)]
         # factor codes: optional arrays and meta keys (a payload without them reads as before)
         for key, t, scale, bits in (("L", r.L_codes, r.L_scale, r.L_bits), ("R", r.R_codes, r.R_scale, r.R_bits)):
@@ -331,7 +338,7 @@ def decompose_sharded(items, decompose_batch, *, rank: int, world: int, max_batc
     dev = _payload_device(results, world, gather, group, device)
     if done:
         results.extend(MatrixResult(r.name, r.m, r.n, r.rank, r.Q_bits, r.codes.to(dev), r.Q_scale, r.L.to(dev),
-                                    r.R.to(dev), r.global_scale, r.errors, r.extra) for r in done)
+                                    r.R.to(dev), r.global_scale, r.errors, r.extra, Q_method=r.Q_method) for r in done)
     results.sort(key=lambda r: order[r.name])
     if resume_path is not None and batches:
         save_results(resume_path, results)
@@ -428,7 +435,7 @@ def _decompose_overlapped(items, decompose_batch, batches, rank, world, max_batc
                     arrs[key] = src[s0:s0 + d["nbytes"]].view(getattr(torch, d["dtype"])).view(d["shape"])
                 allres.append(MatrixResult(e["name"], e["m"], e["n"], e["rank"], e["Q_bits"], arrs["codes"],
                                            e["Q_scale"], arrs["L"], arrs["R"], e["global_scale"], e["errors"],
-                                           e.get("extra", {})))
+                                           e.get("extra", {}), Q_method=e.get("Q_method", "uniform")))
     allres.sort(key=lambda r: order[r.name])
     return allres
 
@@ -462,7 +469,8 @@ def engine_decompose_batch(quant_params, device, H_of=None):
                 name, m, n, seed = batch_items[b]
                 extra = {"n_padded": d["n_padded"]} if "n_padded" in d else {}
                 out[b] = MatrixResult(name, m, n, d["L"].shape[1], quant_params.Q_bits, d["codes"], d["Q_scale"],
-                                      d["L"], d["R"], d["global_scale"], d["errors"], extra)
+                                      d["L"], d["R"], d["global_scale"], d["errors"], extra,
+                                      Q_method=d.get("Q_method", "uniform"))
         return out
 
     def run_all(batches, on_batch_done=None):

@@ -784,6 +784,55 @@ typedef struct cq_linear_packed_backward_args {
 size_t cq_linear_packed_backward_workspace(const cq_linear_packed_backward_args* a);
 int cq_linear_packed_backward_input(const cq_linear_packed_backward_args* a, void* ws, size_t ws_bytes, void* stream);
 
+/* Codebook Q: the same layers with Q given as NF4 / NF2 level indices (the NF quantiser of
+ * quantization.py:39-91 with one block, hence one scale s per matrix) instead of uniform codes.
+ *
+ *   Q term of y:   (s / D) * sum_j x[t, j]  I[idx[i, j]]
+ *   Q term of dx:  (s / D) * sum_i dy[t, i] I[idx[i, j]]
+ *
+ *   NF4 (bits 4): I = 1000 level, D = 1000:
+ *       I = {-1334, -1000, -784, -617, -476, -347, -226, -112, 0, 112, 226, 347, 476, 617, 784, 1000}
+ *   NF2 (bits 2): I = 10000 level, D = 10000:  I = {-8165, -3333, 3333, 8165}
+ *
+ * Contract, beside everything the packed entries' hold to (z and u halves, the factor product
+ * continuing on the scaled accumulator, fixed summation order, no float atomics, row t from row t
+ * alone, graph-capturable, no allocation, the same workspace):
+ *   - s / D is one fp32 division of the two fp32 values qscale and D, as s / k is;
+ *   - the integer sum accumulates unscaled in fp32.  NF4's I are exact in fp16.  NF2's are fed as
+ *     two fp16-exact integer planes, hi in {+-8164, +-3332} and lo = +-1 (the level's sign), both
+ *     multiplied into the same fp32 accumulation, per k step hi then lo;
+ *   - the level tables are compile-time constants of the kernels: no new buffer;
+ *   - codes are the inference layout above with the level index itself as the field (no offset):
+ *     MSB-first, 4 resp. 2 indices per byte, rows 16-byte aligned, stride a multiple of 16.  The
+ *     row's tail holds index 8 (level 0: bytes 0x88) at NF4 and index 0 at NF2; NF2 has no zero
+ *     level, and the result does not depend on the tail: columns >= n contribute nothing because x
+ *     is not read there, and dx is not stored there;
+ *   - this Q differs from the reference's dequantisation level32[idx] * s by rounding only
+ *     (fp32(level), the product, s / D and I * (s / D): at most 4 * 2^-24 relative).
+ * q_format CQ_QFMT_UNIFORM: the packed entry of the same name, with the same bits.  CQ_QFMT_NF:
+ * `bits` selects NF4 (4) or NF2 (2) and qscale is the matrix scale (finite, >= 0).  L and R are
+ * fp16 or uniform codes as in the packed entries; there are no NF factors.
+ * CQ_EINVAL: an unknown q_format, plus everything the packed entries reject. */
+#define CQ_QFMT_UNIFORM 0
+#define CQ_QFMT_NF 1
+
+typedef struct cq_linear_codebook_args {
+    cq_linear_packed_args p;
+    int q_format;
+} cq_linear_codebook_args;
+
+size_t cq_linear_codebook_workspace(const cq_linear_codebook_args* a);
+int cq_linear_codebook_forward(const cq_linear_codebook_args* a, void* ws, size_t ws_bytes, void* stream);
+
+typedef struct cq_linear_codebook_backward_args {
+    cq_linear_packed_backward_args p;
+    int q_format;
+} cq_linear_codebook_backward_args;
+
+size_t cq_linear_codebook_backward_workspace(const cq_linear_codebook_backward_args* a);
+int cq_linear_codebook_backward_input(const cq_linear_codebook_backward_args* a, void* ws, size_t ws_bytes,
+                                      void* stream);
+
 /* ---------------------------------------------------------------------------------
  * Row-wise normalised Sylvester-Hadamard transform (fast Walsh-Hadamard transform), the
  * transform around a packed layer that was decomposed in the Hadamard basis (main.py:108-133,
