@@ -135,6 +135,22 @@ class LinearCodebookBackwardArgs(ctypes.Structure):
     _fields_ = [("p", LinearPackedBackwardArgs), ("q_format", c_int)]
 
 
+class LinearDequantArgs(ctypes.Structure):
+    _fields_ = [
+        ("m", c_i64), ("n", c_i64), ("r", c_i64),
+        ("bits", c_int), ("q_format", c_int),
+        ("codes", c_vp), ("code_stride", c_i64),
+        ("qscale", c_float), ("gscale", c_float),
+        ("L", c_vp), ("ldl", c_i64),
+        ("R", c_vp), ("ldr", c_i64),
+        ("l_bits", c_int), ("r_bits", c_int),
+        ("L_codes", c_vp), ("l_code_stride", c_i64),
+        ("R_codes", c_vp), ("r_code_stride", c_i64),
+        ("lscale", c_float), ("rscale", c_float),
+        ("w", c_vp), ("w_dtype", c_int), ("ldw", c_i64),
+    ]
+
+
 class HadamardArgs(ctypes.Structure):
     _fields_ = [
         ("x", c_vp), ("x_dtype", c_int), ("ldx", c_i64),
@@ -234,6 +250,7 @@ _SIGS = {
     "cq_linear_codebook_forward": (c_int, [ctypes.POINTER(LinearCodebookArgs), c_vp, c_size, c_vp]),
     "cq_linear_codebook_backward_workspace": (c_size, [ctypes.POINTER(LinearCodebookBackwardArgs)]),
     "cq_linear_codebook_backward_input": (c_int, [ctypes.POINTER(LinearCodebookBackwardArgs), c_vp, c_size, c_vp]),
+    "cq_linear_dequant": (c_int, [ctypes.POINTER(LinearDequantArgs), c_vp]),
     "cq_hadamard_rows": (c_int, [ctypes.POINTER(HadamardArgs), c_vp]),
     # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
     "cq_gemm_x3_skip": (c_int, [ctypes.POINTER(X3Args), c_vp]),
@@ -1569,6 +1586,68 @@ def linear_codebook_backward_input(dy, codes, qscale, gscale, L, R, dx, *, m, n,
     _check(lib.cq_linear_codebook_backward_input(ctypes.byref(a), _p(ws), ws.numel(), _stream(dy.device)),
            "cq_linear_codebook_backward_input")
     return dx
+
+
+def linear_dequant_args(codes, qscale, gscale, L, R, w, *, m, n, bits, q_format, r=None, L_codes=None,
+                        R_codes=None) -> LinearDequantArgs:
+    """cq_linear_dequant_args for inference-layout codes (m, row bytes) uint8, L (m, r) / R (r, n) fp16
+    or L_codes / R_codes = (uint8 inference-layout codes, scale, bits in {2, 4}) as `linear_packed_args`
+    takes them (the fp16 operand of a coded factor is None; r is needed when both are coded), and
+    w (m, n) fp32 / fp16 / bf16; L, R and w may be views with a row stride (unit column stride).  The
+    packed and codebook builders' host-side checks."""
+    need = _linear_need
+    _check_q_format(q_format, qscale)
+    if r is None:
+        need(L is not None or R is not None or (L_codes is None and R_codes is None),
+             "r is needed when both factors are coded")
+        r = L.shape[1] if L is not None else R.shape[0] if R is not None else 0
+    r = int(r)
+    if r:
+        need((L is None) != (L_codes is None), "give exactly one of L and L_codes")
+        need((R is None) != (R_codes is None), "give exactly one of R and R_codes")
+    fp16 = ((("L", L),) if r and L_codes is None else ()) + ((("R", R),) if r and R_codes is None else ())
+    for name, t in (("codes", codes), ("w", w)) + fp16:
+        need(t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1), f"{name} must be a matrix with unit column stride")
+    need(codes.dtype == torch.uint8 and codes.shape[0] == m, "codes must be uint8 with one row per output")
+    need(tuple(w.shape) == (m, n), f"w {tuple(w.shape)} does not fit {(m, n)}")
+    need(w.dtype in _ACT_DT, f"w must be fp32, fp16 or bf16, got {w.dtype}")
+    if fp16:
+        need(all(t.dtype == torch.float16 for _, t in fp16),
+             "L and R must be fp16, got " + ", ".join(str(t.dtype) for _, t in fp16))
+        need(all(tuple(t.shape) == ((m, r) if name == "L" else (r, n)) for name, t in fp16),
+             " / ".join(f"{name} {tuple(t.shape)}" for name, t in fp16) + f" do not fit {(m, r)} / {(r, n)}")
+    a = LinearDequantArgs()
+    a.m, a.n, a.r = m, n, r
+    a.bits, a.q_format = bits, int(q_format)
+    a.codes, a.code_stride = codes.data_ptr(), codes.stride(0)
+    a.qscale, a.gscale = float(qscale), float(gscale)
+    for name, t in fp16:
+        setattr(a, name, t.data_ptr())
+        setattr(a, "ld" + name.lower(), t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+    a.l_bits = a.r_bits = 16
+    for what, spec, rows in (("L", L_codes, m), ("R", R_codes, r)):
+        if spec is None or not r:
+            continue
+        t, scale, fbits = spec
+        need(t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.uint8 and t.shape[0] == rows,
+             f"{what}_codes must be a uint8 matrix with {rows} rows and unit column stride")
+        setattr(a, what.lower() + "_bits", int(fbits))
+        setattr(a, what + "_codes", t.data_ptr())
+        setattr(a, what.lower() + "_code_stride", t.stride(0))
+        setattr(a, what.lower() + "scale", float(scale))
+    a.w, a.w_dtype = w.data_ptr(), _ACT_DT[w.dtype]
+    a.ldw = w.stride(0) if m > 1 else max(w.stride(0), n)
+    return a
+
+
+def linear_dequant(codes, qscale, gscale, L, R, w, *, m, n, bits, q_format, r=None, L_codes=None, R_codes=None):
+    """w = gs (Q + L R), the dense weight of a packed layer (cq_linear_dequant); operands as
+    `linear_dequant_args`.  No workspace, no host synchronisation."""
+    _require_hip(codes, L, R, w, None if L_codes is None else L_codes[0], None if R_codes is None else R_codes[0])
+    a = linear_dequant_args(codes, qscale, gscale, L, R, w, m=m, n=n, bits=bits, q_format=q_format, r=r,
+                            L_codes=L_codes, R_codes=R_codes)
+    _check(load().cq_linear_dequant(ctypes.byref(a), _stream(w.device)), "cq_linear_dequant")
+    return w
 
 
 # ---------------------------------------------------------------------------- Hadamard transform

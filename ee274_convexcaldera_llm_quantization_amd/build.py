@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libcaldera_hip.so")
 SOURCES = ["cq_quant.hip", "cq_gemm.hip", "cq_small.hip", "cq_x3.hip", "cq_qtile.hip", "cq_split.hip", "cq_qupdate.hip",
            "cq_codebook.hip", "cq_calib.hip", "cq_bjacobi.hip", "cq_sgram.hip", "cq_linear.hip",
-           "cq_linear_bwd.hip", "cq_hadamard.hip"]
+           "cq_linear_bwd.hip", "cq_linear_dequant.hip", "cq_hadamard.hip"]
 # per-source extra flags: the row-panel Q update keeps its per-element epilogue in scalar fp32
 # (packed fp32 VALU beside MFMAs costs more issue cycles than the scalar pair it replaces)
 EXTRA = {"cq_qupdate.hip": ["-fno-slp-vectorize"]}
@@ -33,7 +33,7 @@ STAMP = OUT + ".srchash"  # content hash of the sources the .so was built from
 
 
 def _deps():
-    return ([os.path.join(CSRC, s) for s in SOURCES + ["cq_common.h", "cq_x3.h", "cq_x3_tile.h", "cq_nf.h"]]
+    return ([os.path.join(CSRC, s) for s in SOURCES + ["cq_common.h", "cq_x3.h", "cq_x3_tile.h", "cq_nf.h", "cq_linear_tile.h"]]
             + [os.path.join(HERE, "..", "include", "caldera_hip.h")])
 
 

@@ -23,6 +23,11 @@ Q may also be an NF4 / NF2 codebook (`q_format` = Q_FORMAT_NF): `codes` then hol
 indices in the same layout, `qscale` the matrix scale, and the layer runs through
 cq_linear_codebook_forward / cq_linear_codebook_backward_input with
 Q = I[idx] (s / D), I the integer levels (include/caldera_hip.h).  Factors stay fp16 or uniform.
+
+`materialize()` gives the dense weight gs (Q + L R) from any of these forms by one kernel
+(cq_linear_dequant, csrc/cq_linear_dequant.hip).  With `dense_prefill_tokens` set a layer hands long
+prefill (and the input gradient at that length) to the dense fp16 GEMM on a weight materialised
+into one scratch buffer that all layers of a stream share; the default, None, changes nothing.
 """
 from __future__ import annotations
 
@@ -120,10 +125,71 @@ def unpack_index_bytes(b: torch.Tensor, bits: int) -> torch.Tensor:
     return torch.stack(parts, dim=-1).reshape(*b.shape[:-1], b.shape[-1] * per)
 
 
+def check_dense_prefill_tokens(tokens):
+    """`tokens` as a `dense_prefill_tokens` value: None, or an int above the decode branch's token
+    count (the dense path replaces the prefill kernels only)."""
+    if tokens is None:
+        return None
+    if isinstance(tokens, bool) or not isinstance(tokens, int) or tokens <= K.LINEAR_DECODE_MAX_TOKENS:
+        raise ValueError(f"CalderaLinear: dense_prefill_tokens must be None or an int > "
+                         f"{K.LINEAR_DECODE_MAX_TOKENS} (the decode kernels' token count), got {tokens!r}")
+    return tokens
+
+
+def _dequant(lin, w: torch.Tensor, L16=None, R16=None):
+    """cq_linear_dequant of the layer into w (out_features, in_features) fp16 / bf16 / fp32.
+    L16 / R16: the fp16 factors to use instead of the layer's buffers (masters rounded to fp16)."""
+    L = lin.L if L16 is None else L16
+    R = lin.R if R16 is None else R16
+    coded_l, coded_r = lin.L_codes is not None, lin.R_codes is not None
+    return K.linear_dequant(
+        lin.codes, lin.qscale, lin.gscale, L if lin.rank and not coded_l else None,
+        R if lin.rank and not coded_r else None, w, m=lin.out_features, n=lin.in_features, bits=lin.bits,
+        q_format=lin.q_format, r=lin.rank,
+        L_codes=(lin.L_codes, lin.lscale, lin.L_bits) if lin.rank and coded_l else None,
+        R_codes=(lin.R_codes, lin.rscale, lin.R_bits) if lin.rank and coded_r else None)
+
+
+def _dense_scratch(lin, L16, R16):
+    """The layer's fp16 weight, freshly materialised into the stream's shared scratch buffer (one
+    per stream, as large as the largest layer that used it; the next dense-path call on the stream
+    overwrites it, which stream order makes safe)."""
+    from . import scratch
+    m, n = lin.out_features, lin.in_features
+    W16 = scratch.get_flat("linear.dense_weight", m * n, torch.float16, lin.codes.device).view(m, n)
+    return _dequant(lin, W16, L16, R16)
+
+
+def _mm_into(a16, b16, out):
+    """out = a16 @ b16 with fp16 operands and the GEMM's fp32 accumulation: rounded once, to out's
+    dtype (fp16: the GEMM's own output rounding; fp32: none)."""
+    if out.dtype == torch.float16:
+        return torch.mm(a16, b16, out=out)
+    return out.copy_(torch.mm(a16, b16, out_dtype=torch.float32))
+
+
+def _use_dense(lin, T: int) -> bool:
+    return lin.dense_prefill_tokens is not None and T >= lin.dense_prefill_tokens
+
+
 def _launch_packed(lin, x2: torch.Tensor, y: torch.Tensor, L16=None, R16=None):
     """The entry `CalderaLinear.forward` takes for this layer, on given fp16 x2 (T, in_features)
     and y (T, out_features): cq_linear_packed_forward with a coded factor, else cq_linear_forward.
-    L16 / R16: the fp16 factors to use instead of the layer's buffers (masters rounded to fp16)."""
+    L16 / R16: the fp16 factors to use instead of the layer's buffers (masters rounded to fp16).
+
+    Dense path (`lin.dense_prefill_tokens` set and T >= it): W16 = f16(gs (Q + L R)) from
+    cq_linear_dequant (the fp32 weight of its contract, rounded once to fp16) into the shared
+    scratch buffer, then the dense GEMM x2 W16^T with fp32 accumulation.  Without a bias an fp16 y is
+    that fp32 sum rounded once; otherwise the sum stays fp32, the bias is added in fp32 and the
+    result is rounded once when y is fp16.  So against the packed kernels the dense path adds one
+    fp16 rounding of each weight and nothing else."""
+    if _use_dense(lin, x2.shape[0]):
+        W16 = _dense_scratch(lin, L16, R16)
+        if lin.bias is None:
+            return _mm_into(x2, W16.t(), y)
+        y32 = torch.mm(x2, W16.t(), out_dtype=torch.float32)
+        y32 += lin.bias
+        return y.copy_(y32)
     L = lin.L if L16 is None else L16
     R = lin.R if R16 is None else R16
     if lin.q_format != Q_FORMAT_UNIFORM:
@@ -154,14 +220,20 @@ def _packed_backward(lin, dy16, x2, L16, R16, needs, dx_dtype, factor_dtypes):
     """(dx2, dL, dR) of one packed layer for dy16 (T, m) fp16 and the saved fp16 x2 (T, n): dx2 (T, n)
     in dx_dtype (fp32 | fp16) from the packed codes -- cq_linear_packed_backward_input with a coded
     factor, else cq_linear_backward_input -- and, for trainable (hence fp16) factors,
-    dL = gs dy^T (x R^T) and dR = gs (dy L)^T x."""
+    dL = gs dy^T (x R^T) and dR = gs (dy L)^T x.  With `lin.dense_prefill_tokens` set and T >= it,
+    dx2 = dy16 W16 by the dense GEMM on a fresh materialisation (`_launch_packed`'s rounding
+    sequence: each weight to fp16 once, fp32 accumulation, one rounding to dx_dtype)."""
     m, n, r, gs = lin.out_features, lin.in_features, lin.rank, lin.gscale
     need_x, need_L, need_R = needs
     T = dy16.shape[0]
     dx2 = dL = dR = u = None
     if need_x:
         dx2 = torch.empty((T, n), dtype=dx_dtype, device=dy16.device)
-        if lin.q_format != Q_FORMAT_UNIFORM:
+        if _use_dense(lin, T):
+            # the dense path of `_launch_packed`, mirrored: dx = dy16 W16 from a fresh materialisation
+            # (the scratch buffer does not outlive the forward); u is left to the torch product below
+            _mm_into(dy16, _dense_scratch(lin, L16, R16), dx2)
+        elif lin.q_format != Q_FORMAT_UNIFORM:
             if r and need_R and lin.R_codes is None:
                 u = torch.empty((T, r), dtype=torch.float32, device=dy16.device)
             K.linear_codebook_backward_input(
@@ -537,6 +609,34 @@ class CalderaLinear(torch.nn.Module):
         L, R = self.factors()
         return self.gscale * (c * sk + L @ R)
 
+    def materialize(self, dtype=torch.float16, out=None) -> torch.Tensor:
+        """gs (Q + L R) as a dense (out_features, in_features) device tensor from the packed form by
+        cq_linear_dequant (csrc/cq_linear_dequant.hip): the fp32 weight of that entry's contract,
+        rounded once to dtype (fp16, bf16 or fp32).  out: the tensor to fill instead of a new one (its
+        dtype counts; may be a view with a row stride and unit column stride).  While the factors
+        are trainable the masters rounded to fp16 are used, as forward does.  There is no CPU path."""
+        if not self.codes.is_cuda or (out is not None and not out.is_cuda):
+            raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
+        if out is None:
+            if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+                raise ValueError(f"CalderaLinear.materialize: dtype {dtype} not fp16, bf16 or fp32")
+            out = torch.empty((self.out_features, self.in_features), dtype=dtype, device=self.codes.device)
+        L16, R16 = _fp16_factors(self.L, self.R) if self.factors_trainable else (None, None)
+        return _dequant(self, out, L16, R16)
+
+    @property
+    def dense_prefill_tokens(self):
+        """None (the default: every forward and backward is the packed kernels'), or the token count T
+        from which the layer materialises its fp16 weight into one scratch buffer shared by all
+        layers of the stream and runs the dense GEMM instead of the prefill kernels, forward and
+        input gradient alike (`_launch_packed`).  An int above `_lib.LINEAR_DECODE_MAX_TOKENS`.  A
+        plain attribute: not part of `state_dict()` nor of the extra state."""
+        return self.__dict__.get("_dense_prefill_tokens")
+
+    @dense_prefill_tokens.setter
+    def dense_prefill_tokens(self, tokens):
+        self.__dict__["_dense_prefill_tokens"] = check_dense_prefill_tokens(tokens)
+
     # ------------------------------------------------------------------ fine-tuning
     @property
     def factors_trainable(self) -> bool:
@@ -699,6 +799,42 @@ class HadamardCalderaLinear(torch.nn.Module):
         pr, pc = self.padded_shape
         H1, H2 = normalized_hadamard(pr, Wt.device), normalized_hadamard(pc, Wt.device)
         return (H1 @ Wt @ H2)[:self.out_features, :self.in_features].contiguous()
+
+    def materialize(self, dtype=torch.float16, out=None) -> torch.Tensor:
+        """(H1 W~ H2)[:out_features, :in_features] as a dense device tensor by kernels alone: the inner
+        layer's `materialize` in fp32, cq_hadamard_rows on its rows (W~ H2, cut to in_features
+        columns), then on the rows of the transposed result (H1 that, cut to out_features), which is
+        rounded once to dtype (fp16, bf16 or fp32).  Not a hot path: two fp32 temporaries of the
+        padded size.  out: as `CalderaLinear.materialize`."""
+        if out is not None and not out.is_cuda:
+            raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
+        if out is not None:
+            dtype = out.dtype
+        if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            raise ValueError(f"HadamardCalderaLinear.materialize: dtype {dtype} not fp16, bf16 or fp32")
+        pr, pc = self.padded_shape
+        m, n = self.out_features, self.in_features
+        Wt = self.inner.materialize(torch.float32)
+        A = torch.empty((pr, n), dtype=torch.float32, device=Wt.device)
+        K.hadamard_rows(Wt, A, n_in=pc, n_out=n, P=pc)
+        At = A.t().contiguous()
+        Wo = torch.empty((n, m), dtype=dtype, device=Wt.device)
+        K.hadamard_rows(At, Wo, n_in=pr, n_out=m, P=pr)
+        if out is None:
+            return Wo.t().contiguous()
+        if tuple(out.shape) != (m, n):
+            raise ValueError(f"HadamardCalderaLinear.materialize: out {tuple(out.shape)} does not fit {(m, n)}")
+        return out.copy_(Wo.t())
+
+    @property
+    def dense_prefill_tokens(self):
+        """`inner.dense_prefill_tokens`: the inner layer's launch takes the dense path, the
+        transforms around it stay as they are."""
+        return self.inner.dense_prefill_tokens
+
+    @dense_prefill_tokens.setter
+    def dense_prefill_tokens(self, tokens):
+        self.inner.dense_prefill_tokens = tokens
 
     # ------------------------------------------------------------------ fine-tuning
     @property

@@ -415,3 +415,51 @@ def finish_factor_finetuning(model: torch.nn.Module) -> torch.nn.Module:
         if isinstance(mod, CalderaLinear):
             mod.freeze_factors()
     return model
+
+
+def _packed_layers(model: torch.nn.Module) -> list:
+    """[(name, module)] of every packed layer of `model`: each `linear.HadamardCalderaLinear` and each
+    `linear.CalderaLinear` that is not the inner layer of one."""
+    from .linear import CalderaLinear, HadamardCalderaLinear
+    inner = {id(mod.inner) for mod in model.modules() if isinstance(mod, HadamardCalderaLinear)}
+    return [(name, mod) for name, mod in model.named_modules()
+            if isinstance(mod, HadamardCalderaLinear) or (isinstance(mod, CalderaLinear) and id(mod) not in inner)]
+
+
+def set_dense_prefill(model: torch.nn.Module, tokens) -> list:
+    """Set (`tokens`: an int above `_lib.LINEAR_DECODE_MAX_TOKENS`) or clear (None) the token count from
+    which every packed layer materialises its fp16 weight into the shared scratch buffer and runs the
+    dense GEMM (`CalderaLinear.dense_prefill_tokens`; a Hadamard layer's threshold is its inner
+    layer's).  Returns the layers' names.  ValueError before any layer is changed."""
+    from .linear import check_dense_prefill_tokens
+    tokens = check_dense_prefill_tokens(tokens)
+    layers = _packed_layers(model)
+    for _, mod in layers:
+        mod.dense_prefill_tokens = tokens
+    return [name for name, _ in layers]
+
+
+def unpack_packed_layers(model: torch.nn.Module, dtype=torch.float16) -> list:
+    """Replace every `linear.CalderaLinear` / `linear.HadamardCalderaLinear` by an `nn.Linear` whose
+    weight is the layer's `materialize(dtype)` (cq_linear_dequant: fp16, bf16 or fp32) and whose bias
+    is the layer's, cast to dtype: the model as plain dense layers, e.g. for export.  Returns the
+    replaced names.  ValueError, before anything is changed, for layers whose factors are trainable:
+    call `finish_factor_finetuning` first."""
+    layers = _packed_layers(model)
+    bad = [name or "<model>" for name, mod in layers if mod.factors_trainable]
+    if bad:
+        raise ValueError("unpack_packed_layers: trainable factors (call finish_factor_finetuning first): "
+                         + ", ".join(bad))
+    for name, mod in layers:
+        if not name:
+            raise ValueError("unpack_packed_layers: the model itself is a packed layer (nothing to replace it in)")
+    for name, mod in layers:
+        W = mod.materialize(dtype)
+        lin = torch.nn.Linear(mod.in_features, mod.out_features, bias=mod.bias is not None, device=W.device,
+                              dtype=dtype)
+        with torch.no_grad():
+            lin.weight.copy_(W)
+            if mod.bias is not None:
+                lin.bias.copy_(mod.bias)
+        _set_module(model, name, lin)
+    return [name for name, _ in layers]

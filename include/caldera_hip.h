@@ -833,6 +833,61 @@ size_t cq_linear_codebook_backward_workspace(const cq_linear_codebook_backward_a
 int cq_linear_codebook_backward_input(const cq_linear_codebook_backward_args* a, void* ws, size_t ws_bytes,
                                       void* stream);
 
+/* Materialise: the dense weight of a packed layer, for callers that hand long prefill to a dense
+ * GEMM from one shared transient buffer, or that want a plain dense layer back.
+ *
+ *   W[i, j] = gs * (qs * V(code[i, j]) + fscale * sum_q lam[i, q] rho[q, j])        i < m, j < n
+ *
+ * V and qs are the Q term of the entries above: q_format CQ_QFMT_UNIFORM V = u - k and qs = s / k;
+ * CQ_QFMT_NF V = I[idx] (the integer levels above) and qs = s / D; each one fp32 division of qscale.
+ * lam is the L codes (l_bits 2 | 4) or the fp16 L (l_bits 16), rho the R codes or the fp16 R
+ * (r_bits); fscale is cq_linear_packed_forward's zscale, the fp32 product of the coded factors'
+ * scale / k, and 1.0f when neither factor is coded.  Every operand field means what it means in
+ * cq_linear_packed_args (inference layout, L codes as m rows of r codes, R codes as r rows of n
+ * codes, a coded factor's fp16 pointer ignored and the reverse).
+ *
+ * Contract:
+ *   - the factor product accumulates in fp32 over ascending q on v_mfma_f32_16x16x32_f16 (chunks
+ *     of 32 q; operands past r are zeros).  For coded factors it is the unscaled integer sum,
+ *     exact up to r = CQ_LINEAR_MAX_RANK (49 * 1024 < 2^24);
+ *   - the Q term is not an MFMA operand: V is formed exactly in fp32 (NF2's 8165 as 8164 + 1);
+ *   - fscale, qs and gs are each applied once per output, in this sequence of fp32 operations:
+ *         f = fscale * sum            (skipped when neither factor is coded: f = sum)
+ *         t = fma(qs, V, f)           (one rounding)
+ *         w = gs * t
+ *     three roundings after the sum, two with fp16 factors;
+ *   - w (m x n, row stride ldw >= n elements, CQ_F32 | CQ_F16 | CQ_BF16) receives the fp32 w,
+ *     for the narrow types rounded once (to nearest even).  It is written only at i < m, j < n:
+ *     whatever lies beyond inside ldw is not touched;
+ *   - a fixed order and no float atomics: the same input gives the same bits, and an output
+ *     depends on its own code, its L row and its R column alone, not on m, n, the strides or the
+ *     output type's neighbours;
+ *   - stream-ordered, no allocation, no host synchronisation (graph-capturable), no workspace;
+ *   - nothing is read past the operands' logical extent: codes and L not at rows >= m, R not at
+ *     rows >= r, fp16 L not at q >= r, fp16 R not at j >= n.  The result does not depend on the
+ *     code rows' tails, on the L codes' pad columns (q >= r: they meet R's zero rows) or on bytes
+ *     after the last R-code row;
+ *   - r = 0: codes only (L, R and the factor codes may be NULL).
+ * CQ_EINVAL, before any HIP call: everything the packed and codebook entries reject for these
+ * fields (bits, q_format, an NF scale that is not finite and >= 0, r > CQ_LINEAR_MAX_RANK, factor
+ * bits, code pointers and strides, factor scales, misaligned or NULL pointers, ldl < r, ldr < n), an
+ * unknown w_dtype, ldw < n, a negative shape.  m == 0 or n == 0 returns 0 without a launch. */
+typedef struct cq_linear_dequant_args {
+    int64_t m, n, r;
+    int bits, q_format;
+    const uint8_t* codes; int64_t code_stride;
+    float qscale, gscale;
+    const uint16_t* L; int64_t ldl;
+    const uint16_t* R; int64_t ldr;
+    int l_bits, r_bits;
+    const uint8_t* L_codes; int64_t l_code_stride;
+    const uint8_t* R_codes; int64_t r_code_stride;
+    float lscale, rscale;
+    void* w; int w_dtype; int64_t ldw;
+} cq_linear_dequant_args;
+
+int cq_linear_dequant(const cq_linear_dequant_args* a, void* stream);
+
 /* ---------------------------------------------------------------------------------
  * Row-wise normalised Sylvester-Hadamard transform (fast Walsh-Hadamard transform), the
  * transform around a packed layer that was decomposed in the Hadamard basis (main.py:108-133,
