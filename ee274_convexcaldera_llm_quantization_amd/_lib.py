@@ -135,6 +135,11 @@ class LinearCodebookBackwardArgs(ctypes.Structure):
     _fields_ = [("p", LinearPackedBackwardArgs), ("q_format", c_int)]
 
 
+class LinearGroupArgs(ctypes.Structure):
+    """cq_linear_group_args: `members` points at a host array of `count` cq_linear_packed_args."""
+    _fields_ = [("count", ctypes.c_int32), ("q_format", ctypes.c_int32), ("members", ctypes.POINTER(LinearPackedArgs))]
+
+
 class LinearDequantArgs(ctypes.Structure):
     _fields_ = [
         ("m", c_i64), ("n", c_i64), ("r", c_i64),
@@ -250,6 +255,8 @@ _SIGS = {
     "cq_linear_codebook_forward": (c_int, [ctypes.POINTER(LinearCodebookArgs), c_vp, c_size, c_vp]),
     "cq_linear_codebook_backward_workspace": (c_size, [ctypes.POINTER(LinearCodebookBackwardArgs)]),
     "cq_linear_codebook_backward_input": (c_int, [ctypes.POINTER(LinearCodebookBackwardArgs), c_vp, c_size, c_vp]),
+    "cq_linear_group_workspace": (c_size, [ctypes.POINTER(LinearGroupArgs)]),
+    "cq_linear_group_forward": (c_int, [ctypes.POINTER(LinearGroupArgs), c_vp, c_size, c_vp]),
     "cq_linear_dequant": (c_int, [ctypes.POINTER(LinearDequantArgs), c_vp]),
     "cq_hadamard_rows": (c_int, [ctypes.POINTER(HadamardArgs), c_vp]),
     # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
@@ -1434,6 +1441,66 @@ def linear_codebook_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bi
     _check(lib.cq_linear_codebook_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)),
            "cq_linear_codebook_forward")
     return y
+
+
+LINEAR_GROUP_MAX = 8  # include/caldera_hip.h CQ_LINEAR_GROUP_MAX
+
+
+def linear_group_args(x, members, ys, q_format) -> LinearGroupArgs:
+    """cq_linear_group_args of layers that share the activation x (T, n) fp16.  members: one dict per
+    layer with `linear_packed_args`' operands after x and before y as keys (codes, qscale, gscale, L,
+    R, bias, m, n, bits and optionally r, L_codes, R_codes); ys: the layers' outputs (T, m_i), all fp32
+    or all fp16.  Each member passes `linear_packed_args`' host-side checks and `q_format`'s; the
+    members must share n, bits and the output dtype, and those with r > 0 the factor formats.  The
+    struct keeps the member array alive."""
+    need = _linear_need
+    members, ys = list(members), list(ys)
+    need(1 <= len(members) <= LINEAR_GROUP_MAX, f"group: count {len(members)} not in 1 .. {LINEAR_GROUP_MAX}")
+    need(len(ys) == len(members), f"group: {len(ys)} outputs for {len(members)} members")
+    need(q_format in (QFMT_UNIFORM, QFMT_NF), f"group: unknown q_format {q_format!r}")
+    arr = (LinearPackedArgs * len(members))()
+    ranked = None
+    for i, (mem, y) in enumerate(zip(members, ys)):
+        try:
+            _check_q_format(q_format, mem["qscale"])
+            a = linear_packed_args(x, mem["codes"], mem["qscale"], mem["gscale"], mem.get("L"), mem.get("R"),
+                                   mem.get("bias"), y, m=mem["m"], n=mem["n"], bits=mem["bits"], r=mem.get("r"),
+                                   L_codes=mem.get("L_codes"), R_codes=mem.get("R_codes"), into=arr[i])
+        except ValueError as e:
+            raise ValueError(f"cq_linear: group member {i}: {str(e).removeprefix('cq_linear: ')}") from None
+        for field in ("n", "bits", "y_dtype"):
+            need(getattr(a, field) == getattr(arr[0], field), f"group member {i}: {field} {getattr(a, field)} differs "
+                 f"from member 0's {getattr(arr[0], field)}")
+        if a.r > 0:
+            if ranked is None:
+                ranked = i
+            for field in ("l_bits", "r_bits"):
+                need(getattr(a, field) == getattr(arr[ranked], field), f"group member {i}: {field} "
+                     f"{getattr(a, field)} differs from member {ranked}'s {getattr(arr[ranked], field)}")
+    g = LinearGroupArgs()
+    g.count, g.q_format = len(members), int(q_format)
+    g.members = ctypes.cast(arr, ctypes.POINTER(LinearPackedArgs))
+    g._members = arr
+    return g
+
+
+def linear_group_forward(x, members, ys, q_format, ws=None):
+    """The layers `members` (see `linear_group_args`) on the one activation x in one z launch and one
+    code + L launch (cq_linear_group_forward): ys[i] receives, bit for bit, what member i's own entry
+    writes.  ws as `linear_forward`.  No host synchronisation."""
+    members = list(members)
+    for mem in members:
+        _require_hip(x, mem["codes"], mem.get("L"), mem.get("R"), mem.get("bias"),
+                     None if mem.get("L_codes") is None else mem["L_codes"][0],
+                     None if mem.get("R_codes") is None else mem["R_codes"][0])
+    _require_hip(*ys)
+    g = linear_group_args(x, members, ys, q_format)
+    lib = load()
+    if ws is None:
+        ws = workspace(lib.cq_linear_group_workspace(ctypes.byref(g)), x.device)
+    _check(lib.cq_linear_group_forward(ctypes.byref(g), _p(ws), ws.numel(), _stream(x.device)),
+           "cq_linear_group_forward")
+    return ys
 
 
 def linear_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, ws=None):

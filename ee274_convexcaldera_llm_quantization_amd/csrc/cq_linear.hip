@@ -42,7 +42,9 @@
 // signed), the lo plane (+-1, the level's sign) is made from it in registers, and both planes are
 // multiplied into the same accumulator, hi first.  Everything around the expansion is unchanged.
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "cq_common.h"
 #include "cq_nf.h"
@@ -79,6 +81,16 @@ struct LinP {
     const uint8_t* lc; int64_t lcstride;          // packed L codes (m rows of r codes): bytes per row
     float zscale;                                 // on the complete z sum, before it is split (1 without factor codes)
 };
+
+// the grouped kernel's argument, see linear_kernel
+struct GroupP {
+    LinP m[CQ_LINEAR_GROUP_MAX];
+    int32_t first[CQ_LINEAR_GROUP_MAX];
+};
+__device__ __forceinline__ const LinP& member(const LinP& p, int) { return p; }
+__device__ __forceinline__ const LinP& member(const GroupP& g, int off) {
+    return *reinterpret_cast<const LinP*>(reinterpret_cast<const char*>(g.m) + off);
+}
 
 // elements k .. k + 7 of a row, zero at and beyond lim (lim = 0: nothing is read)
 __device__ __forceinline__ h8 ld8(const _Float16* row, int64_t k, int64_t lim, bool al) {
@@ -138,9 +150,36 @@ __device__ __forceinline__ h8 expand(const u4 q, int jj) {
 // workgroup per CU where the uniform tile has two; asked for two waves per SIMD it fits 220 VGPRs
 // without scratch.  Every other instantiation states a minimum of one wave per SIMD, which
 // is what its launch bounds imply already: their code is the same with and without the attribute.
-template <int WT, int QF, int LB, bool ZP, int TT, int RG, int NW, bool KSPLIT>
+//
+// ARG: the kernel's argument.  LinP: one layer, the workgroup's place in the grid is its place in the
+// layer.  GroupP (cq_linear_group_forward): up to CQ_LINEAR_GROUP_MAX layers that share x, T, n and
+// the template parameters in one grid whose x extent is the members' own x extents laid end to end,
+// so a workgroup never spans two members; first[i] is member i's first blockIdx.x (INT32_MAX past
+// the last member).  A workgroup finds its member by comparing blockIdx.x with that table -- kernel
+// arguments and blockIdx only: scalar loads, compares and selects -- and then runs on the member's
+// parameters at its own place (bx) in the member's grid: the same work in the same order as alone.
+// The body is one and the same text for both; with ARG = LinP, p is the kernel argument itself.
+// The grouped prefill code kernels ask for two waves per SIMD as well: their fields are loaded from a
+// computed address where they are used, and left alone the 2-bit tile came out at 146 VGPRs + 120
+// AGPRs, one wave; asked, all of them fit 214 .. 222 VGPRs without scratch.
+template <int WT, int QF, int LB, bool ZP, int TT, int RG, int NW, bool KSPLIT, typename ARG>
 __global__ __launch_bounds__(NW * 64)
-__attribute__((amdgpu_waves_per_eu(QF == CQ_QFMT_NF && WT == 4 && TT > 1 ? 2 : 1))) void linear_kernel(const LinP p) {
+__attribute__((amdgpu_waves_per_eu(
+    (QF == CQ_QFMT_NF && WT == 4 && TT > 1) || (std::is_same_v<ARG, GroupP> && !ZP && TT > 1) ? 2 : 1))) void
+linear_kernel(const ARG arg) {
+    unsigned bx = blockIdx.x;
+    int off = 0;  // the member's byte offset in arg.m
+    if constexpr (std::is_same_v<ARG, GroupP>) {
+        int32_t base = 0;
+#pragma unroll
+        for (int i = 1; i < CQ_LINEAR_GROUP_MAX; ++i) {
+            const bool past = (int32_t)blockIdx.x >= arg.first[i];
+            off = past ? i * (int)sizeof(LinP) : off;  // the table ascends: the last member at or before blockIdx.x
+            base = past ? arg.first[i] : base;
+        }
+        bx -= (unsigned)base;
+    }
+    const LinP& p = member(arg, off);
     constexpr bool CODES = WT != 16;
     constexpr bool NF = QF == CQ_QFMT_NF;
     static_assert(!NF || (CODES && !ZP), "only the layer's own codes are level indices");
@@ -162,7 +201,7 @@ __attribute__((amdgpu_waves_per_eu(QF == CQ_QFMT_NF && WT == 4 && TT > 1 ? 2 : 1
     struct WR { u4 v[WV]; };
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 15, g = lane >> 4;
-    const int64_t row0 = (KSPLIT ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * NW + wave) * (16 * RG);
+    const int64_t row0 = (KSPLIT ? (int64_t)bx : (int64_t)bx * NW + wave) * (16 * RG);
     // blockIdx.y: the token tile; under the K split (one tile) the workgroup's share of K
     const int64_t tok0 = KSPLIT ? 0 : (int64_t)blockIdx.y * (TT * 16);
     const int64_t rows_out = ZP ? p.r32 : p.rows;
@@ -465,17 +504,26 @@ inline bool al16(const void* ptr, int64_t ld_elems) {
     return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld_elems % 8 == 0;
 }
 
+constexpr int kPrefillWaves = 4;   // waves per prefill workgroup (codes; the z product has one)
+
+// the x extent of a layer's own grid: workgroups over its weight rows
+template <bool ZP>
+inline int64_t x_extent(const LinP& p) {
+    const int64_t groups = ceil_div(ZP ? p.r32 : p.rows, 16);
+    return p.T <= kDecodeMax ? groups : ceil_div(groups, ZP ? 1 : kPrefillWaves * kPrefillGroups);
+}
+
 template <int WT, int QF, int LB, bool ZP>
 void launch(const LinP& p, hipStream_t s) {
-    const int64_t groups = ceil_div(ZP ? p.r32 : p.rows, 16);
     if (p.T <= kDecodeMax) {
         constexpr int NW = ZP ? kDecodeWavesZ : kDecodeWaves;
-        const dim3 grid((unsigned)groups, ZP ? kDecodeSplitZ : 1);
-        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, 1, 1, NW, true>), grid, dim3(NW * 64), 0, s, p);
+        const dim3 grid((unsigned)x_extent<ZP>(p), ZP ? kDecodeSplitZ : 1);
+        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, 1, 1, NW, true, LinP>), grid, dim3(NW * 64), 0, s, p);
     } else {
-        constexpr int NW = ZP ? 1 : 4, RG = ZP ? 1 : kPrefillGroups;
-        const dim3 grid((unsigned)ceil_div(groups, NW * RG), (unsigned)ceil_div(p.T, kPrefillTiles * 16));
-        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, kPrefillTiles, RG, NW, false>), grid, dim3(NW * 64), 0, s, p);
+        constexpr int NW = ZP ? 1 : kPrefillWaves, RG = ZP ? 1 : kPrefillGroups;
+        const dim3 grid((unsigned)x_extent<ZP>(p), (unsigned)ceil_div(p.T, kPrefillTiles * 16));
+        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, kPrefillTiles, RG, NW, false, LinP>), grid, dim3(NW * 64), 0, s,
+                           p);
     }
 }
 
@@ -484,6 +532,39 @@ void launch_layer(const LinP& p, int l_bits, hipStream_t s) {
     if (l_bits == 2) launch<WT, QF, 2, false>(p, s);
     else if (l_bits == 4) launch<WT, QF, 4, false>(p, s);
     else launch<WT, QF, 16, false>(p, s);
+}
+
+// `count` layers (1 .. CQ_LINEAR_GROUP_MAX, the same T and template parameters, each with a nonempty
+// grid of its own) in one grid: the members' x extents end to end, the y extent they share
+template <int WT, int QF, int LB, bool ZP>
+void launch_group(const LinP* ps, int count, hipStream_t s) {
+    GroupP g{};
+    int64_t total = 0;
+    for (int i = 0; i < CQ_LINEAR_GROUP_MAX; ++i) {
+        g.first[i] = i < count ? (int32_t)total : INT32_MAX;
+        if (i < count) {
+            g.m[i] = ps[i];
+            total += x_extent<ZP>(ps[i]);
+        }
+    }
+    const int64_t T = ps[0].T;
+    if (T <= kDecodeMax) {
+        constexpr int NW = ZP ? kDecodeWavesZ : kDecodeWaves;
+        const dim3 grid((unsigned)total, ZP ? kDecodeSplitZ : 1);
+        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, 1, 1, NW, true, GroupP>), grid, dim3(NW * 64), 0, s, g);
+    } else {
+        constexpr int NW = ZP ? 1 : kPrefillWaves, RG = ZP ? 1 : kPrefillGroups;
+        const dim3 grid((unsigned)total, (unsigned)ceil_div(T, kPrefillTiles * 16));
+        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, kPrefillTiles, RG, NW, false, GroupP>), grid, dim3(NW * 64), 0,
+                           s, g);
+    }
+}
+
+template <int WT, int QF>
+void launch_group_layers(const LinP* ps, int count, int l_bits, hipStream_t s) {
+    if (l_bits == 2) launch_group<WT, QF, 2, false>(ps, count, s);
+    else if (l_bits == 4) launch_group<WT, QF, 4, false>(ps, count, s);
+    else launch_group<WT, QF, 16, false>(ps, count, s);
 }
 
 inline bool coded(int bits) { return bits == 2 || bits == 4; }
@@ -556,22 +637,21 @@ cq_linear_packed_args with_fp16_factors(const cq_linear_args* a) {
     return b;
 }
 
-int forward(const cq_linear_packed_args* a, int q_format, void* ws, size_t ws_bytes, void* stream, const char* who) {
-    if (int st = validate(a)) return st;
-    CQ_REQUIRE(q_format == CQ_QFMT_UNIFORM || q_format == CQ_QFMT_NF, "%s: unknown q_format %d", who, q_format);
-    const bool nf = q_format == CQ_QFMT_NF;
-    CQ_REQUIRE(!nf || (std::isfinite(a->qscale) && a->qscale >= 0.f), "%s: NF scale %g is not finite and >= 0", who,
-               (double)a->qscale);
-    if (a->tokens == 0) return CQ_OK;
-    const size_t need = workspace_bytes(a->tokens, a->r);
+int check_workspace(size_t need, const void* ws, size_t ws_bytes, const char* who) {
     if (need) {
         CQ_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
                    "%s: workspace must be 16-byte aligned", who);
         if (ws_bytes < need) return set_error(CQ_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
     }
+    return CQ_OK;
+}
+
+// The kernels' parameters of one validated layer on its own workspace ws: z, the z product (used
+// for r > 0 only), and p, codes + L + epilogue.  Shared by the single-layer and the grouped entry,
+// so a grouped member's parameters are the ones it runs with alone.
+void layer_params(const cq_linear_packed_args* a, bool nf, void* ws, LinP& z, LinP& p) {
     const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
-    hipStream_t s = as_stream(stream);
-    LinP p{};
+    p = LinP{};
     p.x = reinterpret_cast<const _Float16*>(a->x);
     p.ldx = a->ldx;
     p.x_al = al16(a->x, a->ldx);
@@ -585,8 +665,8 @@ int forward(const cq_linear_packed_args* a, int q_format, void* ws, size_t ws_by
     p.zscale = 1.0f;
     if (lcoded) p.zscale = a->lscale / kmax(a->l_bits);
     if (rcoded) p.zscale = lcoded ? p.zscale * (a->rscale / kmax(a->r_bits)) : a->rscale / kmax(a->r_bits);
-    if (a->r > 0) {  // z = x R^T as split halves
-        LinP z = p;
+    z = p;  // z = x R^T as split halves
+    if (a->r > 0) {
         z.rows = a->r;
         z.ozp = reinterpret_cast<float*>(ws);
         z.oh = zh;
@@ -594,17 +674,11 @@ int forward(const cq_linear_packed_args* a, int q_format, void* ws, size_t ws_by
         if (rcoded) {
             z.w = a->R_codes;
             z.wstride = a->r_code_stride;
-            if (a->r_bits == 2) launch<2, CQ_QFMT_UNIFORM, 16, true>(z, s);
-            else launch<4, CQ_QFMT_UNIFORM, 16, true>(z, s);
         } else {
             z.w = reinterpret_cast<const uint8_t*>(a->R);
             z.wstride = a->ldr;
             z.w_al = al16(a->R, a->ldr);
-            launch<16, CQ_QFMT_UNIFORM, 16, true>(z, s);
         }
-        char what[64];
-        snprintf(what, sizeof what, "%s (z)", who);
-        if (int st = check_launch(what)) return st;
     }
     p.rows = a->m;
     p.w = a->codes;
@@ -627,6 +701,33 @@ int forward(const cq_linear_packed_args* a, int q_format, void* ws, size_t ws_by
     p.y = a->y;
     p.y_f16 = a->y_dtype == CQ_F16;
     p.ldy = a->ldy;
+}
+
+int validate_format(const cq_linear_packed_args* a, int q_format, const char* who) {
+    CQ_REQUIRE(q_format == CQ_QFMT_UNIFORM || q_format == CQ_QFMT_NF, "%s: unknown q_format %d", who, q_format);
+    CQ_REQUIRE(q_format != CQ_QFMT_NF || (std::isfinite(a->qscale) && a->qscale >= 0.f),
+               "%s: NF scale %g is not finite and >= 0", who, (double)a->qscale);
+    return CQ_OK;
+}
+
+int forward(const cq_linear_packed_args* a, int q_format, void* ws, size_t ws_bytes, void* stream, const char* who) {
+    if (int st = validate(a)) return st;
+    if (int st = validate_format(a, q_format, who)) return st;
+    const bool nf = q_format == CQ_QFMT_NF;
+    if (a->tokens == 0) return CQ_OK;
+    if (int st = check_workspace(workspace_bytes(a->tokens, a->r), ws, ws_bytes, who)) return st;
+    const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
+    hipStream_t s = as_stream(stream);
+    LinP z, p;
+    layer_params(a, nf, ws, z, p);
+    if (a->r > 0) {
+        if (!rcoded) launch<16, CQ_QFMT_UNIFORM, 16, true>(z, s);
+        else if (a->r_bits == 2) launch<2, CQ_QFMT_UNIFORM, 16, true>(z, s);
+        else launch<4, CQ_QFMT_UNIFORM, 16, true>(z, s);
+        char what[64];
+        snprintf(what, sizeof what, "%s (z)", who);
+        if (int st = check_launch(what)) return st;
+    }
     const int l_bits = lcoded ? a->l_bits : 16;
     if (nf) {
         if (a->bits == 2) launch_layer<2, CQ_QFMT_NF>(p, l_bits, s);
@@ -636,6 +737,96 @@ int forward(const cq_linear_packed_args* a, int q_format, void* ws, size_t ws_by
         else launch_layer<4, CQ_QFMT_UNIFORM>(p, l_bits, s);
     }
     return check_launch(who);
+}
+
+constexpr const char* kGroupWho = "cq_linear_group_forward";
+
+// the group's workspace: the members' own, at 16-byte aligned offsets (offs, may be null) in member order
+size_t group_offsets(const cq_linear_group_args* g, size_t* offs) {
+    size_t total = 0;
+    for (int i = 0; i < g->count; ++i) {
+        if (offs) offs[i] = total;
+        total += align_up(workspace_bytes(g->members[i].tokens, g->members[i].r), 16);
+    }
+    return total;
+}
+
+// cq_linear_group_forward's decision, made on the host before any launch
+int validate_group(const cq_linear_group_args* g) {
+    CQ_REQUIRE(g != nullptr, "%s: null args", kGroupWho);
+    CQ_REQUIRE(g->count >= 1 && g->count <= CQ_LINEAR_GROUP_MAX, "%s: count %d not in 1 .. %d", kGroupWho, g->count,
+               CQ_LINEAR_GROUP_MAX);
+    CQ_REQUIRE(g->members != nullptr, "%s: null members", kGroupWho);
+    CQ_REQUIRE(g->q_format == CQ_QFMT_UNIFORM || g->q_format == CQ_QFMT_NF, "%s: unknown q_format %d", kGroupWho,
+               g->q_format);
+    const cq_linear_packed_args* a0 = &g->members[0];
+    const cq_linear_packed_args* ranked = nullptr;  // the first member with factors
+    int ranked_i = -1;
+    for (int i = 0; i < g->count; ++i) {
+        const cq_linear_packed_args* a = &g->members[i];
+        char who[64];
+        snprintf(who, sizeof who, "%s: member %d", kGroupWho, i);
+        if (int st = validate(a)) {  // the member's own message, with its index in front
+            char msg[400];
+            snprintf(msg, sizeof msg, "%s", cq_last_error());
+            return set_error(st, "%s: %s", who, msg);
+        }
+        if (int st = validate_format(a, g->q_format, who)) return st;
+#define CQ_GROUP_SAME(field, fmt, cast)                                                                            \
+    CQ_REQUIRE(a->field == a0->field, "%s: " #field " " fmt " differs from member 0's " fmt, who, (cast)a->field, \
+               (cast)a0->field)
+        CQ_GROUP_SAME(x, "%p", const void*);
+        CQ_GROUP_SAME(ldx, "%lld", long long);
+        CQ_GROUP_SAME(tokens, "%lld", long long);
+        CQ_GROUP_SAME(n, "%lld", long long);
+        CQ_GROUP_SAME(bits, "%d", int);
+        CQ_GROUP_SAME(y_dtype, "%d", int);
+#undef CQ_GROUP_SAME
+        if (a->r > 0) {
+            if (!ranked) ranked = a, ranked_i = i;
+            CQ_REQUIRE(a->l_bits == ranked->l_bits, "%s: l_bits %d differs from member %d's %d", who, a->l_bits,
+                       ranked_i, ranked->l_bits);
+            CQ_REQUIRE(a->r_bits == ranked->r_bits, "%s: r_bits %d differs from member %d's %d", who, a->r_bits,
+                       ranked_i, ranked->r_bits);
+        }
+    }
+    return CQ_OK;
+}
+
+int group_forward(const cq_linear_group_args* g, void* ws, size_t ws_bytes, void* stream) {
+    if (int st = validate_group(g)) return st;
+    if (g->members[0].tokens == 0) return CQ_OK;
+    size_t offs[CQ_LINEAR_GROUP_MAX];
+    if (int st = check_workspace(group_offsets(g, offs), ws, ws_bytes, kGroupWho)) return st;
+    const bool nf = g->q_format == CQ_QFMT_NF;
+    hipStream_t s = as_stream(stream);
+    LinP zs[CQ_LINEAR_GROUP_MAX], ps[CQ_LINEAR_GROUP_MAX];
+    int nz = 0, l_bits = 16, r_bits = 16;
+    for (int i = 0; i < g->count; ++i) {
+        const cq_linear_packed_args* a = &g->members[i];
+        LinP z;
+        layer_params(a, nf, static_cast<char*>(ws) + offs[i], z, ps[i]);
+        if (a->r > 0) {  // the factor formats are the ranked members' (validate_group: all the same)
+            zs[nz++] = z;
+            l_bits = coded(a->l_bits) ? a->l_bits : 16;
+            r_bits = coded(a->r_bits) ? a->r_bits : 16;
+        }
+    }
+    if (nz > 0) {  // one z launch over the members with factors
+        if (r_bits == 16) launch_group<16, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
+        else if (r_bits == 2) launch_group<2, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
+        else launch_group<4, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
+        if (int st = check_launch("cq_linear_group_forward (z)")) return st;
+    }
+    const int bits = g->members[0].bits;
+    if (nf) {
+        if (bits == 2) launch_group_layers<2, CQ_QFMT_NF>(ps, g->count, l_bits, s);
+        else launch_group_layers<4, CQ_QFMT_NF>(ps, g->count, l_bits, s);
+    } else {
+        if (bits == 2) launch_group_layers<2, CQ_QFMT_UNIFORM>(ps, g->count, l_bits, s);
+        else launch_group_layers<4, CQ_QFMT_UNIFORM>(ps, g->count, l_bits, s);
+    }
+    return check_launch(kGroupWho);
 }
 
 }  // namespace
@@ -659,6 +850,15 @@ extern "C" int cq_linear_forward(const cq_linear_args* a, void* ws, size_t ws_by
 
 extern "C" int cq_linear_packed_forward(const cq_linear_packed_args* a, void* ws, size_t ws_bytes, void* stream) {
     return forward(a, CQ_QFMT_UNIFORM, ws, ws_bytes, stream, "cq_linear_packed_forward");
+}
+
+extern "C" size_t cq_linear_group_workspace(const cq_linear_group_args* g) {
+    if (g == nullptr || g->members == nullptr || g->count < 1 || g->count > CQ_LINEAR_GROUP_MAX) return 0;
+    return group_offsets(g, nullptr);
+}
+
+extern "C" int cq_linear_group_forward(const cq_linear_group_args* g, void* ws, size_t ws_bytes, void* stream) {
+    return group_forward(g, ws, ws_bytes, stream);
 }
 
 extern "C" size_t cq_linear_codebook_workspace(const cq_linear_codebook_args* a) {

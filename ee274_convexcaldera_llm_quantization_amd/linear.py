@@ -28,8 +28,15 @@ Q = I[idx] (s / D), I the integer levels (include/caldera_hip.h).  Factors stay 
 (cq_linear_dequant, csrc/cq_linear_dequant.hip).  With `dense_prefill_tokens` set a layer hands long
 prefill (and the input gradient at that length) to the dense fp16 GEMM on a weight materialised
 into one scratch buffer that all layers of a stream share; the default, None, changes nothing.
+
+Layers that read the same activation (q / k / v, gate / up) can form a `CalderaLinearGroup`: the set
+runs as one z launch and one code + L launch (cq_linear_group_forward), every output with the bits of
+the layer run alone, and the model's own calls `q_proj(h)`, `k_proj(h)`, `v_proj(h)` stay as they are
+(`model.group_shared_input_layers`).
 """
 from __future__ import annotations
+
+import weakref
 
 import torch
 
@@ -671,7 +678,20 @@ class CalderaLinear(torch.nn.Module):
         return self
 
     # ------------------------------------------------------------------ forward
+    @property
+    def group(self):
+        """The `CalderaLinearGroup` this layer is a member of, or None.  A plain attribute kept in
+        `__dict__`: no buffer, no state, not a submodule."""
+        return self.__dict__.get("_group")
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        group = self.__dict__.get("_group")
+        if group is not None:  # a member of a CalderaLinearGroup: one launch pair for the whole group
+            return group._member_forward(self, x)
+        return self._forward_alone(x)
+
+    def _forward_alone(self, x: torch.Tensor) -> torch.Tensor:
+        """The layer's own launches, whether it is in a group or not."""
         if not x.is_cuda or not self.codes.is_cuda:
             raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
         if x.shape[-1] != self.in_features:
@@ -886,3 +906,147 @@ class HadamardCalderaLinear(torch.nn.Module):
         L16, R16 = _fp16_factors(inner.L, inner.R) if trainable else (None, None)
         y = self._forward_launches(x, L16, R16)[2]
         return y.to(x.dtype).reshape(*x.shape[:-1], self.out_features)
+
+
+def _group_operands(lin):
+    """`_lib.linear_group_args`' member dict of one layer: the operands `_launch_packed` passes."""
+    ranked = lin.rank > 0
+    return dict(codes=lin.codes, qscale=lin.qscale, gscale=lin.gscale,
+                L=lin.L if ranked and lin.L_codes is None else None,
+                R=lin.R if ranked and lin.R_codes is None else None, bias=lin.bias,
+                m=lin.out_features, n=lin.in_features, bits=lin.bits, r=lin.rank,
+                L_codes=(lin.L_codes, lin.lscale, lin.L_bits) if ranked and lin.L_codes is not None else None,
+                R_codes=(lin.R_codes, lin.rscale, lin.R_bits) if ranked and lin.R_codes is not None else None)
+
+
+class CalderaLinearGroup:
+    """Packed layers that read the same activation (q / k / v, gate / up), run as one z launch and
+    one code + L launch (cq_linear_group_forward) instead of two launches each; every member's output
+    has the bits the member computes alone.  A plain object, not a module: the members stay where they
+    are in the model, and their state dict, extra state, `to_result`, `packed_bytes` and `_apply` do
+    not know about it.  Each member keeps a back-reference in its `__dict__` (`CalderaLinear.group`).
+
+    members: 1 .. `_lib.LINEAR_GROUP_MAX` `CalderaLinear` layers on one device that share
+    in_features, bits and q_format, and, among those with rank > 0, L_bits and R_bits; none of them in
+    another group.  `HadamardCalderaLinear` cannot be grouped (its transforms are per layer).
+    ValueError names the member and the attribute.
+
+    group(x) -> the members' outputs in member order, each shaped and typed as member(x).
+
+    member(x) of a grouped layer runs the whole group on the first call with a given x, returns its
+    own output and keeps the siblings' until they are claimed: a sibling called with the same x (the
+    same tensor object, at the same version and data pointer) gets its kept output, which is then
+    dropped.  A call with any other x starts over and releases what was not claimed.  x itself is
+    held through a weak reference only.  So `q_proj(h)`, `k_proj(h)`, `v_proj(h)` of unchanged model
+    code are one launch pair.  (A write to x's memory that does not bump its version counter, e.g.
+    through `x.data`, is not seen.)
+
+    The grouped launch is taken only where it is the members' own inference launch: no autograd graph
+    is needed (grad mode off, or x does not require grad), no member has trainable factors, and no
+    member's `dense_prefill_tokens` applies at this token count.  Otherwise every member runs alone,
+    as without a group.
+
+    member(x) also runs alone when x is an inference tensor (one made under `torch.inference_mode()`):
+    it has no version counter, so a kept output could outlive a write to x.  Use `torch.no_grad()`
+    for the transparent path, or call group(x), which keeps nothing and launches grouped there too.
+
+    The back-reference is an ordinary attribute, so a shallow copy of a member (`nn.DataParallel`'s
+    replicas) carries it without being a member: such a copy runs alone, on its own operands.
+    `copy.deepcopy` or pickling of a single grouped layer takes the group, and with it the siblings,
+    along; copy the model that holds them all, or `dissolve()` first."""
+
+    def __init__(self, members):
+        members = list(members)
+        if not 1 <= len(members) <= K.LINEAR_GROUP_MAX:
+            raise ValueError(f"CalderaLinearGroup: {len(members)} members, not 1 .. {K.LINEAR_GROUP_MAX}")
+        first = ranked = None
+        for i, lin in enumerate(members):
+            if isinstance(lin, HadamardCalderaLinear):
+                raise ValueError(f"CalderaLinearGroup: member {i} is a HadamardCalderaLinear: its input and output "
+                                 "transforms are per layer, it cannot be grouped")
+            if not isinstance(lin, CalderaLinear):
+                raise ValueError(f"CalderaLinearGroup: member {i} is a {type(lin).__name__}, not a CalderaLinear")
+            if any(lin is other for other in members[:i]):
+                raise ValueError(f"CalderaLinearGroup: member {i} is given twice")
+            if lin.__dict__.get("_group") is not None:
+                raise ValueError(f"CalderaLinearGroup: member {i} is already in a group (dissolve() it first)")
+            if first is None:
+                first = lin
+            if lin.codes.device != first.codes.device:
+                raise ValueError(f"CalderaLinearGroup: member {i}: device {lin.codes.device} differs from member 0's "
+                                 f"{first.codes.device}")
+            for attr in ("in_features", "bits", "q_format"):
+                if getattr(lin, attr) != getattr(first, attr):
+                    raise ValueError(f"CalderaLinearGroup: member {i}: {attr} {getattr(lin, attr)} differs from "
+                                     f"member 0's {getattr(first, attr)}")
+            if lin.rank > 0:
+                if ranked is None:
+                    ranked = i
+                for attr in ("L_bits", "R_bits"):
+                    if getattr(lin, attr) != getattr(members[ranked], attr):
+                        raise ValueError(f"CalderaLinearGroup: member {i}: {attr} {getattr(lin, attr)} differs from "
+                                         f"member {ranked}'s {getattr(members[ranked], attr)}")
+        self.members = tuple(members)
+        self._key = None    # (weakref of x, x._version, x.data_ptr()) of the kept outputs
+        self._kept = {}     # id(member) -> its output for that x, until claimed
+        for lin in self.members:
+            lin.__dict__["_group"] = self
+
+    def __len__(self):
+        return len(self.members)
+
+    def __getstate__(self):  # a weak reference does not pickle; the kept outputs are transient
+        return {"members": self.members, "_key": None, "_kept": {}}
+
+    def dissolve(self):
+        """Remove the members' back-references: every layer runs alone again."""
+        for lin in self.members:
+            if lin.__dict__.get("_group") is self:
+                del lin.__dict__["_group"]
+        self._key, self._kept = None, {}
+
+    def _grouped(self, x) -> bool:
+        """Whether the grouped launch is the members' own inference launch for this x."""
+        if torch.is_grad_enabled() and x.requires_grad:
+            return False
+        T = x.numel() // max(x.shape[-1], 1)
+        return not any(lin.factors_trainable or _use_dense(lin, T) for lin in self.members)
+
+    def _launch(self, x):
+        """One cq_linear_group_forward on x: `CalderaLinear.forward`'s x handling and output dtype."""
+        n = self.members[0].in_features
+        if x.shape[-1] != n:
+            raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {n}")
+        x2 = x.reshape(-1, n).to(torch.float16)
+        if x2.stride(1) != 1:
+            x2 = x2.contiguous()
+        ydt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
+        ys = [torch.empty((x2.shape[0], lin.out_features), dtype=ydt, device=x.device) for lin in self.members]
+        K.linear_group_forward(x2, [_group_operands(lin) for lin in self.members], ys, self.members[0].q_format)
+        return tuple(y.to(x.dtype).reshape(*x.shape[:-1], lin.out_features) for y, lin in zip(ys, self.members))
+
+    def __call__(self, x: torch.Tensor):
+        self._key, self._kept = None, {}
+        if not self._grouped(x):
+            return tuple(lin._forward_alone(x) for lin in self.members)
+        return self._launch(x)
+
+    def _member_forward(self, member, x):
+        """`member.forward(x)` of a grouped layer, see the class docstring."""
+        if member not in self.members:
+            # a shallow copy of a member (e.g. a DataParallel replica) still points here: it is not ours
+            return member._forward_alone(x)
+        if x.is_inference() or not self._grouped(x):
+            # an inference tensor has no version counter: a write in place could not be told from the
+            # x the kept outputs belong to, so none are kept for it
+            self._key, self._kept = None, {}
+            return member._forward_alone(x)
+        key = self._key
+        if (key is not None and key[0]() is x and key[1] == x._version and key[2] == x.data_ptr()
+                and id(member) in self._kept):
+            return self._kept.pop(id(member))
+        self._key, self._kept = None, {}   # another x (or a second call with this one): start over
+        ys = self._launch(x)
+        self._kept = {id(lin): y for lin, y in zip(self.members, ys) if lin is not member}
+        self._key = (weakref.ref(x), x._version, x.data_ptr())
+        return ys[self.members.index(member)]

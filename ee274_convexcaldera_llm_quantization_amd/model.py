@@ -342,7 +342,9 @@ def apply_packed_results(model: torch.nn.Module, results, device=None) -> list:
     `extra` has "hadamard": [m, n] (a layer decomposed in the Hadamard basis, on the padded grid)
     is matched against that original shape and becomes a `linear.HadamardCalderaLinear`.  device: where
     the new layers live (default: each replaced module's own device).  KeyError for a result
-    whose module the model does not have; returns the replaced names."""
+    whose module the model does not have; returns the replaced names.  A `linear.CalderaLinearGroup` that a
+    replaced module belonged to is dissolved (a plain packed layer holds no `weight` and is refused by
+    the shape check like any other such module, its group left as it was)."""
     from .linear import CalderaLinear, HadamardCalderaLinear
     modules = dict(model.named_modules())
     done = []
@@ -358,6 +360,7 @@ def apply_packed_results(model: torch.nn.Module, results, device=None) -> list:
                              f"!= result {want}")
         cls = CalderaLinear if had is None else HadamardCalderaLinear
         lin = cls.from_result(res, bias=getattr(mod, "bias", None))
+        _dissolve_group_of(mod)
         _set_module(model, res.name, lin.to(w.device if device is None else device))
         done.append(res.name)
     return done
@@ -444,7 +447,7 @@ def unpack_packed_layers(model: torch.nn.Module, dtype=torch.float16) -> list:
     weight is the layer's `materialize(dtype)` (cq_linear_dequant: fp16, bf16 or fp32) and whose bias
     is the layer's, cast to dtype: the model as plain dense layers, e.g. for export.  Returns the
     replaced names.  ValueError, before anything is changed, for layers whose factors are trainable:
-    call `finish_factor_finetuning` first."""
+    call `finish_factor_finetuning` first.  A `linear.CalderaLinearGroup` of a replaced layer is dissolved."""
     layers = _packed_layers(model)
     bad = [name or "<model>" for name, mod in layers if mod.factors_trainable]
     if bad:
@@ -461,5 +464,72 @@ def unpack_packed_layers(model: torch.nn.Module, dtype=torch.float16) -> list:
             lin.weight.copy_(W)
             if mod.bias is not None:
                 lin.bias.copy_(mod.bias)
+        _dissolve_group_of(mod)  # a group of layers that are no longer all in the model
         _set_module(model, name, lin)
     return [name for name, _ in layers]
+
+
+SHARED_INPUT_SETS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"))
+
+
+def group_shared_input_layers(model: torch.nn.Module, sets=SHARED_INPUT_SETS):
+    """Make a `linear.CalderaLinearGroup` of every set of sibling packed layers that read the same
+    activation: for each module of `model` and each tuple of child names in `sets`, the children of
+    those names, when all of them are `linear.CalderaLinear` layers that can form a group.  The
+    model's code stays as it is: `self.q_proj(h)`, `self.k_proj(h)`, `self.v_proj(h)` then run as one
+    launch pair (see `CalderaLinearGroup`), with the bits of the ungrouped layers.
+
+    Returns (grouped, skipped): the dotted names of each group made, as tuples, and for every set of
+    which a module has at least one child but which was not grouped, (names, reason) -- a child is
+    missing, dense, a Hadamard-basis layer, already grouped, or the layers do not fit one group.
+    Nothing raises for them."""
+    from .linear import CalderaLinear, CalderaLinearGroup, HadamardCalderaLinear
+    grouped, skipped = [], []
+    for prefix, mod in list(model.named_modules()):
+        for names in sets:
+            children = [mod._modules.get(name) for name in names]
+            if all(child is None for child in children):
+                continue
+            full = tuple(f"{prefix}.{name}" if prefix else name for name in names)
+            reason = None
+            for name, child in zip(names, children):
+                if child is None:
+                    reason = f"{name} is missing"
+                elif isinstance(child, HadamardCalderaLinear):
+                    reason = f"{name} is a HadamardCalderaLinear"
+                elif not isinstance(child, CalderaLinear):
+                    reason = f"{name} is dense ({type(child).__name__})"
+                elif child.group is not None:
+                    reason = f"{name} is already grouped"
+                if reason:
+                    break
+            if reason is None:
+                try:
+                    CalderaLinearGroup(children)
+                except ValueError as e:
+                    reason = f"incompatible: {e}"
+            if reason is None:
+                grouped.append(full)
+            else:
+                skipped.append((full, reason))
+    return grouped, skipped
+
+
+def ungroup_shared_input_layers(model: torch.nn.Module) -> list:
+    """Dissolve every `linear.CalderaLinearGroup` that a layer of `model` belongs to; returns the
+    dotted names of each dissolved group's members found in the model, as tuples."""
+    from .linear import CalderaLinear
+    names = {id(mod): name for name, mod in model.named_modules()}
+    done = []
+    for mod in list(model.modules()):
+        group = mod.group if isinstance(mod, CalderaLinear) else None
+        if group is not None:
+            done.append(tuple(names[id(lin)] for lin in group.members if id(lin) in names))
+            group.dissolve()
+    return done
+
+
+def _dissolve_group_of(mod):
+    group = mod.__dict__.get("_group")
+    if group is not None:
+        group.dissolve()

@@ -833,6 +833,40 @@ size_t cq_linear_codebook_backward_workspace(const cq_linear_codebook_backward_a
 int cq_linear_codebook_backward_input(const cq_linear_codebook_backward_args* a, void* ws, size_t ws_bytes,
                                       void* stream);
 
+/* Grouped forward: 1 .. CQ_LINEAR_GROUP_MAX packed layers that read the same activation (q / k / v,
+ * gate / up) in one z launch and one code + L launch instead of two launches each.
+ *
+ * Contract:
+ *   - member i's y is bit for bit what cq_linear_codebook_forward with q_format gives on the same
+ *     operands (for CQ_QFMT_UNIFORM: cq_linear_packed_forward's, and with fp16 factors
+ *     cq_linear_forward's).  It holds by construction: a workgroup of the grouped grid belongs to
+ *     one member, found from its index in a table of first workgroups passed by value, and does
+ *     that member's workgroup's work in the same order.  A workgroup never spans two members;
+ *   - the members share x, ldx, tokens, n, bits, y_dtype and q_format, and the members with r > 0
+ *     share l_bits and r_bits (the kernels' compile-time parameters).  A member with r = 0 fits any
+ *     factor format.  m, r, the scales, bias, y, ldy and every weight pointer are per member;
+ *   - each member is checked as the single-layer entries check it; anything else that does not
+ *     fit is CQ_EINVAL with a message naming the member and the field, decided on the host before
+ *     any launch;
+ *   - workspace: each member's cq_linear_packed_workspace bytes rounded up to 16, laid out in
+ *     member order; cq_linear_group_workspace is their sum (16-byte aligned base);
+ *   - tokens == 0 returns CQ_OK without a launch;
+ *   - at most two launches per call: the z product over the members with r > 0 (none: skipped),
+ *     then codes + L + epilogue over all members;
+ *   - everything else is the single-layer contract: fixed summation order, no float atomics,
+ *     stream-ordered, no allocation, no host-device copy, no synchronisation (graph-capturable).
+ *     The members array is read on the host during the call only. */
+#define CQ_LINEAR_GROUP_MAX 8
+
+typedef struct cq_linear_group_args {
+    int32_t count;                          /* 1 .. CQ_LINEAR_GROUP_MAX */
+    int32_t q_format;                       /* CQ_QFMT_UNIFORM | CQ_QFMT_NF, of every member */
+    const cq_linear_packed_args* members;   /* host array of `count` layers */
+} cq_linear_group_args;
+
+size_t cq_linear_group_workspace(const cq_linear_group_args* g);
+int cq_linear_group_forward(const cq_linear_group_args* g, void* ws, size_t ws_bytes, void* stream);
+
 /* Materialise: the dense weight of a packed layer, for callers that hand long prefill to a dense
  * GEMM from one shared transient buffer, or that want a plain dense layer back.
  *
