@@ -140,6 +140,12 @@ class LinearGroupArgs(ctypes.Structure):
     _fields_ = [("count", ctypes.c_int32), ("q_format", ctypes.c_int32), ("members", ctypes.POINTER(LinearPackedArgs))]
 
 
+class LinearGluArgs(ctypes.Structure):
+    """cq_linear_glu_args: the two members by value (their y fields unused), then the pair's own fields."""
+    _fields_ = [("gate", LinearPackedArgs), ("up", LinearPackedArgs), ("q_format", c_int), ("act", c_int),
+                ("h", c_vp), ("h_dtype", c_int), ("ldh", c_i64)]
+
+
 class LinearDequantArgs(ctypes.Structure):
     _fields_ = [
         ("m", c_i64), ("n", c_i64), ("r", c_i64),
@@ -257,6 +263,8 @@ _SIGS = {
     "cq_linear_codebook_backward_input": (c_int, [ctypes.POINTER(LinearCodebookBackwardArgs), c_vp, c_size, c_vp]),
     "cq_linear_group_workspace": (c_size, [ctypes.POINTER(LinearGroupArgs)]),
     "cq_linear_group_forward": (c_int, [ctypes.POINTER(LinearGroupArgs), c_vp, c_size, c_vp]),
+    "cq_linear_glu_workspace": (c_size, [ctypes.POINTER(LinearGluArgs)]),
+    "cq_linear_glu_forward": (c_int, [ctypes.POINTER(LinearGluArgs), c_vp, c_size, c_vp]),
     "cq_linear_dequant": (c_int, [ctypes.POINTER(LinearDequantArgs), c_vp]),
     "cq_hadamard_rows": (c_int, [ctypes.POINTER(HadamardArgs), c_vp]),
     # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
@@ -1501,6 +1509,66 @@ def linear_group_forward(x, members, ys, q_format, ws=None):
     _check(lib.cq_linear_group_forward(ctypes.byref(g), _p(ws), ws.numel(), _stream(x.device)),
            "cq_linear_group_forward")
     return ys
+
+
+ACT_IDENTITY = 0  # include/caldera_hip.h CQ_ACT_IDENTITY: h = g * u
+ACT_SILU = 1      # CQ_ACT_SILU: h = g / (1 + exp(-g)) * u
+
+
+def linear_glu_args(x, gate, up, h, q_format, act) -> LinearGluArgs:
+    """cq_linear_glu_args of a gated pair on the activation x (T, n) fp16.  gate, up: member dicts as
+    `linear_group_args` takes them; h: the output (T, m) fp32 / fp16, may be a view with a row stride.
+    Each member passes `linear_packed_args`' host-side checks and `q_format`'s; the two must share m, n
+    and bits, and when both have r > 0 the factor formats.  The members' y fields stay zero."""
+    need = _linear_need
+    need(q_format in (QFMT_UNIFORM, QFMT_NF), f"glu: unknown q_format {q_format!r}")
+    need(act in (ACT_IDENTITY, ACT_SILU), f"glu: unknown act {act!r}")
+    need(torch.is_tensor(h) and h.dim() == 2 and h.stride(1) == 1, "glu: h must be a matrix with unit column stride")
+    need(h.dtype in (torch.float32, torch.float16), f"glu: h must be fp32 or fp16, got {h.dtype}")
+    need(tuple(h.shape) == (x.shape[0], gate["m"]), f"glu: h {tuple(h.shape)} does not fit (tokens, m) = "
+         f"{(x.shape[0], gate['m'])}")
+    need(h.shape[0] <= 1 or h.stride(0) >= h.shape[1], f"glu: ldh {h.stride(0)} < m {h.shape[1]}")
+    a = LinearGluArgs()
+    for name, mem in (("gate", gate), ("up", up)):
+        p = getattr(a, name)
+        try:
+            _check_q_format(q_format, mem["qscale"])
+            need(mem["m"] == gate["m"], f"m {mem['m']} differs from gate's {gate['m']}")
+            # h stands in for y while the member's other operands are checked
+            linear_packed_args(x, mem["codes"], mem["qscale"], mem["gscale"], mem.get("L"), mem.get("R"),
+                               mem.get("bias"), h, m=mem["m"], n=mem["n"], bits=mem["bits"], r=mem.get("r"),
+                               L_codes=mem.get("L_codes"), R_codes=mem.get("R_codes"), into=p)
+        except ValueError as e:
+            raise ValueError(f"cq_linear: glu {name}: {str(e).removeprefix('cq_linear: ')}") from None
+        p.y, p.y_dtype, p.ldy = None, 0, 0
+        for field in ("n", "bits"):
+            need(getattr(p, field) == getattr(a.gate, field), f"glu {name}: {field} {getattr(p, field)} differs "
+                 f"from gate's {getattr(a.gate, field)}")
+    if a.gate.r > 0 and a.up.r > 0:
+        for field in ("l_bits", "r_bits"):
+            need(getattr(a.up, field) == getattr(a.gate, field), f"glu up: {field} {getattr(a.up, field)} differs "
+                 f"from gate's {getattr(a.gate, field)}")
+    a.q_format, a.act = int(q_format), int(act)
+    a.h, a.ldh = h.data_ptr(), h.stride(0) if h.shape[0] > 1 else max(h.stride(0), h.shape[1])
+    a.h_dtype = {torch.float32: CQ_F32, torch.float16: CQ_F16}[h.dtype]
+    return a
+
+
+def linear_glu_forward(x, gate, up, h, q_format, act=ACT_SILU, ws=None):
+    """h = a(gate(x)) * up(x) of a gated pair in one z launch and one code + L launch
+    (cq_linear_glu_forward): the pre-activations have the bits of the members' own fp32 outputs and are
+    never written.  Operands as `linear_glu_args`, ws as `linear_forward`.  No host synchronisation."""
+    for mem in (gate, up):
+        _require_hip(x, mem["codes"], mem.get("L"), mem.get("R"), mem.get("bias"),
+                     None if mem.get("L_codes") is None else mem["L_codes"][0],
+                     None if mem.get("R_codes") is None else mem["R_codes"][0])
+    _require_hip(h)
+    a = linear_glu_args(x, gate, up, h, q_format, act)
+    lib = load()
+    if ws is None:
+        ws = workspace(lib.cq_linear_glu_workspace(ctypes.byref(a)), x.device)
+    _check(lib.cq_linear_glu_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)), "cq_linear_glu_forward")
+    return h
 
 
 def linear_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, ws=None):

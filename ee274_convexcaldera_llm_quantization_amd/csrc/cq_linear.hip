@@ -567,6 +567,365 @@ void launch_group_layers(const LinP* ps, int count, int l_bits, hipStream_t s) {
     else launch_group<WT, QF, 16, false>(ps, count, s);
 }
 
+// Gated pair (cq_linear_glu_forward): h = act(v_g) * v_u with v_g, v_u the fp32 values linear_kernel's
+// epilogue forms for the layers g (gate) and u (up), which share x, T, n, rows and the template
+// parameters.  A wave owns the SAME weight rows of both layers, so both pre-activations of an output
+// sit in its registers and neither is written.  The row-to-wave mapping differs from linear_kernel's
+// (a prefill wave owns RG = 2 row groups of each layer where linear_kernel's owns 4 of one: the same 16
+// accumulator tiles); what one output goes through does not: the loaders, `expand`, the chunk and k step
+// order, hi plane before lo, s / k on the accumulator before the L product resp. s0 * sk + s1 after the
+// ordered LDS add, gs, then the bias are linear_kernel's, line by line, so v_g and v_u have the bits of
+// the layers run alone.  An x fragment is loaded once and feeds both layers.  The two L products run
+// one after the other, each over its own rank (r = 0: no iterations).  Decode: the four partial tiles
+// of a wave (code and L sums of g and of u) go through 32 KB of LDS and wave 0 adds them in wave order.
+struct GluP {
+    LinP g, u;                 // y, y_f16, ldy: not used
+    int act;                   // CQ_ACT_*
+    void* h; int h_f16; int64_t ldh;
+};
+
+template <int WT, int QF, int LB, int TT, int RG, int NW, bool KSPLIT>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(TT > 1 ? 2 : 1))) void
+linear_glu_kernel(const GluP arg) {
+    constexpr int M = 2;
+    auto mp = [&](int mi) -> const LinP& { return mi ? arg.u : arg.g; };
+    const LinP& p = arg.g;  // what the two layers share: x, ldx, x_al, T, n, rows
+    constexpr bool NF = QF == CQ_QFMT_NF;
+    constexpr bool PLANES2 = NF && WT == 2;
+    static_assert(WT == 2 || WT == 4, "the layers' own weights are codes");
+    const uint32_t* nftab = nullptr;
+    if constexpr (NF) {  // before any wave leaves
+        __shared__ uint32_t tab[WT == 4 ? 256 : 512];
+        fill_nf_table<WT>(tab, threadIdx.x, NW * 64);
+        __syncthreads();
+        nftab = tab;
+    }
+    constexpr int CK = 16 * 8 / WT * 4;   // k per chunk: 4 lane groups x one 16-byte load
+    constexpr int NM = CK / 32;           // MFMA k steps per chunk
+    constexpr int GK = CK / 4;            // k per lane group
+    static_assert(!KSPLIT || (TT == 1 && RG == 1), "the K split reduces one tile per layer");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int li = lane & 15, g = lane >> 4;
+    const int64_t row0 = (KSPLIT ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * NW + wave) * (16 * RG);
+    const int64_t tok0 = KSPLIT ? 0 : (int64_t)blockIdx.y * (TT * 16);
+    if (!KSPLIT && row0 >= p.rows) return;
+
+    int64_t rowc[RG];
+#pragma unroll
+    for (int rg = 0; rg < RG; ++rg) {
+        const int64_t row = row0 + rg * 16 + li;
+        rowc[rg] = row < p.rows ? row : p.rows - 1;
+    }
+    const _Float16* xrow[TT];
+    int64_t xlim[TT];
+#pragma unroll
+    for (int tt = 0; tt < TT; ++tt) {
+        const int64_t t = tok0 + tt * 16 + li;
+        xrow[tt] = p.x + (t < p.T ? t : 0) * p.ldx;
+        xlim[tt] = t < p.T ? p.n : 0;
+    }
+
+    f4 acc[M][RG][TT], accl[M];
+#pragma unroll
+    for (int mi = 0; mi < M; ++mi) {
+        accl[mi] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int rg = 0; rg < RG; ++rg)
+#pragma unroll
+            for (int tt = 0; tt < TT; ++tt) acc[mi][rg][tt] = f4{0.f, 0.f, 0.f, 0.f};
+    }
+
+    const int64_t nchunks = (p.n + CK - 1) / CK;
+    const int64_t c0 = KSPLIT ? wave : 0, cstep = KSPLIT ? NW : 1;
+
+    auto load_w = [&](int mi, int64_t c, int rg) -> u4 {
+        const int64_t kg = c * CK + g * GK;
+        const uint8_t* wrow = mp(mi).w + rowc[rg] * mp(mi).wstride;
+        // a piece that starts inside n lies inside the 16-byte padded row
+        return kg < p.n ? *reinterpret_cast<const u4*>(wrow + kg * WT / 8) : u4{0u, 0u, 0u, 0u};
+    };
+    auto frag = [&](const u4& w, int jj) -> h8 {
+        if constexpr (NF) return expand_nf<WT>(nftab, WT == 4 ? w[jj & 3] : w[jj >> 1], jj & 1);
+        else return expand<WT>(w, jj);
+    };
+    auto load_x = [&](int64_t c, int jj, int tt) -> h8 {
+        return ld8(xrow[tt], c * CK + g * GK + jj * 8, xlim[tt], p.x_al);
+    };
+
+    // L codes, as in linear_kernel: nothing is read from q0 >= r on
+    constexpr int LCK = LB == 16 ? 32 : 16 * 8 / LB * 4, LNM = LCK / 32, LGK = LCK / 4;
+    auto load_l = [&](const LinP& pm, int64_t c, int rg) -> u4 {
+        const int64_t q0 = c * LCK + g * LGK;
+        return q0 < pm.r ? *reinterpret_cast<const u4*>(pm.lc + rowc[rg] * pm.lcstride + q0 * LB / 8)
+                         : u4{0u, 0u, 0u, 0u};
+    };
+    u4 lfirst[M] = {u4{0u, 0u, 0u, 0u}, u4{0u, 0u, 0u, 0u}};
+    if constexpr (LB != 16 && KSPLIT) {  // decode: both layers' first L unit before the K loop
+#pragma unroll
+        for (int mi = 0; mi < M; ++mi)
+            if (c0 < (mp(mi).r + LCK - 1) / LCK * LNM) lfirst[mi] = load_l(mp(mi), c0 / LNM, 0);
+    }
+
+    u4 q[M][RG], qn[M][RG];
+    if constexpr (TT == 1) {
+        // decode: the next chunk's codes of both layers and all its x fragments are in flight during this one
+        h8 a[NM], an[NM];
+        if (c0 < nchunks) {
+#pragma unroll
+            for (int mi = 0; mi < M; ++mi) q[mi][0] = load_w(mi, c0, 0);
+#pragma unroll
+            for (int jj = 0; jj < NM; ++jj) a[jj] = load_x(c0, jj, 0);
+        }
+        for (int64_t c = c0; c < nchunks; c += cstep) {
+            if (c + cstep < nchunks) {
+#pragma unroll
+                for (int mi = 0; mi < M; ++mi) qn[mi][0] = load_w(mi, c + cstep, 0);
+#pragma unroll
+                for (int jj = 0; jj < NM; ++jj) an[jj] = load_x(c + cstep, jj, 0);
+            }
+#pragma unroll
+            for (int jj = 0; jj < NM; ++jj) {
+#pragma unroll
+                for (int mi = 0; mi < M; ++mi) {
+                    const h8 b = frag(q[mi][0], jj);
+                    acc[mi][0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[jj], b, acc[mi][0][0], 0, 0, 0);
+                    if constexpr (PLANES2)
+                        acc[mi][0][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[jj], nf2_lo(b), acc[mi][0][0], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int mi = 0; mi < M; ++mi) q[mi][0] = qn[mi][0];
+#pragma unroll
+            for (int jj = 0; jj < NM; ++jj) a[jj] = an[jj];
+        }
+    } else {
+        // prefill: codes one chunk ahead, x fragments one k step ahead; an x fragment feeds M RG MFMAs
+        h8 a[TT], an[TT];
+        if (c0 < nchunks) {
+#pragma unroll
+            for (int mi = 0; mi < M; ++mi)
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg) q[mi][rg] = load_w(mi, c0, rg);
+#pragma unroll
+            for (int tt = 0; tt < TT; ++tt) a[tt] = load_x(c0, 0, tt);
+        }
+        for (int64_t c = c0; c < nchunks; c += cstep) {
+            const bool more = c + cstep < nchunks;
+            if (more) {
+#pragma unroll
+                for (int mi = 0; mi < M; ++mi)
+#pragma unroll
+                    for (int rg = 0; rg < RG; ++rg) qn[mi][rg] = load_w(mi, c + cstep, rg);
+            }
+#pragma unroll
+            for (int jj = 0; jj < NM; ++jj) {
+                if (jj + 1 < NM) {
+#pragma unroll
+                    for (int tt = 0; tt < TT; ++tt) an[tt] = load_x(c, jj + 1, tt);
+                } else if (more) {
+#pragma unroll
+                    for (int tt = 0; tt < TT; ++tt) an[tt] = load_x(c + cstep, 0, tt);
+                }
+#pragma unroll
+                for (int mi = 0; mi < M; ++mi)
+#pragma unroll
+                    for (int rg = 0; rg < RG; ++rg) {
+                        const h8 b = frag(q[mi][rg], jj);
+#pragma unroll
+                        for (int tt = 0; tt < TT; ++tt)
+                            acc[mi][rg][tt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[tt], b, acc[mi][rg][tt], 0, 0, 0);
+                        if constexpr (PLANES2) {
+                            const h8 bl = nf2_lo(b);
+#pragma unroll
+                            for (int tt = 0; tt < TT; ++tt)
+                                acc[mi][rg][tt] =
+                                    __builtin_amdgcn_mfma_f32_16x16x32_f16(a[tt], bl, acc[mi][rg][tt], 0, 0, 0);
+                        }
+                    }
+#pragma unroll
+                for (int tt = 0; tt < TT; ++tt) a[tt] = an[tt];
+            }
+#pragma unroll
+            for (int mi = 0; mi < M; ++mi)
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg) q[mi][rg] = qn[mi][rg];
+        }
+    }
+
+    // the z fragment of layer pm, token tile tt, columns qq .. qq + 7 as split halves (linear_kernel's)
+    auto load_z = [&](const LinP& pm, int tt, int64_t qq, h8& zh, h8& zl) {
+        const int64_t zo = (tok0 + tt * 16 + li) * pm.r32 + qq;
+        const bool in = LB == 16 || qq < pm.r32;
+        if constexpr (KSPLIT) {  // the partial z of the z kernel's workgroups, added in order
+            float zs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            if (li < pm.T && in) {  // rows past T are zero
+                for (int ks = 0; ks < kDecodeSplitZ; ++ks) {
+                    const f4* pp = reinterpret_cast<const f4*>(pm.zp + (int64_t)ks * 16 * pm.r32 + zo);
+                    const f4 u = pp[0], v = pp[1];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) zs[j] += u[j], zs[4 + j] += v[j];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float zv = zs[j] * pm.zscale;  // once, on the complete sum
+                zh[j] = (_Float16)zv;
+                zl[j] = (_Float16)(zv - (float)zh[j]);
+            }
+        } else if (in) {
+            zl = *reinterpret_cast<const h8*>(pm.zl + zo);
+            zh = *reinterpret_cast<const h8*>(pm.zh + zo);
+        } else {
+            zl = zh = h8{0, 0, 0, 0, 0, 0, 0, 0};
+        }
+    };
+
+    // the L products, one layer after the other: onto its own tile under the K split, else onto the
+    // scaled code sum
+#pragma unroll
+    for (int mi = 0; mi < M; ++mi) {
+        const LinP& pm = mp(mi);
+        if constexpr (!KSPLIT) {  // s / k once per output
+#pragma unroll
+            for (int rg = 0; rg < RG; ++rg)
+#pragma unroll
+                for (int tt = 0; tt < TT; ++tt) acc[mi][rg][tt] = acc[mi][rg][tt] * pm.sk;
+        }
+        if constexpr (LB == 16) {
+            const int64_t lchunks = pm.r32 / 32;
+            for (int64_t c = c0; c < lchunks; c += cstep) {
+                const int64_t qq = c * 32 + g * 8;
+                h8 b[RG];
+#pragma unroll
+                for (int rg = 0; rg < RG; ++rg) b[rg] = ld8(pm.L + rowc[rg] * pm.ldl, qq, pm.r, pm.l_al);
+#pragma unroll
+                for (int tt = 0; tt < TT; ++tt) {
+                    h8 zl, zh;
+                    load_z(pm, tt, qq, zh, zl);
+#pragma unroll
+                    for (int rg = 0; rg < RG; ++rg) {
+                        f4& d = KSPLIT ? accl[mi] : acc[mi][rg][tt];
+                        d = __builtin_amdgcn_mfma_f32_16x16x32_f16(zl, b[rg], d, 0, 0, 0);
+                        d = __builtin_amdgcn_mfma_f32_16x16x32_f16(zh, b[rg], d, 0, 0, 0);
+                    }
+                }
+            }
+        } else {
+            const int64_t lchunks = (pm.r + LCK - 1) / LCK;
+            if constexpr (KSPLIT) {
+                // decode: one k step of one chunk per unit, interleaved over the waves
+                for (int64_t u = c0; u < lchunks * LNM; u += cstep) {
+                    const int64_t c = u / LNM;
+                    const int jj = (int)(u % LNM);
+                    if (c * LCK + jj * 8 >= pm.r32) continue;  // no lane has z columns here
+                    const h8 b = expand<LB>(u == c0 ? lfirst[mi] : load_l(pm, c, 0), jj);
+                    h8 zl, zh;
+                    load_z(pm, 0, c * LCK + g * LGK + jj * 8, zh, zl);
+                    accl[mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zl, b, accl[mi], 0, 0, 0);
+                    accl[mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(zh, b, accl[mi], 0, 0, 0);
+                }
+            } else {
+                for (int64_t c = 0; c < lchunks; ++c) {
+                    u4 lw[RG];
+#pragma unroll
+                    for (int rg = 0; rg < RG; ++rg) lw[rg] = load_l(pm, c, rg);
+#pragma unroll
+                    for (int jj = 0; jj < LNM; ++jj) {
+                        if (c * LCK + jj * 8 >= pm.r32) break;
+                        h8 b[RG];
+#pragma unroll
+                        for (int rg = 0; rg < RG; ++rg) b[rg] = expand<LB>(lw[rg], jj);
+#pragma unroll
+                        for (int tt = 0; tt < TT; ++tt) {
+                            h8 zl, zh;
+                            load_z(pm, tt, c * LCK + g * LGK + jj * 8, zh, zl);
+#pragma unroll
+                            for (int rg = 0; rg < RG; ++rg) {
+                                acc[mi][rg][tt] =
+                                    __builtin_amdgcn_mfma_f32_16x16x32_f16(zl, b[rg], acc[mi][rg][tt], 0, 0, 0);
+                                acc[mi][rg][tt] =
+                                    __builtin_amdgcn_mfma_f32_16x16x32_f16(zh, b[rg], acc[mi][rg][tt], 0, 0, 0);
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+
+    if constexpr (KSPLIT) {  // the four partial tiles summed in wave order
+        __shared__ f4 red[NW][2 * M][64];
+#pragma unroll
+        for (int mi = 0; mi < M; ++mi) {
+            red[wave][2 * mi][lane] = acc[mi][0][0];
+            red[wave][2 * mi + 1][lane] = accl[mi];
+        }
+        __syncthreads();
+        if (wave != 0) return;
+#pragma unroll
+        for (int mi = 0; mi < M; ++mi) {
+            f4 s0 = red[0][2 * mi][lane], s1 = red[0][2 * mi + 1][lane];
+#pragma unroll
+            for (int w = 1; w < NW; ++w) {
+                s0 += red[w][2 * mi][lane];
+                s1 += red[w][2 * mi + 1][lane];
+            }
+            acc[mi][0][0] = s0 * mp(mi).sk + s1;
+        }
+    }
+
+    // D tile: column (weight row) = lane & 15, row (token) = 4 (lane >> 4) + register
+#pragma unroll
+    for (int rg = 0; rg < RG; ++rg) {
+        const int64_t row = row0 + rg * 16 + li;
+#pragma unroll
+        for (int tt = 0; tt < TT; ++tt) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t t = tok0 + tt * 16 + g * 4 + e;
+                if (row < p.rows && t < p.T) {
+                    float vg = arg.g.gs * acc[0][rg][tt][e];
+                    if (arg.g.bias) vg += arg.g.bias[row];
+                    float vu = arg.u.gs * acc[1][rg][tt][e];
+                    if (arg.u.bias) vu += arg.u.bias[row];
+                    float a = vg;
+                    if (arg.act == CQ_ACT_SILU) {  // the device library's expf, one correctly rounded division
+                        const float ex = expf(-vg);
+                        const float d = 1.0f + ex;
+                        a = vg / d;
+                    }
+                    const float h32 = a * vu;  // one fp32 multiply
+                    if (arg.h_f16) reinterpret_cast<_Float16*>(arg.h)[t * arg.ldh + row] = (_Float16)h32;
+                    else reinterpret_cast<float*>(arg.h)[t * arg.ldh + row] = h32;
+                }
+            }
+        }
+    }
+}
+
+constexpr int kGluPrefillGroups = 2;  // 16-row groups of each layer per prefill wave
+
+template <int WT, int QF, int LB>
+void launch_glu(const GluP& a, hipStream_t s) {
+    const int64_t groups = ceil_div(a.g.rows, 16);
+    if (a.g.T <= kDecodeMax) {
+        hipLaunchKernelGGL((linear_glu_kernel<WT, QF, LB, 1, 1, kDecodeWaves, true>), dim3((unsigned)groups),
+                           dim3(kDecodeWaves * 64), 0, s, a);
+    } else {
+        const dim3 grid((unsigned)ceil_div(groups, kPrefillWaves * kGluPrefillGroups),
+                        (unsigned)ceil_div(a.g.T, kPrefillTiles * 16));
+        hipLaunchKernelGGL((linear_glu_kernel<WT, QF, LB, kPrefillTiles, kGluPrefillGroups, kPrefillWaves, false>), grid,
+                           dim3(kPrefillWaves * 64), 0, s, a);
+    }
+}
+
+template <int WT, int QF>
+void launch_glu_layers(const GluP& a, int l_bits, hipStream_t s) {
+    if (l_bits == 2) launch_glu<WT, QF, 2>(a, s);
+    else if (l_bits == 4) launch_glu<WT, QF, 4>(a, s);
+    else launch_glu<WT, QF, 16>(a, s);
+}
+
 inline bool coded(int bits) { return bits == 2 || bits == 4; }
 inline float kmax(int bits) { return (float)((1 << (bits - 1)) - 1); }
 
@@ -581,7 +940,8 @@ int validate_factor(const char* name, int bits, const uint8_t* codes, int64_t st
     return CQ_OK;
 }
 
-int validate(const cq_linear_packed_args* a) {
+// with_y = false: y, y_dtype and ldy are neither used nor checked (a member of cq_linear_glu_args)
+int validate(const cq_linear_packed_args* a, bool with_y = true) {
     CQ_REQUIRE(a != nullptr, "cq_linear: null args");
     CQ_REQUIRE(a->bits == 2 || a->bits == 4, "cq_linear: bits %d not in {2, 4}", a->bits);
     CQ_REQUIRE((coded(a->l_bits) || a->l_bits == 16) && (coded(a->r_bits) || a->r_bits == 16),
@@ -591,8 +951,9 @@ int validate(const cq_linear_packed_args* a) {
                (long long)a->tokens, (long long)a->m, (long long)a->n, (long long)a->r);
     CQ_REQUIRE(a->r <= CQ_LINEAR_MAX_RANK, "cq_linear: rank %lld > %d", (long long)a->r, CQ_LINEAR_MAX_RANK);
     CQ_REQUIRE(a->tokens <= (int64_t)65535 * 64 && a->m <= ((int64_t)1 << 31), "cq_linear: shape too large");
-    CQ_REQUIRE(a->y_dtype == CQ_F32 || a->y_dtype == CQ_F16, "cq_linear: y dtype %d not fp32 / fp16", a->y_dtype);
-    CQ_REQUIRE(a->x && a->codes && a->y, "cq_linear: null x / codes / y");
+    CQ_REQUIRE(!with_y || a->y_dtype == CQ_F32 || a->y_dtype == CQ_F16, "cq_linear: y dtype %d not fp32 / fp16",
+               a->y_dtype);
+    CQ_REQUIRE(a->x && a->codes && (!with_y || a->y), "cq_linear: null x / codes / y");
     CQ_REQUIRE(a->r == 0 || ((lcoded || a->L) && (rcoded || a->R)), "cq_linear: null L / R with r = %lld",
                (long long)a->r);
     if (lcoded)
@@ -606,10 +967,10 @@ int validate(const cq_linear_packed_args* a) {
     CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->x) & 1) == 0 && (reinterpret_cast<uintptr_t>(a->L) & 1) == 0 &&
                    (reinterpret_cast<uintptr_t>(a->R) & 1) == 0,
                "cq_linear: misaligned fp16 pointer");
-    CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->y) & (a->y_dtype == CQ_F16 ? 1 : 3)) == 0 &&
+    CQ_REQUIRE((!with_y || (reinterpret_cast<uintptr_t>(a->y) & (a->y_dtype == CQ_F16 ? 1 : 3)) == 0) &&
                    (reinterpret_cast<uintptr_t>(a->bias) & 3) == 0,
                "cq_linear: misaligned y / bias pointer");
-    CQ_REQUIRE(a->ldx >= a->n && a->ldy >= a->m &&
+    CQ_REQUIRE(a->ldx >= a->n && (!with_y || a->ldy >= a->m) &&
                    (a->r == 0 || ((lcoded || a->ldl >= a->r) && (rcoded || a->ldr >= a->n))),
                "cq_linear: leading dimension smaller than the row");
     return CQ_OK;
@@ -829,6 +1190,100 @@ int group_forward(const cq_linear_group_args* g, void* ws, size_t ws_bytes, void
     return check_launch(kGroupWho);
 }
 
+constexpr const char* kGluWho = "cq_linear_glu_forward";
+
+inline const cq_linear_packed_args* glu_member(const cq_linear_glu_args* a, int i) { return i ? &a->up : &a->gate; }
+
+// the pair's workspace: the grouped entry's layout for the two members gate, up
+size_t glu_offsets(const cq_linear_glu_args* a, size_t* offs) {
+    size_t total = 0;
+    for (int i = 0; i < 2; ++i) {
+        if (offs) offs[i] = total;
+        total += align_up(workspace_bytes(glu_member(a, i)->tokens, glu_member(a, i)->r), 16);
+    }
+    return total;
+}
+
+// cq_linear_glu_forward's decision, made on the host before any launch
+int validate_glu(const cq_linear_glu_args* a) {
+    CQ_REQUIRE(a != nullptr, "%s: null args", kGluWho);
+    CQ_REQUIRE(a->q_format == CQ_QFMT_UNIFORM || a->q_format == CQ_QFMT_NF, "%s: unknown q_format %d", kGluWho,
+               a->q_format);
+    CQ_REQUIRE(a->act == CQ_ACT_IDENTITY || a->act == CQ_ACT_SILU, "%s: unknown act %d", kGluWho, a->act);
+    CQ_REQUIRE(a->h_dtype == CQ_F32 || a->h_dtype == CQ_F16, "%s: h_dtype %d not fp32 / fp16", kGluWho, a->h_dtype);
+    const cq_linear_packed_args* g = &a->gate;
+    for (int i = 0; i < 2; ++i) {
+        const cq_linear_packed_args* m = glu_member(a, i);
+        char who[64];
+        snprintf(who, sizeof who, "%s: %s", kGluWho, i ? "up" : "gate");
+        if (int st = validate(m, false)) {  // the member's own message, with its name in front
+            char msg[400];
+            snprintf(msg, sizeof msg, "%s", cq_last_error());
+            return set_error(st, "%s: %s", who, msg);
+        }
+        if (int st = validate_format(m, a->q_format, who)) return st;
+#define CQ_GLU_SAME(field, fmt, cast) \
+    CQ_REQUIRE(m->field == g->field, "%s: " #field " " fmt " differs from gate's " fmt, who, (cast)m->field, (cast)g->field)
+        CQ_GLU_SAME(x, "%p", const void*);
+        CQ_GLU_SAME(ldx, "%lld", long long);
+        CQ_GLU_SAME(tokens, "%lld", long long);
+        CQ_GLU_SAME(n, "%lld", long long);
+        CQ_GLU_SAME(m, "%lld", long long);
+        CQ_GLU_SAME(bits, "%d", int);
+        if (m->r > 0 && g->r > 0) {
+            CQ_GLU_SAME(l_bits, "%d", int);
+            CQ_GLU_SAME(r_bits, "%d", int);
+        }
+#undef CQ_GLU_SAME
+    }
+    CQ_REQUIRE(a->h != nullptr, "%s: null h", kGluWho);
+    CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->h) & (a->h_dtype == CQ_F16 ? 1 : 3)) == 0, "%s: misaligned h pointer",
+               kGluWho);
+    CQ_REQUIRE(a->ldh >= g->m, "%s: ldh %lld < m %lld", kGluWho, (long long)a->ldh, (long long)g->m);
+    return CQ_OK;
+}
+
+int glu_forward(const cq_linear_glu_args* a, void* ws, size_t ws_bytes, void* stream) {
+    if (int st = validate_glu(a)) return st;
+    if (a->gate.tokens == 0) return CQ_OK;
+    size_t offs[2];
+    if (int st = check_workspace(glu_offsets(a, offs), ws, ws_bytes, kGluWho)) return st;
+    const bool nf = a->q_format == CQ_QFMT_NF;
+    hipStream_t s = as_stream(stream);
+    GluP gp{};
+    LinP zs[2];
+    int nz = 0, l_bits = 16, r_bits = 16;
+    for (int i = 0; i < 2; ++i) {
+        const cq_linear_packed_args* m = glu_member(a, i);
+        LinP z;
+        layer_params(m, nf, static_cast<char*>(ws) + offs[i], z, i ? gp.u : gp.g);
+        if (m->r > 0) {  // the factor formats are the ranked members' (validate_glu: the same)
+            zs[nz++] = z;
+            l_bits = coded(m->l_bits) ? m->l_bits : 16;
+            r_bits = coded(m->r_bits) ? m->r_bits : 16;
+        }
+    }
+    gp.act = a->act;
+    gp.h = a->h;
+    gp.h_f16 = a->h_dtype == CQ_F16;
+    gp.ldh = a->ldh;
+    if (nz > 0) {  // the grouped z launch over the members with factors, unchanged
+        if (r_bits == 16) launch_group<16, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
+        else if (r_bits == 2) launch_group<2, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
+        else launch_group<4, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
+        if (int st = check_launch("cq_linear_glu_forward (z)")) return st;
+    }
+    const int bits = a->gate.bits;
+    if (nf) {
+        if (bits == 2) launch_glu_layers<2, CQ_QFMT_NF>(gp, l_bits, s);
+        else launch_glu_layers<4, CQ_QFMT_NF>(gp, l_bits, s);
+    } else {
+        if (bits == 2) launch_glu_layers<2, CQ_QFMT_UNIFORM>(gp, l_bits, s);
+        else launch_glu_layers<4, CQ_QFMT_UNIFORM>(gp, l_bits, s);
+    }
+    return check_launch(kGluWho);
+}
+
 }  // namespace
 }  // namespace cq
 
@@ -868,4 +1323,12 @@ extern "C" size_t cq_linear_codebook_workspace(const cq_linear_codebook_args* a)
 extern "C" int cq_linear_codebook_forward(const cq_linear_codebook_args* a, void* ws, size_t ws_bytes, void* stream) {
     CQ_REQUIRE(a != nullptr, "cq_linear_codebook_forward: null args");
     return forward(&a->p, a->q_format, ws, ws_bytes, stream, "cq_linear_codebook_forward");
+}
+
+extern "C" size_t cq_linear_glu_workspace(const cq_linear_glu_args* a) {
+    return a == nullptr ? 0 : glu_offsets(a, nullptr);
+}
+
+extern "C" int cq_linear_glu_forward(const cq_linear_glu_args* a, void* ws, size_t ws_bytes, void* stream) {
+    return glu_forward(a, ws, ws_bytes, stream);
 }

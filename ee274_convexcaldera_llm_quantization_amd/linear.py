@@ -33,6 +33,11 @@ Layers that read the same activation (q / k / v, gate / up) can form a `CalderaL
 runs as one z launch and one code + L launch (cq_linear_group_forward), every output with the bits of
 the layer run alone, and the model's own calls `q_proj(h)`, `k_proj(h)`, `v_proj(h)` stay as they are
 (`model.group_shared_input_layers`).
+
+A gated MLP block `down_proj(act(gate_proj(x)) * up_proj(x))` can become a `CalderaGatedMLP`: its gate / up
+pair runs as one z launch and one code + L launch whose epilogue applies the activation and the product
+(cq_linear_glu_forward), so neither pre-activation is written and the two elementwise launches are gone
+(`model.fuse_gated_mlps`).
 """
 from __future__ import annotations
 
@@ -1050,3 +1055,119 @@ class CalderaLinearGroup:
         self._kept = {id(lin): y for lin, y in zip(self.members, ys) if lin is not member}
         self._key = (weakref.ref(x), x._version, x.data_ptr())
         return ys[self.members.index(member)]
+
+
+ACTIVATIONS = {"silu": K.ACT_SILU, "identity": K.ACT_IDENTITY}
+# Q bits -> the largest token count at which `CalderaGatedMLP` takes the fused launch by default.  Measured on
+# 2 x 11008 x 4096 (tools/bench_linear_mlp.py): at 2 bits (r = 128) the fused launch is faster at
+# every T measured up to 2048, so there is no limit; at 4 bits (r = 256) it is level with the grouped pair +
+# silu + product at T = 64 (170.4 against 170.6 us) and slower at T = 512 (353.0 against 350.2 us) and
+# T = 2048 (1104 against 1077 us), so above 64 tokens the block takes the unfused formula.
+FUSED_TOKEN_LIMIT = {2: None, 4: 64}
+
+
+def _act_torch(act: int, g: torch.Tensor) -> torch.Tensor:
+    return torch.nn.functional.silu(g) if act == K.ACT_SILU else g
+
+
+def glu_fit(gate, up):
+    """None when the layers `gate` and `up` fit cq_linear_glu_forward, else the reason as a string that
+    names the attribute."""
+    for name, lin in (("gate_proj", gate), ("up_proj", up)):
+        if isinstance(lin, HadamardCalderaLinear):
+            return (f"{name} is a HadamardCalderaLinear: its input and output transforms are per layer, it does "
+                    "not fit the fused launch")
+        if not isinstance(lin, CalderaLinear):
+            return f"{name} is a {type(lin).__name__}, not a CalderaLinear"
+    if gate is up:
+        return "gate_proj and up_proj are the same layer"
+    if up.codes.device != gate.codes.device:
+        return f"up_proj: device {up.codes.device} differs from gate_proj's {gate.codes.device}"
+    for attr in ("in_features", "out_features", "bits", "q_format"):
+        if getattr(up, attr) != getattr(gate, attr):
+            return f"up_proj: {attr} {getattr(up, attr)} differs from gate_proj's {getattr(gate, attr)}"
+    if gate.rank > 0 and up.rank > 0:
+        for attr in ("L_bits", "R_bits"):
+            if getattr(up, attr) != getattr(gate, attr):
+                return f"up_proj: {attr} {getattr(up, attr)} differs from gate_proj's {getattr(gate, attr)}"
+    return None
+
+
+class CalderaGatedMLP(torch.nn.Module):
+    """A gated MLP block `down_proj(act(gate_proj(x)) * up_proj(x))` whose gate / up pair runs as one z
+    launch and one code + L launch that applies the activation and the product in its epilogue
+    (cq_linear_glu_forward): no separate activation and product launches, one (T, m) intermediate
+    instead of three, one rounding instead of three.
+
+    gate_proj, up_proj: `CalderaLinear` layers on one device that share in_features, out_features, bits
+    and q_format, and, when both have rank > 0, L_bits and R_bits.  A `HadamardCalderaLinear` does not
+    fit.  ValueError names the attribute.  down_proj: any module.  act: "silu" (the default) or
+    "identity" (a bilinear GLU).  The three layers are submodules under exactly these names, so a state
+    dict of the original MLP loads into this module and back.
+
+    glu(x) -> act(gate_proj(x)) * up_proj(x), shaped (..., out_features) in x's dtype.  The fused launch
+    is taken only where it is the members' own inference launch (`CalderaLinearGroup._grouped`'s
+    conditions): no autograd graph is needed, neither layer has trainable factors, no
+    `dense_prefill_tokens` applies at this token count, and the token count does not exceed
+    `max_fused_tokens` ("auto", the default: `FUSED_TOKEN_LIMIT` for the layers' Q bits, which is where the
+    fused launch was measured slower than the unfused path; None: no limit; or an int).  There x is cast to fp16 and h is computed in x's dtype when that is fp16
+    or fp32, otherwise in fp32 and then cast, as `CalderaLinear.forward` does.  The pre-activations have
+    the bits of the layers' own fp32 outputs; against the unfused formula on fp16 tensors the fused
+    result skips the roundings of gate(x), up(x) and act(gate(x)).  Otherwise glu(x) is the formula
+    through the layers' ordinary forwards (gradients flow; a `CalderaLinearGroup` they belong to still
+    serves them).  The fused path calls the entry on the layers' operands directly: it neither uses nor
+    disturbs a group.
+
+    If the two layers stop fitting after construction (one of them replaced or unpacked), glu(x) takes
+    the formula as well."""
+
+    def __init__(self, gate_proj, up_proj, down_proj, act="silu", max_fused_tokens="auto"):
+        super().__init__()
+        if act not in ACTIVATIONS:
+            raise ValueError(f"CalderaGatedMLP: act {act!r} not in {tuple(ACTIVATIONS)}")
+        why = glu_fit(gate_proj, up_proj)
+        if why is not None:
+            raise ValueError(f"CalderaGatedMLP: {why}")
+        if not isinstance(down_proj, torch.nn.Module):
+            raise ValueError(f"CalderaGatedMLP: down_proj is a {type(down_proj).__name__}, not a module")
+        self.act = act
+        if max_fused_tokens not in ("auto", None) and (isinstance(max_fused_tokens, bool)
+                                                       or not isinstance(max_fused_tokens, int)):
+            raise ValueError(f"CalderaGatedMLP: max_fused_tokens {max_fused_tokens!r} is not \"auto\", None or an int")
+        self.max_fused_tokens = max_fused_tokens
+        self.gate_proj, self.up_proj, self.down_proj = gate_proj, up_proj, down_proj
+
+    def extra_repr(self):
+        return f"act={self.act}"
+
+    def _fused(self, x) -> bool:
+        """Whether the fused launch is the layers' own inference launch for this x."""
+        gate, up = self.gate_proj, self.up_proj
+        if glu_fit(gate, up) is not None:
+            return False
+        if torch.is_grad_enabled() and x.requires_grad:
+            return False
+        T = x.numel() // max(x.shape[-1], 1)
+        limit = FUSED_TOKEN_LIMIT.get(gate.bits) if self.max_fused_tokens == "auto" else self.max_fused_tokens
+        if limit is not None and T > limit:
+            return False
+        return not any(lin.factors_trainable or _use_dense(lin, T) for lin in (gate, up))
+
+    def glu(self, x: torch.Tensor) -> torch.Tensor:
+        gate, up = self.gate_proj, self.up_proj
+        act = ACTIVATIONS[self.act]
+        if not self._fused(x):
+            return _act_torch(act, gate(x)) * up(x)
+        n, m = gate.in_features, gate.out_features
+        if x.shape[-1] != n:
+            raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {n}")
+        x2 = x.reshape(-1, n).to(torch.float16)
+        if x2.stride(1) != 1:
+            x2 = x2.contiguous()
+        hdt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
+        h = torch.empty((x2.shape[0], m), dtype=hdt, device=x.device)
+        K.linear_glu_forward(x2, _group_operands(gate), _group_operands(up), h, gate.q_format, act)
+        return h.to(x.dtype).reshape(*x.shape[:-1], m)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.down_proj(self.glu(x))

@@ -533,3 +533,99 @@ def _dissolve_group_of(mod):
     group = mod.__dict__.get("_group")
     if group is not None:
         group.dissolve()
+
+
+GATED_MLP_NAMES = ("gate_proj", "up_proj", "down_proj", "act_fn")
+
+
+def _recognise_activation(fn):
+    """"silu" for an `nn.SiLU` instance or `torch.nn.functional.silu`, else None."""
+    if isinstance(fn, torch.nn.SiLU) or fn is torch.nn.functional.silu:
+        return "silu"
+    return None
+
+
+def fuse_gated_mlps(model: torch.nn.Module, names=GATED_MLP_NAMES, act=None):
+    """Replace every gated MLP block of `model` by a `linear.CalderaGatedMLP`, whose gate / up pair runs
+    as one launch pair with the activation and the product in its epilogue (cq_linear_glu_forward).
+
+    A block is a module with the three children names[0:3] (gate, up, down) and a recognisable
+    activation: its attribute names[3] is an `nn.SiLU` instance or `torch.nn.functional.silu`, or `act`
+    ("silu" | "identity") is passed explicitly and overrides it.  THE ASSUMPTION: the block's forward
+    computes the standard formula `down(act(gate(x)) * up(x))` and nothing else; this function cannot see
+    the forward's code, so do not fuse a block that does more (dropout, a residual, a different product).
+    A block with further children, parameters or buffers of its own is left alone for that reason.
+
+    The new module holds the three layers under the names gate_proj / up_proj / down_proj (with the
+    default `names` the state dict keys are unchanged, and a state dict saved before loads after and the
+    other way round) and keeps the original block in its `__dict__` (not a submodule) for
+    `unfuse_gated_mlps`.
+
+    Returns (fused, skipped): the dotted names of the replaced blocks, and (name, reason) for every
+    module that has the three children but was left alone -- a dense child, a Hadamard-basis layer, an
+    unknown activation, layers that do not fit the entry, extra state, the model itself, already fused.
+    Nothing raises for them.  `unpack_packed_layers`, `set_dense_prefill`, `prepare_factor_finetuning`
+    and `group_shared_input_layers` work on a fused model: they find the layers by type, and the fused
+    module takes its unfused formula wherever the fused launch is not the layers' own."""
+    from .linear import ACTIVATIONS, CalderaGatedMLP, CalderaLinear, HadamardCalderaLinear, glu_fit
+    if len(names) != 4:
+        raise ValueError(f"fuse_gated_mlps: names {names!r} is not (gate, up, down, activation)")
+    if act is not None and act not in ACTIVATIONS:
+        raise ValueError(f"fuse_gated_mlps: act {act!r} not in {tuple(ACTIVATIONS)}")
+    gate_n, up_n, down_n, act_n = names
+    fused, skipped = [], []
+    for name, mod in list(model.named_modules()):
+        children = [mod._modules.get(n) for n in (gate_n, up_n, down_n)]
+        if any(child is None for child in children):
+            continue
+        label = name or "<model>"
+        if isinstance(mod, CalderaGatedMLP):
+            skipped.append((label, "already fused"))
+            continue
+        gate, up, down = children
+        how = act if act is not None else _recognise_activation(getattr(mod, act_n, None))
+        extra = [n for n in mod._modules if n not in names] + list(mod._parameters) + list(mod._buffers)
+        reason = None
+        for n, child in ((gate_n, gate), (up_n, up)):
+            if isinstance(child, HadamardCalderaLinear):
+                reason = f"{n} is a HadamardCalderaLinear"
+            elif not isinstance(child, CalderaLinear):
+                reason = f"{n} is dense ({type(child).__name__})"
+            if reason:
+                break
+        if reason is None:
+            why = glu_fit(gate, up)
+            if why is not None:
+                reason = f"incompatible: {why}"
+            elif how is None:
+                reason = f"unknown activation {act_n} = {getattr(mod, act_n, None)!r} (pass act=)"
+            elif extra:
+                reason = f"the block has more than the three layers and the activation: {', '.join(extra)}"
+            elif not name:
+                reason = "the model itself is the block (nothing to replace it in)"
+        if reason is not None:
+            skipped.append((label, reason))
+            continue
+        new = CalderaGatedMLP(gate, up, down, act=how)
+        new.__dict__["_original"] = (mod, (gate_n, up_n, down_n))
+        new.train(mod.training)
+        _set_module(model, name, new)
+        fused.append(name)
+    return fused, skipped
+
+
+def unfuse_gated_mlps(model: torch.nn.Module) -> list:
+    """Put back the original block of every `linear.CalderaGatedMLP` that `fuse_gated_mlps` made, with
+    the three layers the fused module holds now (they may have been replaced or unpacked since);
+    returns the dotted names.  A `CalderaGatedMLP` built by hand has no original and stays."""
+    from .linear import CalderaGatedMLP
+    done = []
+    for name, mod in list(model.named_modules()):
+        if not isinstance(mod, CalderaGatedMLP) or "_original" not in mod.__dict__ or not name:
+            continue
+        orig, names = mod.__dict__["_original"]
+        for n, layer in zip(names, (mod.gate_proj, mod.up_proj, mod.down_proj)):
+            setattr(orig, n, layer)
+        _set_module(model, name, orig)
+        done.append(name)
+    return done

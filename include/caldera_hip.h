@@ -867,6 +867,46 @@ typedef struct cq_linear_group_args {
 size_t cq_linear_group_workspace(const cq_linear_group_args* g);
 int cq_linear_group_forward(const cq_linear_group_args* g, void* ws, size_t ws_bytes, void* stream);
 
+/* Gated pair (ABI 5, additive): h = a(gate(x)) * up(x) of a gated MLP block in one z launch and one
+ * code + L launch; neither pre-activation is written to memory.
+ *
+ * Contract:
+ *   - let v_g[t, i] and v_u[t, i] be the fp32 values cq_linear_codebook_forward with q_format computes
+ *     for gate and for up before its output rounding, gs * acc (+ bias): what that entry writes with
+ *     y_dtype = CQ_F32.  This entry computes those same bits.  It holds by construction: a workgroup
+ *     owns the same weight rows of both layers, and each output takes the same loads, MFMAs and
+ *     additions in the same order as it does alone (the factor product continues on the scaled
+ *     accumulator in prefill and is s0 * sk + s1 in decode, as there);
+ *   - h32 = a(v_g) * v_u, one fp32 multiply.  CQ_ACT_IDENTITY: a(v) = v.  CQ_ACT_SILU: e = expf(-v)
+ *     (the device library's, not the fast intrinsic), d = 1.0f + e, a = v / d with the correctly
+ *     rounded fp32 division; nothing is contracted.  h receives h32, at CQ_F16 rounded once to
+ *     nearest even, and is written only at t < tokens, i < m;
+ *   - gate and up share x, ldx, tokens, n, m, bits and q_format, and when both have r > 0 also
+ *     l_bits and r_bits.  A member with r = 0 fits any factor format.  r, the scales, the bias and
+ *     every weight pointer are per member.  y, y_dtype and ldy of both are not used and not checked;
+ *   - each member is checked as the single-layer entries check it, minus the y fields; every
+ *     mismatch, an unknown act or h_dtype, ldh < m and a null or misaligned h are CQ_EINVAL with a
+ *     message naming the member and the field, decided on the host before any launch;
+ *   - workspace: gate's cq_linear_packed_workspace bytes rounded up to 16, then up's (the grouped
+ *     entry's layout for the two members; 16-byte aligned base);
+ *   - tokens == 0 returns CQ_OK without a launch;
+ *   - at most two launches per call: the grouped z product over the members with r > 0 (none:
+ *     skipped), then codes + L + epilogue of both layers;
+ *   - everything else is the single-layer contract: fixed summation order, no float atomics,
+ *     stream-ordered, no allocation, no host-device copy, no synchronisation (graph-capturable). */
+#define CQ_ACT_IDENTITY 0      /* h = g * u  (bilinear GLU) */
+#define CQ_ACT_SILU     1      /* h = g / (1 + exp(-g)) * u */
+
+typedef struct cq_linear_glu_args {
+    cq_linear_packed_args gate, up;   /* y, y_dtype, ldy of both: not used, not checked */
+    int q_format;                     /* CQ_QFMT_UNIFORM | CQ_QFMT_NF, of both */
+    int act;                          /* CQ_ACT_* */
+    void* h; int h_dtype; int64_t ldh;   /* (tokens, m), CQ_F32 | CQ_F16, ldh >= m */
+} cq_linear_glu_args;
+
+size_t cq_linear_glu_workspace(const cq_linear_glu_args* a);
+int cq_linear_glu_forward(const cq_linear_glu_args* a, void* ws, size_t ws_bytes, void* stream);
+
 /* Materialise: the dense weight of a packed layer, for callers that hand long prefill to a dense
  * GEMM from one shared transient buffer, or that want a plain dense layer back.
  *
