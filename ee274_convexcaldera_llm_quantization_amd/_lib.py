@@ -171,6 +171,22 @@ class HadamardArgs(ctypes.Structure):
     ]
 
 
+class HadamardGroupArgs(ctypes.Structure):
+    """cq_hadamard_group_args: `members` points at a host array of `count` cq_hadamard_args."""
+    _fields_ = [("count", ctypes.c_int32), ("members", ctypes.POINTER(HadamardArgs))]
+
+
+class HadamardGluArgs(ctypes.Structure):
+    _fields_ = [
+        ("g", c_vp), ("g_dtype", c_int), ("ldg", c_i64),
+        ("u", c_vp), ("u_dtype", c_int), ("ldu", c_i64),
+        ("h", c_vp), ("h_dtype", c_int), ("ldh", c_i64),
+        ("rows", c_i64), ("n_in", c_i64), ("n_out", c_i64), ("P", c_i64),
+        ("bias_g", c_vp), ("bias_u", c_vp),
+        ("act", c_int),
+    ]
+
+
 _SIGS = {
     "cq_abi_version": (c_int, []),
     "cq_last_error": (ctypes.c_char_p, []),
@@ -267,6 +283,8 @@ _SIGS = {
     "cq_linear_glu_forward": (c_int, [ctypes.POINTER(LinearGluArgs), c_vp, c_size, c_vp]),
     "cq_linear_dequant": (c_int, [ctypes.POINTER(LinearDequantArgs), c_vp]),
     "cq_hadamard_rows": (c_int, [ctypes.POINTER(HadamardArgs), c_vp]),
+    "cq_hadamard_group_rows": (c_int, [ctypes.POINTER(HadamardGroupArgs), c_vp]),
+    "cq_hadamard_glu_rows": (c_int, [ctypes.POINTER(HadamardGluArgs), c_vp]),
     # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
     "cq_gemm_x3_skip": (c_int, [ctypes.POINTER(X3Args), c_vp]),
     "cq_gram_f64_masked": (c_int, [c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_i64,
@@ -1794,9 +1812,10 @@ def _hadamard_need(cond, what):
         raise ValueError(f"cq_hadamard_rows: {what}")
 
 
-def hadamard_args(x, y, *, n_in, n_out, P, bias=None) -> HadamardArgs:
+def hadamard_args(x, y, *, n_in, n_out, P, bias=None, into=None) -> HadamardArgs:
     """cq_hadamard_args for x (rows, n_in) and y (rows, n_out), each fp16 / bf16 / fp32 and
-    possibly a view with a row stride (unit column stride), bias (n_out,) fp32 or None."""
+    possibly a view with a row stride (unit column stride), bias (n_out,) fp32 or None.  into: the
+    (zeroed) struct to fill, e.g. an element of a member array."""
     need = _hadamard_need
     for name, t, cols in (("x", x, n_in), ("y", y, n_out)):
         need(t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1), f"{name} must be a matrix with unit column stride")
@@ -1809,7 +1828,7 @@ def hadamard_args(x, y, *, n_in, n_out, P, bias=None) -> HadamardArgs:
     if bias is not None:
         need(bias.dtype == torch.float32 and tuple(bias.shape) == (n_out,) and bias.is_contiguous(),
              f"bias must be a contiguous fp32 ({n_out},) vector, got {bias.dtype} {tuple(bias.shape)}")
-    a = HadamardArgs()
+    a = HadamardArgs() if into is None else into
     rows = x.shape[0]
     a.x, a.x_dtype, a.ldx = x.data_ptr(), _ACT_DT[x.dtype], (x.stride(0) if rows > 1 else max(x.stride(0), n_in))
     a.y, a.y_dtype, a.ldy = y.data_ptr(), _ACT_DT[y.dtype], (y.stride(0) if rows > 1 else max(y.stride(0), n_out))
@@ -1827,3 +1846,91 @@ def hadamard_rows(x, y, *, n_in, n_out, P, bias=None):
     a = hadamard_args(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias)
     _check(load().cq_hadamard_rows(ctypes.byref(a), _stream(x.device)), "cq_hadamard_rows")
     return y
+
+
+HADAMARD_GROUP_MAX = 8      # include/caldera_hip.h CQ_HADAMARD_GROUP_MAX
+HADAMARD_GLU_MAX_N = 16384  # CQ_HADAMARD_GLU_MAX_N
+
+
+def hadamard_group_args(members) -> HadamardGroupArgs:
+    """cq_hadamard_group_args of 1 .. HADAMARD_GROUP_MAX transforms.  members: one dict per transform with
+    `hadamard_args`' arguments as keys (x, y, n_in, n_out, P and optionally bias).  Each member passes
+    `hadamard_args`' host-side checks; the members must share the row count and P.  The struct keeps
+    the member array alive."""
+    members = list(members)
+    if not 1 <= len(members) <= HADAMARD_GROUP_MAX:
+        raise ValueError(f"cq_hadamard_group_rows: count {len(members)} not in 1 .. {HADAMARD_GROUP_MAX}")
+    arr = (HadamardArgs * len(members))()
+    for i, mem in enumerate(members):
+        try:
+            a = hadamard_args(mem["x"], mem["y"], n_in=mem["n_in"], n_out=mem["n_out"], P=mem["P"],
+                              bias=mem.get("bias"), into=arr[i])
+        except ValueError as e:
+            raise ValueError(f"cq_hadamard_group_rows: member {i}: "
+                             f"{str(e).removeprefix('cq_hadamard_rows: ')}") from None
+        for field in ("rows", "P"):
+            if getattr(a, field) != getattr(arr[0], field):
+                raise ValueError(f"cq_hadamard_group_rows: member {i}: {field} {getattr(a, field)} differs from "
+                                 f"member 0's {getattr(arr[0], field)}")
+    g = HadamardGroupArgs()
+    g.count = len(members)
+    g.members = ctypes.cast(arr, ctypes.POINTER(HadamardArgs))
+    g._members = arr
+    return g
+
+
+def hadamard_group_rows(members):
+    """The transforms `members` (see `hadamard_group_args`) in one launch (cq_hadamard_group_rows): each
+    member's y receives, bit for bit, what `hadamard_rows` writes on the same arguments.  No member's y
+    may overlap an x or another y.  No workspace, no host synchronisation."""
+    members = list(members)
+    for mem in members:
+        _require_hip(mem["x"], mem["y"], mem.get("bias"))
+    g = hadamard_group_args(members)
+    _check(load().cq_hadamard_group_rows(ctypes.byref(g), _stream(members[0]["x"].device)), "cq_hadamard_group_rows")
+    return [mem["y"] for mem in members]
+
+
+def hadamard_glu_args(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=None, act=ACT_SILU) -> HadamardGluArgs:
+    """cq_hadamard_glu_args for g and u (rows, n_in) and h (rows, n_out), each fp16 / bf16 / fp32 and
+    possibly a view with a row stride (unit column stride); bias_g / bias_u (n_out,) fp32 or None."""
+    def need(cond, what):
+        if not cond:
+            raise ValueError(f"cq_hadamard_glu_rows: {what}")
+    need(act in (ACT_IDENTITY, ACT_SILU), f"unknown act {act!r}")
+    for name, t, cols in (("g", g, n_in), ("u", u, n_in), ("h", h, n_out)):
+        need(t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1), f"{name} must be a matrix with unit column stride")
+        need(t.dtype in _ACT_DT, f"{name} must be fp16, bf16 or fp32, got {t.dtype}")
+        need(t.shape[1] == cols, f"{name} {tuple(t.shape)} does not have {cols} columns")
+        need(t.shape[0] == g.shape[0], f"g {tuple(g.shape)} and {name} {tuple(t.shape)} differ in rows")
+    P = int(P)
+    need(1 <= P <= HADAMARD_GLU_MAX_N and P & (P - 1) == 0,
+         f"P = {P} is not a power of two in [1, {HADAMARD_GLU_MAX_N}]")
+    need(1 <= n_in <= P and 0 <= n_out <= P, f"n_in = {n_in} / n_out = {n_out} do not fit P = {P}")
+    for name, b in (("bias_g", bias_g), ("bias_u", bias_u)):
+        if b is not None:
+            need(b.dtype == torch.float32 and tuple(b.shape) == (n_out,) and b.is_contiguous(),
+                 f"{name} must be a contiguous fp32 ({n_out},) vector, got {b.dtype} {tuple(b.shape)}")
+    a = HadamardGluArgs()
+    rows = g.shape[0]
+    a.g, a.g_dtype, a.ldg = g.data_ptr(), _ACT_DT[g.dtype], (g.stride(0) if rows > 1 else max(g.stride(0), n_in))
+    a.u, a.u_dtype, a.ldu = u.data_ptr(), _ACT_DT[u.dtype], (u.stride(0) if rows > 1 else max(u.stride(0), n_in))
+    a.h, a.h_dtype, a.ldh = h.data_ptr(), _ACT_DT[h.dtype], (h.stride(0) if rows > 1 else max(h.stride(0), n_out))
+    a.rows, a.n_in, a.n_out, a.P = rows, n_in, n_out, P
+    if bias_g is not None:
+        a.bias_g = bias_g.data_ptr()
+    if bias_u is not None:
+        a.bias_u = bias_u.data_ptr()
+    a.act = int(act)
+    return a
+
+
+def hadamard_glu_rows(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=None, act=ACT_SILU):
+    """h[t, :n_out] = a(H g[t] / sqrt(P) + bias_g) * (H u[t] / sqrt(P) + bias_u) (cq_hadamard_glu_rows): the
+    two pre-activations have the bits of `hadamard_rows`' fp32 outputs and are never written; a is the
+    identity or silu, h is rounded once.  P <= HADAMARD_GLU_MAX_N.  h must not overlap g or u.  No
+    workspace, no host synchronisation."""
+    _require_hip(g, u, h, bias_g, bias_u)
+    a = hadamard_glu_args(g, u, h, n_in=n_in, n_out=n_out, P=P, bias_g=bias_g, bias_u=bias_u, act=act)
+    _check(load().cq_hadamard_glu_rows(ctypes.byref(a), _stream(g.device)), "cq_hadamard_glu_rows")
+    return h

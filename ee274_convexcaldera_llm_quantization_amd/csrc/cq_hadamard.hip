@@ -29,6 +29,10 @@
 // a function of P alone: its bits do not depend on the other rows, the row count, its index or
 // the strides (the scalar path of an unaligned or cut chunk loads the same values).
 // No atomics, no inline assembly, no workspace.
+//
+// cq_hadamard_group_rows runs up to eight such transforms of the same rows and P in one launch of the
+// same kernels (the member is blockIdx.y), and cq_hadamard_glu_rows two of them -- the rows of gate and
+// of up -- with h = a(v_g) * v_u as the epilogue of kernels of its own built from the same stages.
 #include <cmath>
 
 #include "cq_common.h"
@@ -46,6 +50,23 @@ struct HadP {
     int x_dt, y_dt;
     int x_vec, y_vec, b_vec; // whole chunks may take one aligned vector access
     float c;
+};
+
+// cq_hadamard_group_rows' kernel argument: the members with something to write, by value.  They share
+// rows and P (the template instantiation and the grid's x extent); blockIdx.y is the member.
+struct HadGroupP {
+    HadP m[CQ_HADAMARD_GROUP_MAX];
+};
+__device__ __forceinline__ const HadP& member(const HadP& p) { return p; }
+__device__ __forceinline__ const HadP& member(const HadGroupP& g) {
+    return *reinterpret_cast<const HadP*>(reinterpret_cast<const char*>(g.m) + blockIdx.y * sizeof(HadP));
+}
+
+// cq_hadamard_glu_rows' kernel argument: g and u are the two transforms as cq_hadamard_rows would run
+// them (x = the row of gate resp. up, bias, n_in, c); g's y fields and n_out describe h, u's y is unused.
+struct HadGluP {
+    HadP g, u;
+    int act;
 };
 
 __device__ __forceinline__ float bf16_to_f32(uint32_t h) { return __uint_as_float(h << 16); }
@@ -85,7 +106,59 @@ __device__ __forceinline__ void load4(const HadP& p, const char* row, int i0, fl
     for (int k = 0; k < 4; ++k) v[k] = (i0 + k < p.n_in) ? load1(row, p.x_dt, i0 + k) : 0.0f;
 }
 
-// c * v (+ bias) rounded once to y's type; columns >= n_out are not written
+// o = c * v (+ bias) for the columns [i0, i0 + 4), i0 < n_out: the fp32 values before the output rounding
+__device__ __forceinline__ void scaled4(const HadP& p, int i0, const float* v, float* o) {
+    const bool full = i0 + 4 <= p.n_out;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = v[k] * p.c;
+    if (p.bias != nullptr) {
+        if (full && p.b_vec) {
+            const float4 b = *reinterpret_cast<const float4*>(p.bias + i0);
+            o[0] += b.x, o[1] += b.y, o[2] += b.z, o[3] += b.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (i0 + k < p.n_out) o[k] += p.bias[i0 + k];
+        }
+    }
+}
+
+// o rounded once to y's type into the columns [i0, i0 + 4), i0 < n_out; columns >= n_out are not written
+__device__ __forceinline__ void write4(const HadP& p, char* row, int i0, const float* o) {
+    const bool full = i0 + 4 <= p.n_out;
+    if (p.y_dt == CQ_F32) {
+        float* y = reinterpret_cast<float*>(row) + i0;
+        if (full && p.y_vec) {
+            *reinterpret_cast<float4*>(y) = make_float4(o[0], o[1], o[2], o[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (i0 + k < p.n_out) y[k] = o[k];
+        }
+        return;
+    }
+    uint16_t h[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (p.y_dt == CQ_F16) {
+            const _Float16 f = (_Float16)o[k];
+            h[k] = *reinterpret_cast<const uint16_t*>(&f);
+        } else {
+            h[k] = f32_to_bf16(o[k]);
+        }
+    }
+    uint16_t* y = reinterpret_cast<uint16_t*>(row) + i0;
+    if (full && p.y_vec) {
+        *reinterpret_cast<uint2*>(y) = make_uint2(h[0] | (uint32_t)h[1] << 16, h[2] | (uint32_t)h[3] << 16);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i0 + k < p.n_out) y[k] = h[k];
+    }
+}
+
+// c * v (+ bias) rounded once to y's type; columns >= n_out are not written.  scaled4 then write4 in one
+// text: calling the two changed the existing kernels' registers (179 -> 193 VGPRs at P = 2048), DESIGN 9.9
 __device__ __forceinline__ void store4(const HadP& p, char* row, int i0, const float* v) {
     if (i0 >= p.n_out) return;
     const bool full = i0 + 4 <= p.n_out;
@@ -131,6 +204,27 @@ __device__ __forceinline__ void store4(const HadP& p, char* row, int i0, const f
         for (int k = 0; k < 4; ++k)
             if (i0 + k < p.n_out) y[k] = h[k];
     }
+}
+
+// h = a(v_g) * v_u of the columns [i0, i0 + 4): v_g and v_u are store4's fp32 values of the two
+// transforms (scaled4 on each), a is the identity or e = expf(-v), d = 1 + e, v / d (the file is built
+// without contraction and with the correctly rounded division); one multiply, one rounding to h's type
+__device__ __forceinline__ void glu_store4(const HadGluP& a, char* hrow, int i0, const float* vg, const float* vu) {
+    if (i0 >= a.g.n_out) return;
+    float og[4], ou[4], h[4];
+    scaled4(a.g, i0, vg, og);
+    scaled4(a.u, i0, vu, ou);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float act = og[k];
+        if (a.act == CQ_ACT_SILU) {
+            const float e = expf(-og[k]);
+            const float d = 1.0f + e;
+            act = og[k] / d;
+        }
+        h[k] = act * ou[k];
+    }
+    write4(a.g, hrow, i0, h);
 }
 
 // butterflies over bit `bit` of the register (chunk) index, on all four elements of a chunk
@@ -180,8 +274,14 @@ constexpr int ilog2(int x) { return x <= 1 ? 0 : 1 + ilog2(x / 2); }
 
 // Rows of up to 2048 values: CH chunks of four elements per lane, a team of 2^lg_tl lanes per
 // row, 256 >> lg_tl rows per workgroup (CH > 1 only with a whole wave per row).  No LDS.
-template <int CH>
-__global__ __launch_bounds__(256) void hadamard_wave_kernel(const HadP p) {
+//
+// ARG (both kernels): HadP, the kernel argument is the transform's parameters themselves
+// (cq_hadamard_rows); HadGroupP (cq_hadamard_group_rows), the grid's y extent is the member count and a
+// workgroup runs on member blockIdx.y's parameters, at its own place blockIdx.x in that member's grid:
+// the same body, hence the same work in the same order as alone.
+template <int CH, typename ARG>
+__global__ __launch_bounds__(256) void hadamard_wave_kernel(const ARG arg) {
+    const HadP& p = member(arg);
     constexpr int kQBits = ilog2(CH);
     const int tid = threadIdx.x, lane = tid & 63;
     const int lg = CH == 1 ? p.lg_tl : 6;   // lane bits of a row's chunk index
@@ -221,8 +321,9 @@ __global__ __launch_bounds__(256) void hadamard_wave_kernel(const HadP p) {
 // stores do not fit without scratch: two teams)
 constexpr int block_teams(int G) { return G == 8 ? 2 : G; }
 
-template <int G>
-__global__ __launch_bounds__(256 * block_teams(G)) void hadamard_block_kernel(const HadP p) {
+template <int G, typename ARG>
+__global__ __launch_bounds__(256 * block_teams(G)) void hadamard_block_kernel(const ARG arg) {
+    const HadP& p = member(arg);
     constexpr int kTeams = block_teams(G), kThreads = 256 * kTeams;
     __shared__ float4 rowbuf[G * 1024];
     const int tid = threadIdx.x & 255, lane = tid & 63, w = tid >> 6, team = threadIdx.x >> 8;
@@ -279,19 +380,162 @@ __global__ __launch_bounds__(256 * block_teams(G)) void hadamard_block_kernel(co
     }
 }
 
+// cq_hadamard_glu_rows, rows of up to 2048 values: hadamard_wave_kernel's stages run twice, on the row
+// of gate and on the row of up, into two register sets; the epilogue takes both.
+template <int CH>
+__global__ __launch_bounds__(256) void hadamard_wave_glu_kernel(const HadGluP a) {
+    constexpr int kQBits = ilog2(CH);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int lg = CH == 1 ? a.g.lg_tl : 6;
+    const int cbase = tid & ((1 << lg) - 1);
+    const int64_t rows_per_wg = 256 >> lg;
+    const size_t ges = a.g.x_dt == CQ_F32 ? 4 : 2, ues = a.u.x_dt == CQ_F32 ? 4 : 2, hes = a.g.y_dt == CQ_F32 ? 4 : 2;
+
+    for (int64_t row = (int64_t)blockIdx.x * rows_per_wg + (tid >> lg); row < a.g.rows;
+         row += (int64_t)gridDim.x * rows_per_wg) {
+        const char* grow = a.g.x + (size_t)row * (size_t)a.g.ldx * ges;
+        const char* urow = a.u.x + (size_t)row * (size_t)a.u.ldx * ues;
+        char* hrow = a.g.y + (size_t)row * (size_t)a.g.ldy * hes;
+        float vg[CH * 4], vu[CH * 4];
+#pragma unroll
+        for (int q = 0; q < CH; ++q) load4(a.g, grow, (cbase | (q << lg)) * 4, &vg[q * 4]);
+        chunk_stage<CH>(vg);
+        lane_stages<CH>(vg, lane, lg);
+#pragma unroll
+        for (int b = 0; b < kQBits; ++b) reg_stage<CH>(vg, b);
+#pragma unroll
+        for (int q = 0; q < CH; ++q) load4(a.u, urow, (cbase | (q << lg)) * 4, &vu[q * 4]);
+        chunk_stage<CH>(vu);
+        lane_stages<CH>(vu, lane, lg);
+#pragma unroll
+        for (int b = 0; b < kQBits; ++b) reg_stage<CH>(vu, b);
+#pragma unroll
+        for (int q = 0; q < CH; ++q) glu_store4(a, hrow, (cbase | (q << lg)) * 4, &vg[q * 4], &vu[q * 4]);
+    }
+}
+
+// cq_hadamard_glu_rows, rows of P = 4096 G values, G in {1, 2, 4}: hadamard_block_kernel's stage A on
+// the row of gate and then on the row of up, each into its own row buffer (2 x 16 KB G of static LDS,
+// 128 KB at P = 16384; P = 32768 would need 256 KB and is refused on the host), then stage B on both:
+// a lane reads chunk c of every sub-row of both buffers, finishes the log2 G bits of each in registers
+// and writes h.  G = 1 goes through the buffers too (stage B is then the epilogue alone).
+// (P = 16384 at four teams caps a lane at 128 registers, which stage B's 2 x 16 values, the two epilogues
+// and the stores do not fit without scratch: two teams, as hadamard_block_kernel has at P = 32768)
+constexpr int glu_teams(int G) { return G == 4 ? 2 : G; }
+
+template <int G>
+__global__ __launch_bounds__(256 * glu_teams(G)) void hadamard_block_glu_kernel(const HadGluP a) {
+    static_assert(G == 1 || G == 2 || G == 4, "two row buffers of 16 KB G must fit the CU's LDS");
+    constexpr int kTeams = glu_teams(G), kThreads = 256 * kTeams;
+    __shared__ float4 rowbuf[2 * G * 1024];
+    const int tid = threadIdx.x & 255, lane = tid & 63, w = tid >> 6, team = threadIdx.x >> 8;
+    const size_t hes = a.g.y_dt == CQ_F32 ? 4 : 2;
+
+    for (int64_t row = blockIdx.x; row < a.g.rows; row += gridDim.x) {
+        char* hrow = a.g.y + (size_t)row * (size_t)a.g.ldy * hes;
+#pragma unroll 1
+        for (int sg = team; sg < 2 * G; sg += kTeams) {  // gate's sub-rows, then up's: 2 G / kTeams passes for
+            const int s = sg >= G, g = sg - s * G;       // every team, so the barrier is uniform
+            const HadP& p = s ? a.u : a.g;
+            const char* xrow = p.x + (size_t)row * (size_t)p.ldx * (p.x_dt == CQ_F32 ? 4 : 2);
+            float4* buf = rowbuf + sg * 1024;
+            float v[16];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) load4(p, xrow, (g * 1024 + (tid | (q << 8))) * 4, &v[q * 4]);
+            chunk_stage<4>(v);
+            lane_stages<4>(v, lane, 6);
+            reg_stage<4>(v, 0);
+            reg_stage<4>(v, 1);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                buf[lane + 64 * (w + 4 * q)] = make_float4(v[q * 4], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3]);
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float4 f = buf[lane + 64 * (u + 4 * w)];
+                v[u * 4] = f.x, v[u * 4 + 1] = f.y, v[u * 4 + 2] = f.z, v[u * 4 + 3] = f.w;
+            }
+            reg_stage<4>(v, 0);
+            reg_stage<4>(v, 1);
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                buf[lane + 64 * (u + 4 * w)] = make_float4(v[u * 4], v[u * 4 + 1], v[u * 4 + 2], v[u * 4 + 3]);
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int c = threadIdx.x; c < 1024; c += kThreads) {
+            float vg[G * 4], vu[G * 4];
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const float4 f = rowbuf[g * 1024 + c];
+                vg[g * 4] = f.x, vg[g * 4 + 1] = f.y, vg[g * 4 + 2] = f.z, vg[g * 4 + 3] = f.w;
+                const float4 e = rowbuf[(G + g) * 1024 + c];
+                vu[g * 4] = e.x, vu[g * 4 + 1] = e.y, vu[g * 4 + 2] = e.z, vu[g * 4 + 3] = e.w;
+            }
+#pragma unroll
+            for (int b = 0; b < ilog2(G); ++b) {
+                reg_stage<G>(vg, b);
+                reg_stage<G>(vu, b);
+            }
+#pragma unroll
+            for (int g = 0; g < G; ++g) glu_store4(a, hrow, (g * 1024 + c) * 4, &vg[g * 4], &vu[g * 4]);
+        }
+        __syncthreads();  // the next row's exchange writes the buffers again
+    }
+}
+
 constexpr int64_t kMaxGridRows = (int64_t)1 << 20;  // more rows take the grid-stride loop
 
+// ny: the grid's y extent (1 for HadP, the member count for HadGroupP)
+template <int CH, typename ARG>
+void launch_wave(const ARG& arg, int64_t rows, int lg_tl, unsigned ny, hipStream_t s) {
+    const int64_t wgs = ceil_div(rows, (int64_t)(256 >> lg_tl));
+    hipLaunchKernelGGL((hadamard_wave_kernel<CH, ARG>), dim3((unsigned)(wgs < kMaxGridRows ? wgs : kMaxGridRows), ny),
+                       dim3(256), 0, s, arg);
+}
+
+template <int G, typename ARG>
+void launch_block(const ARG& arg, int64_t rows, unsigned ny, hipStream_t s) {
+    hipLaunchKernelGGL((hadamard_block_kernel<G, ARG>), dim3((unsigned)(rows < kMaxGridRows ? rows : kMaxGridRows), ny),
+                       dim3(256 * block_teams(G)), 0, s, arg);
+}
+
+// lg: log2 of the row's chunks of four (0 for P <= 4)
+int log2_chunks(int64_t P) {
+    // P < 4 runs as one chunk: the pad columns are zero, and adding zero changes no sum
+    const int64_t chunks = P < 4 ? 1 : P / 4;
+    int lg = 0;
+    while (((int64_t)1 << lg) < chunks) ++lg;
+    return lg;
+}
+
+template <typename ARG>
+void launch_rows(const ARG& arg, int64_t rows, int lg, unsigned ny, hipStream_t s) {
+    const int lg_tl = lg < 6 ? lg : 6;
+    switch (lg) {
+        case 7: launch_wave<2>(arg, rows, lg_tl, ny, s); break;   // P = 512
+        case 8: launch_wave<4>(arg, rows, lg_tl, ny, s); break;   // 1024
+        case 9: launch_wave<8>(arg, rows, lg_tl, ny, s); break;   // 2048
+        case 10: launch_block<1>(arg, rows, ny, s); break;        // 4096
+        case 11: launch_block<2>(arg, rows, ny, s); break;        // 8192
+        case 12: launch_block<4>(arg, rows, ny, s); break;        // 16384
+        case 13: launch_block<8>(arg, rows, ny, s); break;        // 32768
+        default: launch_wave<1>(arg, rows, lg_tl, ny, s); break;  // P <= 256: 2^lg lanes per row
+    }
+}
+
 template <int CH>
-void launch_wave(const HadP& p, hipStream_t s) {
-    const int64_t wgs = ceil_div(p.rows, (int64_t)(256 >> p.lg_tl));
-    hipLaunchKernelGGL((hadamard_wave_kernel<CH>), dim3((unsigned)(wgs < kMaxGridRows ? wgs : kMaxGridRows)),
-                       dim3(256), 0, s, p);
+void launch_wave_glu(const HadGluP& a, hipStream_t s) {
+    const int64_t wgs = ceil_div(a.g.rows, (int64_t)(256 >> a.g.lg_tl));
+    hipLaunchKernelGGL((hadamard_wave_glu_kernel<CH>), dim3((unsigned)(wgs < kMaxGridRows ? wgs : kMaxGridRows)),
+                       dim3(256), 0, s, a);
 }
 
 template <int G>
-void launch_block(const HadP& p, hipStream_t s) {
-    hipLaunchKernelGGL((hadamard_block_kernel<G>), dim3((unsigned)(p.rows < kMaxGridRows ? p.rows : kMaxGridRows)),
-                       dim3(256 * block_teams(G)), 0, s, p);
+void launch_block_glu(const HadGluP& a, hipStream_t s) {
+    hipLaunchKernelGGL((hadamard_block_glu_kernel<G>),
+                       dim3((unsigned)(a.g.rows < kMaxGridRows ? a.g.rows : kMaxGridRows)), dim3(256 * glu_teams(G)), 0, s,
+                       a);
 }
 
 bool dtype_ok(int dt) { return dt == CQ_F32 || dt == CQ_F16 || dt == CQ_BF16; }
@@ -303,34 +547,38 @@ bool vec_ok(const void* ptr, int64_t ld, size_t es) {
     return (reinterpret_cast<uintptr_t>(ptr) % (4 * es)) == 0 && ((size_t)ld * es) % (4 * es) == 0;
 }
 
-}  // namespace
-}  // namespace cq
+// what a transform's fields are called in the caller's struct (the messages name them)
+struct Names {
+    const char *x, *y, *ldx, *ldy, *bias;
+};
+constexpr Names kRowsNames{"x", "y", "ldx", "ldy", "bias"};
 
-using namespace cq;
-
-extern "C" int cq_hadamard_rows(const cq_hadamard_args* a, void* stream) {
-    CQ_REQUIRE(a != nullptr, "cq_hadamard_rows: null args");
-    CQ_REQUIRE(a->P >= 1 && a->P <= CQ_HADAMARD_MAX_N && (a->P & (a->P - 1)) == 0,
-               "cq_hadamard_rows: P = %lld is not a power of two in [1, %d]", (long long)a->P, CQ_HADAMARD_MAX_N);
-    CQ_REQUIRE(a->n_in >= 1 && a->n_in <= a->P, "cq_hadamard_rows: n_in = %lld is not in [1, P = %lld]",
-               (long long)a->n_in, (long long)a->P);
-    CQ_REQUIRE(a->n_out >= 0 && a->n_out <= a->P, "cq_hadamard_rows: n_out = %lld is not in [0, P = %lld]",
+// cq_hadamard_rows' checks of one transform; `who` names the entry (and the member) in the message, `nm`
+// the fields, max_P the entry's largest transform
+int validate(const cq_hadamard_args* a, const char* who, const Names& nm = kRowsNames, int max_P = CQ_HADAMARD_MAX_N) {
+    CQ_REQUIRE(a->P >= 1 && a->P <= max_P && (a->P & (a->P - 1)) == 0,
+               "%s: P = %lld is not a power of two in [1, %d]", who, (long long)a->P, max_P);
+    CQ_REQUIRE(a->n_in >= 1 && a->n_in <= a->P, "%s: n_in = %lld is not in [1, P = %lld]", who, (long long)a->n_in,
+               (long long)a->P);
+    CQ_REQUIRE(a->n_out >= 0 && a->n_out <= a->P, "%s: n_out = %lld is not in [0, P = %lld]", who,
                (long long)a->n_out, (long long)a->P);
-    CQ_REQUIRE(a->rows >= 0, "cq_hadamard_rows: rows = %lld is negative", (long long)a->rows);
-    CQ_REQUIRE(dtype_ok(a->x_dtype), "cq_hadamard_rows: unknown x dtype %d (fp32 | fp16 | bf16)", a->x_dtype);
-    CQ_REQUIRE(dtype_ok(a->y_dtype), "cq_hadamard_rows: unknown y dtype %d (fp32 | fp16 | bf16)", a->y_dtype);
-    CQ_REQUIRE(reinterpret_cast<uintptr_t>(a->x) % esize(a->x_dtype) == 0,
-               "cq_hadamard_rows: x is not aligned to its %s element", dtype_name(a->x_dtype));
-    CQ_REQUIRE(reinterpret_cast<uintptr_t>(a->y) % esize(a->y_dtype) == 0,
-               "cq_hadamard_rows: y is not aligned to its %s element", dtype_name(a->y_dtype));
+    CQ_REQUIRE(a->rows >= 0, "%s: rows = %lld is negative", who, (long long)a->rows);
+    CQ_REQUIRE(dtype_ok(a->x_dtype), "%s: unknown %s dtype %d (fp32 | fp16 | bf16)", who, nm.x, a->x_dtype);
+    CQ_REQUIRE(dtype_ok(a->y_dtype), "%s: unknown %s dtype %d (fp32 | fp16 | bf16)", who, nm.y, a->y_dtype);
+    CQ_REQUIRE(reinterpret_cast<uintptr_t>(a->x) % esize(a->x_dtype) == 0, "%s: %s is not aligned to its %s element",
+               who, nm.x, dtype_name(a->x_dtype));
+    CQ_REQUIRE(reinterpret_cast<uintptr_t>(a->y) % esize(a->y_dtype) == 0, "%s: %s is not aligned to its %s element",
+               who, nm.y, dtype_name(a->y_dtype));
     CQ_REQUIRE(reinterpret_cast<uintptr_t>(a->bias) % sizeof(float) == 0,
-               "cq_hadamard_rows: bias is not aligned to its fp32 element");
+               "%s: %s is not aligned to its fp32 element", who, nm.bias);
     CQ_REQUIRE(a->ldx >= a->n_in && a->ldy >= a->n_out,
-               "cq_hadamard_rows: leading dimension smaller than the row (ldx %lld < n_in %lld or ldy %lld < n_out "
-               "%lld)", (long long)a->ldx, (long long)a->n_in, (long long)a->ldy, (long long)a->n_out);
-    if (a->rows == 0 || a->n_out == 0) return CQ_OK;
-    CQ_REQUIRE(a->x != nullptr && a->y != nullptr, "cq_hadamard_rows: null x or y");
+               "%s: leading dimension smaller than the row (%s %lld < n_in %lld or %s %lld < n_out %lld)", who, nm.ldx,
+               (long long)a->ldx, (long long)a->n_in, nm.ldy, (long long)a->ldy, (long long)a->n_out);
+    return CQ_OK;
+}
 
+// the kernels' parameters of one validated transform with rows > 0 and n_out > 0
+HadP params(const cq_hadamard_args* a) {
     HadP p{};
     p.x = reinterpret_cast<const char*>(a->x);
     p.y = reinterpret_cast<char*>(a->y);
@@ -342,21 +590,80 @@ extern "C" int cq_hadamard_rows(const cq_hadamard_args* a, void* stream) {
     p.y_vec = vec_ok(a->y, a->ldy, esize(a->y_dtype));
     p.b_vec = reinterpret_cast<uintptr_t>(a->bias) % 16 == 0;
     p.c = (float)(1.0 / std::sqrt((double)a->P));
-    // P < 4 runs as one chunk: the pad columns are zero, and adding zero changes no sum
-    const int64_t chunks = a->P < 4 ? 1 : a->P / 4;
-    int lg = 0;
-    while (((int64_t)1 << lg) < chunks) ++lg;
+    const int lg = log2_chunks(a->P);
     p.lg_tl = lg < 6 ? lg : 6;
-    hipStream_t s = as_stream(stream);
-    switch (lg) {
-        case 7: launch_wave<2>(p, s); break;         // P = 512
-        case 8: launch_wave<4>(p, s); break;         // 1024
-        case 9: launch_wave<8>(p, s); break;         // 2048
-        case 10: launch_block<1>(p, s); break;       // 4096
-        case 11: launch_block<2>(p, s); break;       // 8192
-        case 12: launch_block<4>(p, s); break;       // 16384
-        case 13: launch_block<8>(p, s); break;       // 32768
-        default: launch_wave<1>(p, s); break;        // P <= 256: 2^lg lanes per row
-    }
+    return p;
+}
+
+}  // namespace
+}  // namespace cq
+
+using namespace cq;
+
+extern "C" int cq_hadamard_rows(const cq_hadamard_args* a, void* stream) {
+    CQ_REQUIRE(a != nullptr, "cq_hadamard_rows: null args");
+    if (const int st = validate(a, "cq_hadamard_rows")) return st;
+    if (a->rows == 0 || a->n_out == 0) return CQ_OK;
+    CQ_REQUIRE(a->x != nullptr && a->y != nullptr, "cq_hadamard_rows: null x or y");
+    launch_rows(params(a), a->rows, log2_chunks(a->P), 1, as_stream(stream));
     return check_launch("cq_hadamard_rows");
+}
+
+extern "C" int cq_hadamard_group_rows(const cq_hadamard_group_args* g, void* stream) {
+    static const char* kWho = "cq_hadamard_group_rows";
+    CQ_REQUIRE(g != nullptr, "%s: null args", kWho);
+    CQ_REQUIRE(g->count >= 1 && g->count <= CQ_HADAMARD_GROUP_MAX, "%s: count = %d is not in [1, %d]", kWho,
+               (int)g->count, CQ_HADAMARD_GROUP_MAX);
+    CQ_REQUIRE(g->members != nullptr, "%s: null members", kWho);
+    const cq_hadamard_args* m0 = &g->members[0];
+    char who[64];
+    for (int i = 0; i < g->count; ++i) {
+        const cq_hadamard_args* m = &g->members[i];
+        snprintf(who, sizeof who, "%s: member %d", kWho, i);
+        if (const int st = validate(m, who)) return st;
+        CQ_REQUIRE(m->rows == m0->rows, "%s: rows = %lld differs from member 0's %lld", who, (long long)m->rows,
+                   (long long)m0->rows);
+        CQ_REQUIRE(m->P == m0->P, "%s: P = %lld differs from member 0's %lld", who, (long long)m->P, (long long)m0->P);
+    }
+    if (m0->rows == 0) return CQ_OK;
+    HadGroupP arg{};
+    unsigned ny = 0;
+    for (int i = 0; i < g->count; ++i) {
+        const cq_hadamard_args* m = &g->members[i];
+        if (m->n_out == 0) continue;  // nothing to write: the member takes no part in the grid
+        CQ_REQUIRE(m->x != nullptr && m->y != nullptr, "%s: member %d: null x or y", kWho, i);
+        arg.m[ny++] = params(m);
+    }
+    if (ny == 0) return CQ_OK;
+    launch_rows(arg, m0->rows, log2_chunks(m0->P), ny, as_stream(stream));
+    return check_launch(kWho);
+}
+
+extern "C" int cq_hadamard_glu_rows(const cq_hadamard_glu_args* a, void* stream) {
+    static const char* kWho = "cq_hadamard_glu_rows";
+    CQ_REQUIRE(a != nullptr, "%s: null args", kWho);
+    CQ_REQUIRE(a->act == CQ_ACT_IDENTITY || a->act == CQ_ACT_SILU, "%s: unknown act %d", kWho, a->act);
+    // the two transforms as cq_hadamard_rows' arguments, h standing for y in both: the single entry's checks
+    // on each, with the fields under this struct's names
+    const cq_hadamard_args ga{a->g, a->g_dtype, a->ldg, a->h, a->h_dtype, a->ldh, a->rows, a->n_in, a->n_out, a->P,
+                              a->bias_g};
+    const cq_hadamard_args ua{a->u, a->u_dtype, a->ldu, a->h, a->h_dtype, a->ldh, a->rows, a->n_in, a->n_out, a->P,
+                              a->bias_u};
+    if (const int st = validate(&ga, kWho, Names{"g", "h", "ldg", "ldh", "bias_g"}, CQ_HADAMARD_GLU_MAX_N)) return st;
+    if (const int st = validate(&ua, kWho, Names{"u", "h", "ldu", "ldh", "bias_u"}, CQ_HADAMARD_GLU_MAX_N)) return st;
+    if (a->rows == 0 || a->n_out == 0) return CQ_OK;
+    CQ_REQUIRE(a->g != nullptr && a->u != nullptr && a->h != nullptr, "%s: null g, u or h", kWho);
+    HadGluP p{};
+    p.g = params(&ga), p.u = params(&ua), p.act = a->act;
+    hipStream_t s = as_stream(stream);
+    switch (log2_chunks(a->P)) {
+        case 7: launch_wave_glu<2>(p, s); break;     // P = 512
+        case 8: launch_wave_glu<4>(p, s); break;     // 1024
+        case 9: launch_wave_glu<8>(p, s); break;     // 2048
+        case 10: launch_block_glu<1>(p, s); break;   // 4096
+        case 11: launch_block_glu<2>(p, s); break;   // 8192
+        case 12: launch_block_glu<4>(p, s); break;   // 16384
+        default: launch_wave_glu<1>(p, s); break;    // P <= 256
+    }
+    return check_launch(kWho);
 }

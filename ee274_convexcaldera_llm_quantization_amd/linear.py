@@ -881,22 +881,29 @@ class HadamardCalderaLinear(torch.nn.Module):
         """The three launch groups on x: (x2, x^, y) with x2 the (T, in_features) view they read, x^
         the fp16 (T, pc) transform the inner layer takes and y (T, out_features) in x2's dtype.
         L16 / R16: the inner layer's fp16 factors when they are not its buffers."""
-        pr, pc = self.padded_shape
-        x2 = x.reshape(-1, self.in_features)
-        if x2.dtype not in (torch.float16, torch.bfloat16, torch.float32):
-            x2 = x2.float()
-        if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < self.in_features):
-            x2 = x2.contiguous()
+        pr = self.padded_shape[0]
+        x2, xh = _hadamard_input(self, x)
         T = x2.shape[0]
-        xh = torch.empty((T, pc), dtype=torch.float16, device=x.device)
-        K.hadamard_rows(x2, xh, n_in=self.in_features, n_out=pc, P=pc)
         y32 = torch.empty((T, pr), dtype=torch.float32, device=x.device)
         _launch_packed(self.inner, xh, y32, L16, R16)
         y = torch.empty((T, self.out_features), dtype=x2.dtype, device=x.device)
         K.hadamard_rows(y32, y, n_in=pr, n_out=self.out_features, P=pr, bias=self.bias)
         return x2, xh, y
 
+    @property
+    def group(self):
+        """The `HadamardLinearGroup` this layer is a member of, or None.  A plain attribute kept in
+        `__dict__`: no buffer, no state, not a submodule."""
+        return self.__dict__.get("_group")
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        group = self.__dict__.get("_group")
+        if group is not None:  # a member of a HadamardLinearGroup: the set's four launches
+            return group._member_forward(self, x)
+        return self._forward_alone(x)
+
+    def _forward_alone(self, x: torch.Tensor) -> torch.Tensor:
+        """The layer's own launches, whether it is in a group or not."""
         if not x.is_cuda or not self.inner.codes.is_cuda:
             raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
         if x.shape[-1] != self.in_features:
@@ -924,7 +931,62 @@ def _group_operands(lin):
                 R_codes=(lin.R_codes, lin.rscale, lin.R_bits) if ranked and lin.R_codes is not None else None)
 
 
-class CalderaLinearGroup:
+class _SharedInputGroup:
+    """The protocol `CalderaLinearGroup` and `HadamardLinearGroup` share: a plain object over layers that
+    read the same activation; each member keeps a back-reference in its `__dict__["_group"]` and calls
+    `_member_forward` from its `forward`.  A subclass validates its members and then `_adopt`s them, and
+    provides `_grouped(x)` (whether the grouped launch is the members' own inference launch for x) and
+    `_launch(x)` (the grouped launches: the members' outputs in member order).  Members provide
+    `_forward_alone(x)`."""
+
+    def _adopt(self, members):
+        self.members = tuple(members)
+        self._key = None    # (weakref of x, x._version, x.data_ptr()) of the kept outputs
+        self._kept = {}     # id(member) -> its output for that x, until claimed
+        for lin in self.members:
+            lin.__dict__["_group"] = self
+
+    def __len__(self):
+        return len(self.members)
+
+    def __getstate__(self):  # a weak reference does not pickle; the kept outputs are transient
+        return {"members": self.members, "_key": None, "_kept": {}}
+
+    def dissolve(self):
+        """Remove the members' back-references: every layer runs alone again."""
+        for lin in self.members:
+            if lin.__dict__.get("_group") is self:
+                del lin.__dict__["_group"]
+        self._key, self._kept = None, {}
+
+    def __call__(self, x: torch.Tensor):
+        self._key, self._kept = None, {}
+        if not self._grouped(x):
+            return tuple(lin._forward_alone(x) for lin in self.members)
+        return self._launch(x)
+
+    def _member_forward(self, member, x):
+        """`member.forward(x)` of a grouped layer, see `CalderaLinearGroup`'s docstring."""
+        if member not in self.members:
+            # a shallow copy of a member (e.g. a DataParallel replica) still points here: it is not ours
+            return member._forward_alone(x)
+        if x.is_inference() or not self._grouped(x):
+            # an inference tensor has no version counter: a write in place could not be told from the
+            # x the kept outputs belong to, so none are kept for it
+            self._key, self._kept = None, {}
+            return member._forward_alone(x)
+        key = self._key
+        if (key is not None and key[0]() is x and key[1] == x._version and key[2] == x.data_ptr()
+                and id(member) in self._kept):
+            return self._kept.pop(id(member))
+        self._key, self._kept = None, {}   # another x (or a second call with this one): start over
+        ys = self._launch(x)
+        self._kept = {id(lin): y for lin, y in zip(self.members, ys) if lin is not member}
+        self._key = (weakref.ref(x), x._version, x.data_ptr())
+        return ys[self.members.index(member)]
+
+
+class CalderaLinearGroup(_SharedInputGroup):
     """Packed layers that read the same activation (q / k / v, gate / up), run as one z launch and
     one code + L launch (cq_linear_group_forward) instead of two launches each; every member's output
     has the bits the member computes alone.  A plain object, not a module: the members stay where they
@@ -933,7 +995,8 @@ class CalderaLinearGroup:
 
     members: 1 .. `_lib.LINEAR_GROUP_MAX` `CalderaLinear` layers on one device that share
     in_features, bits and q_format, and, among those with rank > 0, L_bits and R_bits; none of them in
-    another group.  `HadamardCalderaLinear` cannot be grouped (its transforms are per layer).
+    another group.  A `HadamardCalderaLinear` is refused (its transforms are per layer): sets of those form a
+    `HadamardLinearGroup`.
     ValueError names the member and the attribute.
 
     group(x) -> the members' outputs in member order, each shaped and typed as member(x).
@@ -964,7 +1027,7 @@ class CalderaLinearGroup:
         members = list(members)
         if not 1 <= len(members) <= K.LINEAR_GROUP_MAX:
             raise ValueError(f"CalderaLinearGroup: {len(members)} members, not 1 .. {K.LINEAR_GROUP_MAX}")
-        first = ranked = None
+        first = None
         for i, lin in enumerate(members):
             if isinstance(lin, HadamardCalderaLinear):
                 raise ValueError(f"CalderaLinearGroup: member {i} is a HadamardCalderaLinear: its input and output "
@@ -980,35 +1043,13 @@ class CalderaLinearGroup:
             if lin.codes.device != first.codes.device:
                 raise ValueError(f"CalderaLinearGroup: member {i}: device {lin.codes.device} differs from member 0's "
                                  f"{first.codes.device}")
-            for attr in ("in_features", "bits", "q_format"):
-                if getattr(lin, attr) != getattr(first, attr):
-                    raise ValueError(f"CalderaLinearGroup: member {i}: {attr} {getattr(lin, attr)} differs from "
-                                     f"member 0's {getattr(first, attr)}")
-            if lin.rank > 0:
-                if ranked is None:
-                    ranked = i
-                for attr in ("L_bits", "R_bits"):
-                    if getattr(lin, attr) != getattr(members[ranked], attr):
-                        raise ValueError(f"CalderaLinearGroup: member {i}: {attr} {getattr(lin, attr)} differs from "
-                                         f"member {ranked}'s {getattr(members[ranked], attr)}")
-        self.members = tuple(members)
-        self._key = None    # (weakref of x, x._version, x.data_ptr()) of the kept outputs
-        self._kept = {}     # id(member) -> its output for that x, until claimed
-        for lin in self.members:
-            lin.__dict__["_group"] = self
-
-    def __len__(self):
-        return len(self.members)
-
-    def __getstate__(self):  # a weak reference does not pickle; the kept outputs are transient
-        return {"members": self.members, "_key": None, "_kept": {}}
-
-    def dissolve(self):
-        """Remove the members' back-references: every layer runs alone again."""
-        for lin in self.members:
-            if lin.__dict__.get("_group") is self:
-                del lin.__dict__["_group"]
-        self._key, self._kept = None, {}
+            if lin.in_features != first.in_features:
+                raise ValueError(f"CalderaLinearGroup: member {i}: in_features {lin.in_features} differs from "
+                                 f"member 0's {first.in_features}")
+            why = _formats_fit(members[:i + 1], [f"member {j}" for j in range(i + 1)])
+            if why is not None:
+                raise ValueError(f"CalderaLinearGroup: {why}")
+        self._adopt(members)
 
     def _grouped(self, x) -> bool:
         """Whether the grouped launch is the members' own inference launch for this x."""
@@ -1030,31 +1071,123 @@ class CalderaLinearGroup:
         K.linear_group_forward(x2, [_group_operands(lin) for lin in self.members], ys, self.members[0].q_format)
         return tuple(y.to(x.dtype).reshape(*x.shape[:-1], lin.out_features) for y, lin in zip(ys, self.members))
 
-    def __call__(self, x: torch.Tensor):
-        self._key, self._kept = None, {}
-        if not self._grouped(x):
-            return tuple(lin._forward_alone(x) for lin in self.members)
-        return self._launch(x)
 
-    def _member_forward(self, member, x):
-        """`member.forward(x)` of a grouped layer, see the class docstring."""
-        if member not in self.members:
-            # a shallow copy of a member (e.g. a DataParallel replica) still points here: it is not ours
-            return member._forward_alone(x)
-        if x.is_inference() or not self._grouped(x):
-            # an inference tensor has no version counter: a write in place could not be told from the
-            # x the kept outputs belong to, so none are kept for it
-            self._key, self._kept = None, {}
-            return member._forward_alone(x)
-        key = self._key
-        if (key is not None and key[0]() is x and key[1] == x._version and key[2] == x.data_ptr()
-                and id(member) in self._kept):
-            return self._kept.pop(id(member))
-        self._key, self._kept = None, {}   # another x (or a second call with this one): start over
-        ys = self._launch(x)
-        self._kept = {id(lin): y for lin, y in zip(self.members, ys) if lin is not member}
-        self._key = (weakref.ref(x), x._version, x.data_ptr())
-        return ys[self.members.index(member)]
+def _formats_fit(layers, labels, what=""):
+    """None when the `CalderaLinear` layers `layers` fit one cq_linear_group_forward -- bits and q_format shared,
+    L_bits and R_bits shared among those with rank > 0 (a rank-0 layer fits any factor format) -- else the
+    reason for the first layer that does not, as "<label>: <what><attribute> a differs from <label>'s b" with
+    the layers called by `labels`."""
+    ranked = None
+    for i, lin in enumerate(layers):
+        for attr in ("bits", "q_format"):
+            if getattr(lin, attr) != getattr(layers[0], attr):
+                return (f"{labels[i]}: {what}{attr} {getattr(lin, attr)} differs from {labels[0]}'s "
+                        f"{getattr(layers[0], attr)}")
+        if lin.rank > 0:
+            if ranked is None:
+                ranked = i
+            for attr in ("L_bits", "R_bits"):
+                if getattr(lin, attr) != getattr(layers[ranked], attr):
+                    return (f"{labels[i]}: {what}{attr} {getattr(lin, attr)} differs from {labels[ranked]}'s "
+                            f"{getattr(layers[ranked], attr)}")
+    return None
+
+
+def _hadamard_input(had, x):
+    """(x2, x^) of `HadamardCalderaLinear._forward_launches`: the (T, in_features) view of x the input
+    transform reads and the fp16 (T, pc) transform every layer with this in_features takes."""
+    n, pc = had.in_features, had.padded_shape[1]
+    if x.shape[-1] != n:
+        raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {n}")
+    x2 = x.reshape(-1, n)
+    if x2.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        x2 = x2.float()
+    if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < n):
+        x2 = x2.contiguous()
+    xh = torch.empty((x2.shape[0], pc), dtype=torch.float16, device=x.device)
+    K.hadamard_rows(x2, xh, n_in=n, n_out=pc, P=pc)
+    return x2, xh
+
+
+# The largest token count at which `HadamardLinearGroup` takes the grouped launches; None: no limit.  Measured on
+# 3 x 4096 x 4096 (tools/bench_hadamard_group.py, DESIGN 9.9): grouped is faster at every T measured, decode and
+# prefill (2-bit, r = 128: 33.4 against 61.6 us at T = 1, 158.5 against 435.2 us at T = 64, 264.2 against 449.5 us
+# at T = 512; 4-bit, r = 256: 37.0 / 70.5, 178.8 / 492.7, 257.1 / 497.0 us), so there is none.  `HadamardGatedMLP`'s
+# `max_fused_tokens` defaults to None for the same reason (2 x 11008 x 4096: 527.2 against 607.5 us at T = 512 at
+# 2 bits, 463.0 against 527.6 us at 4 bits).
+HADAMARD_GROUP_TOKEN_LIMIT = None
+
+
+class HadamardLinearGroup(_SharedInputGroup):
+    """`HadamardCalderaLinear` layers that read the same activation (q / k / v, gate / up), run as four
+    launches instead of four each: one input transform (they share x^ = H2 pad(x)), the inner layers'
+    grouped launch pair (cq_linear_group_forward), and one grouped output transform
+    (cq_hadamard_group_rows) per distinct padded output width, members bucketed in member order -- one
+    when all pr agree, two with GQA's smaller k / v.  Every member's output has the bits the member
+    computes alone.  A plain object with `CalderaLinearGroup`'s protocol: group(x), the transparent
+    member(x) with outputs kept per x, inference tensors and shallow copies running alone, `dissolve()`.
+
+    members: 1 .. `_lib.HADAMARD_GROUP_MAX` `HadamardCalderaLinear` layers on one device that share
+    in_features (hence pc and x^) and whose inner layers share bits and q_format and, among those with
+    rank > 0, L_bits and R_bits; none of them in another group, none of their inner layers in a
+    `CalderaLinearGroup`.  ValueError names the member and the attribute.
+
+    The grouped launches are taken where they are the members' own inference launches (no autograd graph
+    needed, no inner layer with trainable factors, no `dense_prefill_tokens` reached) and the token count
+    does not exceed `HADAMARD_GROUP_TOKEN_LIMIT`; otherwise every member runs alone.  The inner group
+    entry is called on the inner layers' operands directly: no `CalderaLinearGroup` is made or disturbed."""
+
+    def __init__(self, members):
+        members = list(members)
+        who = "HadamardLinearGroup"
+        if not 1 <= len(members) <= K.HADAMARD_GROUP_MAX:
+            raise ValueError(f"{who}: {len(members)} members, not 1 .. {K.HADAMARD_GROUP_MAX}")
+        for i, had in enumerate(members):
+            if not isinstance(had, HadamardCalderaLinear):
+                raise ValueError(f"{who}: member {i} is a {type(had).__name__}, not a HadamardCalderaLinear")
+            if any(had is other for other in members[:i]):
+                raise ValueError(f"{who}: member {i} is given twice")
+            if had.__dict__.get("_group") is not None:
+                raise ValueError(f"{who}: member {i} is already in a group (dissolve() it first)")
+            if had.inner.__dict__.get("_group") is not None:
+                raise ValueError(f"{who}: member {i}: inner is in a CalderaLinearGroup (dissolve() it first)")
+            first = members[0]
+            if had.inner.codes.device != first.inner.codes.device:
+                raise ValueError(f"{who}: member {i}: device {had.inner.codes.device} differs from member 0's "
+                                 f"{first.inner.codes.device}")
+            if had.in_features != first.in_features:
+                raise ValueError(f"{who}: member {i}: in_features {had.in_features} differs from member 0's "
+                                 f"{first.in_features}")
+        why = _formats_fit([had.inner for had in members], [f"member {i}" for i in range(len(members))], "inner ")
+        if why is not None:
+            raise ValueError(f"{who}: {why}")
+        self._adopt(members)
+
+    def _grouped(self, x) -> bool:
+        """Whether the grouped launches are the members' own inference launches for this x."""
+        if torch.is_grad_enabled() and x.requires_grad:
+            return False
+        T = x.numel() // max(x.shape[-1], 1)
+        if HADAMARD_GROUP_TOKEN_LIMIT is not None and T > HADAMARD_GROUP_TOKEN_LIMIT:
+            return False
+        return not any(had.inner.factors_trainable or _use_dense(had.inner, T) for had in self.members)
+
+    def _launch(self, x):
+        """`HadamardCalderaLinear._forward_launches` for every member: x^ once, the inner layers grouped,
+        the output transforms grouped by padded width."""
+        x2, xh = _hadamard_input(self.members[0], x)
+        T = x2.shape[0]
+        y32 = [torch.empty((T, had.padded_shape[0]), dtype=torch.float32, device=x.device) for had in self.members]
+        K.linear_group_forward(xh, [_group_operands(had.inner) for had in self.members], y32,
+                               self.members[0].inner.q_format)
+        ys = [torch.empty((T, had.out_features), dtype=x2.dtype, device=x.device) for had in self.members]
+        buckets = {}  # pr -> the members' transforms, in member order
+        for had, v, y in zip(self.members, y32, ys):
+            pr = had.padded_shape[0]
+            buckets.setdefault(pr, []).append(dict(x=v, y=y, n_in=pr, n_out=had.out_features, P=pr, bias=had.bias))
+        for transforms in buckets.values():
+            K.hadamard_group_rows(transforms)
+        return tuple(y.to(x.dtype).reshape(*x.shape[:-1], had.out_features) for y, had in zip(ys, self.members))
 
 
 ACTIVATIONS = {"silu": K.ACT_SILU, "identity": K.ACT_IDENTITY}
@@ -1083,14 +1216,10 @@ def glu_fit(gate, up):
         return "gate_proj and up_proj are the same layer"
     if up.codes.device != gate.codes.device:
         return f"up_proj: device {up.codes.device} differs from gate_proj's {gate.codes.device}"
-    for attr in ("in_features", "out_features", "bits", "q_format"):
+    for attr in ("in_features", "out_features"):
         if getattr(up, attr) != getattr(gate, attr):
             return f"up_proj: {attr} {getattr(up, attr)} differs from gate_proj's {getattr(gate, attr)}"
-    if gate.rank > 0 and up.rank > 0:
-        for attr in ("L_bits", "R_bits"):
-            if getattr(up, attr) != getattr(gate, attr):
-                return f"up_proj: {attr} {getattr(up, attr)} differs from gate_proj's {getattr(gate, attr)}"
-    return None
+    return _formats_fit((gate, up), ("gate_proj", "up_proj"))
 
 
 class CalderaGatedMLP(torch.nn.Module):
@@ -1167,6 +1296,96 @@ class CalderaGatedMLP(torch.nn.Module):
         hdt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
         h = torch.empty((x2.shape[0], m), dtype=hdt, device=x.device)
         K.linear_glu_forward(x2, _group_operands(gate), _group_operands(up), h, gate.q_format, act)
+        return h.to(x.dtype).reshape(*x.shape[:-1], m)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.down_proj(self.glu(x))
+
+
+def hadamard_glu_fit(gate, up):
+    """None when the `HadamardCalderaLinear` layers `gate` and `up` fit `HadamardGatedMLP`'s fused launches,
+    else the reason as a string that names the attribute."""
+    for name, had in (("gate_proj", gate), ("up_proj", up)):
+        if not isinstance(had, HadamardCalderaLinear):
+            return f"{name} is a {type(had).__name__}, not a HadamardCalderaLinear"
+    if gate is up:
+        return "gate_proj and up_proj are the same layer"
+    if up.inner.codes.device != gate.inner.codes.device:
+        return f"up_proj: device {up.inner.codes.device} differs from gate_proj's {gate.inner.codes.device}"
+    for attr in ("in_features", "out_features"):
+        if getattr(up, attr) != getattr(gate, attr):
+            return f"up_proj: {attr} {getattr(up, attr)} differs from gate_proj's {getattr(gate, attr)}"
+    return _formats_fit((gate.inner, up.inner), ("gate_proj", "up_proj"), "inner ")
+
+
+class HadamardGatedMLP(torch.nn.Module):
+    """A gated MLP block `down_proj(act(gate_proj(x)) * up_proj(x))` whose gate and up are
+    `HadamardCalderaLinear` layers, run as four launches: the input transform once (the two share
+    x^ = H2 pad(x)), the inner layers' grouped launch pair (cq_linear_group_forward) into two fp32
+    (T, pr) buffers, and one output transform of both with the activation and the product in its
+    epilogue (cq_hadamard_glu_rows).  The activation cannot sit in the inner pair's epilogue: it comes
+    after H1.
+
+    gate_proj, up_proj: `HadamardCalderaLinear` layers on one device that share in_features and
+    out_features and whose inner layers share bits and q_format and, when both have rank > 0, L_bits and
+    R_bits.  ValueError names the attribute.  down_proj: any module.  act: "silu" (the default) or
+    "identity".  The three layers are submodules under exactly these names: state-dict keys are those of
+    the original block.
+
+    glu(x) -> act(gate_proj(x)) * up_proj(x), shaped (..., out_features) in x's dtype.  The fused launches
+    are taken only where they are the layers' own inference launches: no autograd graph is needed, neither
+    inner layer has trainable factors, no `dense_prefill_tokens` applies at this token count, the padded
+    width pr does not exceed `_lib.HADAMARD_GLU_MAX_N` (two rows of 32768 do not fit the LDS), the token
+    count does not exceed `max_fused_tokens` (None, the default: no limit; or an int), and the two layers
+    still fit.  There the pre-activations have the bits of the layers' own fp32 outputs (bias included), h32
+    is `cq_linear_glu_forward`'s epilogue sequence on them, and h is rounded once to x's dtype (fp16, bf16 or
+    fp32; anything else is computed in fp32 and cast): against the unfused formula on fp16 tensors the
+    fused result skips the roundings of gate(x), up(x) and act(gate(x)) -- one rounding instead of three.
+    Otherwise glu(x) is the formula through the layers' ordinary forwards (gradients flow; a
+    `HadamardLinearGroup` they belong to still serves them).  The fused path calls the entries on the
+    layers' operands directly: it neither uses nor disturbs a group."""
+
+    def __init__(self, gate_proj, up_proj, down_proj, act="silu", max_fused_tokens=None):
+        super().__init__()
+        if act not in ACTIVATIONS:
+            raise ValueError(f"HadamardGatedMLP: act {act!r} not in {tuple(ACTIVATIONS)}")
+        why = hadamard_glu_fit(gate_proj, up_proj)
+        if why is not None:
+            raise ValueError(f"HadamardGatedMLP: {why}")
+        if not isinstance(down_proj, torch.nn.Module):
+            raise ValueError(f"HadamardGatedMLP: down_proj is a {type(down_proj).__name__}, not a module")
+        if max_fused_tokens is not None and (isinstance(max_fused_tokens, bool) or not isinstance(max_fused_tokens, int)):
+            raise ValueError(f"HadamardGatedMLP: max_fused_tokens {max_fused_tokens!r} is not None or an int")
+        self.act = act
+        self.max_fused_tokens = max_fused_tokens
+        self.gate_proj, self.up_proj, self.down_proj = gate_proj, up_proj, down_proj
+
+    def extra_repr(self):
+        return f"act={self.act}"
+
+    def _fused(self, x) -> bool:
+        """Whether the fused launches are the layers' own inference launches for this x."""
+        gate, up = self.gate_proj, self.up_proj
+        if hadamard_glu_fit(gate, up) is not None or gate.padded_shape[0] > K.HADAMARD_GLU_MAX_N:
+            return False
+        if torch.is_grad_enabled() and x.requires_grad:
+            return False
+        T = x.numel() // max(x.shape[-1], 1)
+        if self.max_fused_tokens is not None and T > self.max_fused_tokens:
+            return False
+        return not any(had.inner.factors_trainable or _use_dense(had.inner, T) for had in (gate, up))
+
+    def glu(self, x: torch.Tensor) -> torch.Tensor:
+        gate, up = self.gate_proj, self.up_proj
+        act = ACTIVATIONS[self.act]
+        if not self._fused(x):
+            return _act_torch(act, gate(x)) * up(x)
+        x2, xh = _hadamard_input(gate, x)
+        T, pr, m = x2.shape[0], gate.padded_shape[0], gate.out_features
+        v = [torch.empty((T, pr), dtype=torch.float32, device=x.device) for _ in range(2)]
+        K.linear_group_forward(xh, [_group_operands(gate.inner), _group_operands(up.inner)], v, gate.inner.q_format)
+        h = torch.empty((T, m), dtype=x2.dtype, device=x.device)
+        K.hadamard_glu_rows(v[0], v[1], h, n_in=pr, n_out=m, P=pr, bias_g=gate.bias, bias_u=up.bias, act=act)
         return h.to(x.dtype).reshape(*x.shape[:-1], m)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -472,7 +472,7 @@ def unpack_packed_layers(model: torch.nn.Module, dtype=torch.float16) -> list:
 SHARED_INPUT_SETS = (("q_proj", "k_proj", "v_proj"), ("gate_proj", "up_proj"))
 
 
-def group_shared_input_layers(model: torch.nn.Module, sets=SHARED_INPUT_SETS):
+def group_shared_input_layers(model: torch.nn.Module, sets=SHARED_INPUT_SETS, hadamard=False):
     """Make a `linear.CalderaLinearGroup` of every set of sibling packed layers that read the same
     activation: for each module of `model` and each tuple of child names in `sets`, the children of
     those names, when all of them are `linear.CalderaLinear` layers that can form a group.  The
@@ -482,8 +482,13 @@ def group_shared_input_layers(model: torch.nn.Module, sets=SHARED_INPUT_SETS):
     Returns (grouped, skipped): the dotted names of each group made, as tuples, and for every set of
     which a module has at least one child but which was not grouped, (names, reason) -- a child is
     missing, dense, a Hadamard-basis layer, already grouped, or the layers do not fit one group.
-    Nothing raises for them."""
-    from .linear import CalderaLinear, CalderaLinearGroup, HadamardCalderaLinear
+    Nothing raises for them.
+
+    hadamard=True: a set whose children are all `linear.HadamardCalderaLinear` layers becomes a
+    `linear.HadamardLinearGroup` (one input transform, one inner launch pair, one grouped output
+    transform per padded width).  A set that mixes plain and Hadamard-basis layers stays skipped.  With
+    the default, Hadamard-basis sets are skipped as before."""
+    from .linear import CalderaLinear, CalderaLinearGroup, HadamardCalderaLinear, HadamardLinearGroup
     grouped, skipped = [], []
     for prefix, mod in list(model.named_modules()):
         for names in sets:
@@ -492,9 +497,13 @@ def group_shared_input_layers(model: torch.nn.Module, sets=SHARED_INPUT_SETS):
                 continue
             full = tuple(f"{prefix}.{name}" if prefix else name for name in names)
             reason = None
+            basis = hadamard and all(isinstance(child, HadamardCalderaLinear) for child in children)
             for name, child in zip(names, children):
                 if child is None:
                     reason = f"{name} is missing"
+                elif basis:
+                    if child.group is not None:
+                        reason = f"{name} is already grouped"
                 elif isinstance(child, HadamardCalderaLinear):
                     reason = f"{name} is a HadamardCalderaLinear"
                 elif not isinstance(child, CalderaLinear):
@@ -505,7 +514,7 @@ def group_shared_input_layers(model: torch.nn.Module, sets=SHARED_INPUT_SETS):
                     break
             if reason is None:
                 try:
-                    CalderaLinearGroup(children)
+                    (HadamardLinearGroup if basis else CalderaLinearGroup)(children)
                 except ValueError as e:
                     reason = f"incompatible: {e}"
             if reason is None:
@@ -516,13 +525,13 @@ def group_shared_input_layers(model: torch.nn.Module, sets=SHARED_INPUT_SETS):
 
 
 def ungroup_shared_input_layers(model: torch.nn.Module) -> list:
-    """Dissolve every `linear.CalderaLinearGroup` that a layer of `model` belongs to; returns the
-    dotted names of each dissolved group's members found in the model, as tuples."""
-    from .linear import CalderaLinear
+    """Dissolve every `linear.CalderaLinearGroup` and `linear.HadamardLinearGroup` that a layer of `model`
+    belongs to; returns the dotted names of each dissolved group's members found in the model, as tuples."""
+    from .linear import CalderaLinear, HadamardCalderaLinear
     names = {id(mod): name for name, mod in model.named_modules()}
     done = []
     for mod in list(model.modules()):
-        group = mod.group if isinstance(mod, CalderaLinear) else None
+        group = mod.group if isinstance(mod, (CalderaLinear, HadamardCalderaLinear)) else None
         if group is not None:
             done.append(tuple(names[id(lin)] for lin in group.members if id(lin) in names))
             group.dissolve()
@@ -545,7 +554,7 @@ def _recognise_activation(fn):
     return None
 
 
-def fuse_gated_mlps(model: torch.nn.Module, names=GATED_MLP_NAMES, act=None):
+def fuse_gated_mlps(model: torch.nn.Module, names=GATED_MLP_NAMES, act=None, hadamard=False):
     """Replace every gated MLP block of `model` by a `linear.CalderaGatedMLP`, whose gate / up pair runs
     as one launch pair with the activation and the product in its epilogue (cq_linear_glu_forward).
 
@@ -566,8 +575,14 @@ def fuse_gated_mlps(model: torch.nn.Module, names=GATED_MLP_NAMES, act=None):
     unknown activation, layers that do not fit the entry, extra state, the model itself, already fused.
     Nothing raises for them.  `unpack_packed_layers`, `set_dense_prefill`, `prepare_factor_finetuning`
     and `group_shared_input_layers` work on a fused model: they find the layers by type, and the fused
-    module takes its unfused formula wherever the fused launch is not the layers' own."""
-    from .linear import ACTIVATIONS, CalderaGatedMLP, CalderaLinear, HadamardCalderaLinear, glu_fit
+    module takes its unfused formula wherever the fused launch is not the layers' own.
+
+    hadamard=True: a block whose gate and up are both `linear.HadamardCalderaLinear` layers becomes a
+    `linear.HadamardGatedMLP` (the activation and the product in the output transform's epilogue,
+    cq_hadamard_glu_rows).  A block that mixes a plain and a Hadamard-basis layer stays skipped.  With the
+    default, Hadamard-basis blocks are skipped as before."""
+    from .linear import (ACTIVATIONS, CalderaGatedMLP, CalderaLinear, HadamardCalderaLinear, HadamardGatedMLP, glu_fit,
+                         hadamard_glu_fit)
     if len(names) != 4:
         raise ValueError(f"fuse_gated_mlps: names {names!r} is not (gate, up, down, activation)")
     if act is not None and act not in ACTIVATIONS:
@@ -579,14 +594,17 @@ def fuse_gated_mlps(model: torch.nn.Module, names=GATED_MLP_NAMES, act=None):
         if any(child is None for child in children):
             continue
         label = name or "<model>"
-        if isinstance(mod, CalderaGatedMLP):
+        if isinstance(mod, (CalderaGatedMLP, HadamardGatedMLP)):
             skipped.append((label, "already fused"))
             continue
         gate, up, down = children
         how = act if act is not None else _recognise_activation(getattr(mod, act_n, None))
         extra = [n for n in mod._modules if n not in names] + list(mod._parameters) + list(mod._buffers)
         reason = None
+        basis = hadamard and isinstance(gate, HadamardCalderaLinear) and isinstance(up, HadamardCalderaLinear)
         for n, child in ((gate_n, gate), (up_n, up)):
+            if basis:
+                break
             if isinstance(child, HadamardCalderaLinear):
                 reason = f"{n} is a HadamardCalderaLinear"
             elif not isinstance(child, CalderaLinear):
@@ -594,7 +612,7 @@ def fuse_gated_mlps(model: torch.nn.Module, names=GATED_MLP_NAMES, act=None):
             if reason:
                 break
         if reason is None:
-            why = glu_fit(gate, up)
+            why = hadamard_glu_fit(gate, up) if basis else glu_fit(gate, up)
             if why is not None:
                 reason = f"incompatible: {why}"
             elif how is None:
@@ -606,7 +624,7 @@ def fuse_gated_mlps(model: torch.nn.Module, names=GATED_MLP_NAMES, act=None):
         if reason is not None:
             skipped.append((label, reason))
             continue
-        new = CalderaGatedMLP(gate, up, down, act=how)
+        new = (HadamardGatedMLP if basis else CalderaGatedMLP)(gate, up, down, act=how)
         new.__dict__["_original"] = (mod, (gate_n, up_n, down_n))
         new.train(mod.training)
         _set_module(model, name, new)
@@ -615,13 +633,14 @@ def fuse_gated_mlps(model: torch.nn.Module, names=GATED_MLP_NAMES, act=None):
 
 
 def unfuse_gated_mlps(model: torch.nn.Module) -> list:
-    """Put back the original block of every `linear.CalderaGatedMLP` that `fuse_gated_mlps` made, with
-    the three layers the fused module holds now (they may have been replaced or unpacked since);
-    returns the dotted names.  A `CalderaGatedMLP` built by hand has no original and stays."""
-    from .linear import CalderaGatedMLP
+    """Put back the original block of every `linear.CalderaGatedMLP` and `linear.HadamardGatedMLP` that
+    `fuse_gated_mlps` made, with the three layers the fused module holds now (they may have been replaced
+    or unpacked since); returns the dotted names.  A fused module built by hand has no original and stays."""
+    from .linear import CalderaGatedMLP, HadamardGatedMLP
     done = []
     for name, mod in list(model.named_modules()):
-        if not isinstance(mod, CalderaGatedMLP) or "_original" not in mod.__dict__ or not name:
+        if (not isinstance(mod, (CalderaGatedMLP, HadamardGatedMLP)) or "_original" not in mod.__dict__
+                or not name):
             continue
         orig, names = mod.__dict__["_original"]
         for n, layer in zip(names, (mod.gate_proj, mod.up_proj, mod.down_proj)):

@@ -997,6 +997,70 @@ typedef struct cq_hadamard_args {
 
 int cq_hadamard_rows(const cq_hadamard_args* a, void* stream);
 
+/* Grouped transform (ABI 5, additive): 1 .. CQ_HADAMARD_GROUP_MAX transforms of the same `rows` and P in
+ * one launch -- the output transforms of Hadamard-basis layers that read the same activation (q / k / v).
+ *
+ * Contract:
+ *   - member i's y has, bit for bit, the value cq_hadamard_rows gives on the same arguments.  It holds by
+ *     construction: the kernels are one body for both entries; the grid's y extent is the number of
+ *     members, a workgroup takes its member's arguments by blockIdx.y (uniform) and does that member's
+ *     workgroup's work at blockIdx.x;
+ *   - the members share rows and P (the kernel's instantiation and the grid's x extent); x, y, the
+ *     dtypes, the strides, n_in, n_out and the bias are per member;
+ *   - each member passes cq_hadamard_rows' checks; those, a member whose rows or P differ from member
+ *     0's, and a count outside 1 .. CQ_HADAMARD_GROUP_MAX are CQ_EINVAL with a message naming the member
+ *     and the field, decided on the host before any HIP call;
+ *   - rows == 0 returns CQ_OK without a launch; a member with n_out == 0 is skipped (it takes no
+ *     workgroup; all skipped: no launch);
+ *   - one launch; no atomics, no workspace, stream-ordered, no allocation, no host synchronisation
+ *     (graph-capturable).  The members array is read on the host during the call only.  No member's y
+ *     may overlap any member's x or another member's y. */
+#define CQ_HADAMARD_GROUP_MAX 8
+
+typedef struct cq_hadamard_group_args {
+    int32_t count;                      /* 1 .. CQ_HADAMARD_GROUP_MAX */
+    const cq_hadamard_args* members;    /* host array of `count` transforms */
+} cq_hadamard_group_args;
+
+int cq_hadamard_group_rows(const cq_hadamard_group_args* g, void* stream);
+
+/* Gated transform pair (ABI 5, additive): h = a(H g + bias_g) * (H u + bias_u), the output transforms of
+ * the gate and up layers of a Hadamard-basis gated MLP with the activation and the product in the
+ * epilogue; neither transformed row is written to memory.
+ *
+ * Contract:
+ *   - let v_g[t, i] and v_u[t, i] be the fp32 values cq_hadamard_rows forms from (g, bias_g) and from
+ *     (u, bias_u) with the same rows, n_in, n_out and P before its output rounding: what it writes with
+ *     y_dtype = CQ_F32.  This entry computes those same bits (the same stage functions in the same
+ *     order, the same scale and bias step);
+ *   - h32 = a(v_g) * v_u, one fp32 multiply.  CQ_ACT_IDENTITY: a(v) = v.  CQ_ACT_SILU: e = expf(-v) (the
+ *     device library's), d = 1.0f + e, a = v / d with the correctly rounded fp32 division; nothing is
+ *     contracted (cq_linear_glu_forward's sequence);
+ *   - h (rows x n_out, fp32 | fp16 | bf16, row stride ldh) receives h32, for the narrow types rounded
+ *     once to nearest even, and is written only in [0, n_out).  g and u (rows x n_in, each fp32 | fp16 |
+ *     bf16 with its own stride) are read only in [0, n_in);
+ *   - P = 2^p <= CQ_HADAMARD_GLU_MAX_N: rows above 4096 keep both rows' sub-row buffers in LDS, 2 x 64 KB
+ *     at P = 16384 of the CU's 160 KB; 32768 does not fit;
+ *   - one launch; no atomics, no workspace, stream-ordered, no allocation, no host synchronisation
+ *     (graph-capturable).  h must not overlap g or u.
+ * CQ_EINVAL (before any HIP call): an unknown act or dtype; P not a power of two or above
+ * CQ_HADAMARD_GLU_MAX_N; n_in outside [1, P], n_out outside [0, P]; rows < 0; g, u, h or a bias not aligned
+ * to its element; a row stride below the row (ldg, ldu < n_in, ldh < n_out); with rows > 0 and n_out > 0 a
+ * null g, u or h.  rows == 0 (or n_out == 0) returns 0 without a launch. */
+#define CQ_HADAMARD_GLU_MAX_N 16384
+
+typedef struct cq_hadamard_glu_args {
+    const void* g; int g_dtype; int64_t ldg;   /* fp16 | bf16 | fp32, rows x n_in  */
+    const void* u; int u_dtype; int64_t ldu;   /* fp16 | bf16 | fp32, rows x n_in  */
+    void* h;       int h_dtype; int64_t ldh;   /* fp16 | bf16 | fp32, rows x n_out */
+    int64_t rows, n_in, n_out, P;              /* P = 2^p, 1 <= P <= CQ_HADAMARD_GLU_MAX_N */
+    const float* bias_g;                       /* n_out fp32 or NULL, added to the scaled gate row */
+    const float* bias_u;                       /* n_out fp32 or NULL, added to the scaled up row */
+    int act;                                   /* CQ_ACT_* */
+} cq_hadamard_glu_args;
+
+int cq_hadamard_glu_rows(const cq_hadamard_glu_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
