@@ -1342,11 +1342,73 @@ def _linear_need(cond, what):
         raise ValueError(f"cq_linear: {what}")
 
 
+def _resolve_rank(L, R, L_codes, R_codes, r) -> int:
+    """The rank: r as given, else an fp16 factor's; with r > 0 each factor comes in exactly one form."""
+    need = _linear_need
+    if r is None:
+        need(L is not None or R is not None or (L_codes is None and R_codes is None),
+             "r is needed when both factors are coded")
+        r = L.shape[1] if L is not None else R.shape[0] if R is not None else 0
+    r = int(r)
+    if r:
+        need((L is None) != (L_codes is None), "give exactly one of L and L_codes")
+        need((R is None) != (R_codes is None), "give exactly one of R and R_codes")
+    return r
+
+
+def _fp16_factors(L, R, r, L_coded, R_coded):
+    """(name, tensor) of the factors that are looked at as fp16: none for r = 0, not a coded one."""
+    return ((("L", L),) if r and not L_coded else ()) + ((("R", R),) if r and not R_coded else ())
+
+
+def _check_fp16_factors(fp16, m, r, n):
+    need = _linear_need
+    if fp16:
+        need(all(t.dtype == torch.float16 for _, t in fp16),
+             "L and R must be fp16, got " + ", ".join(str(t.dtype) for _, t in fp16))
+        need(all(tuple(t.shape) == ((m, r) if name == "L" else (r, n)) for name, t in fp16),
+             " / ".join(f"{name} {tuple(t.shape)}" for name, t in fp16) + f" do not fit {(m, r)} / {(r, n)}")
+
+
+def _fill_factor_codes(a, L_codes, R_codes, m, r):
+    """l_bits / r_bits and, for a factor given as (codes, scale, bits), its code fields."""
+    a.l_bits = a.r_bits = 16
+    for what, spec, rows in (("L", L_codes, m), ("R", R_codes, r)):
+        if spec is None or not r:
+            continue
+        t, scale, fbits = spec
+        _linear_need(t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.uint8 and t.shape[0] == rows,
+                     f"{what}_codes must be a uint8 matrix with {rows} rows and unit column stride")
+        setattr(a, what.lower() + "_bits", int(fbits))
+        setattr(a, what + "_codes", t.data_ptr())
+        setattr(a, what.lower() + "_code_stride", t.stride(0))
+        setattr(a, what.lower() + "scale", float(scale))
+
+
+def _factor_code_tensors(L_codes, R_codes):
+    return (None if L_codes is None else L_codes[0], None if R_codes is None else R_codes[0])
+
+
+def _member_tensors(mem):
+    """The tensors of a member dict (`linear_group_args`), as `_require_hip` takes them."""
+    return (mem["codes"], mem.get("L"), mem.get("R"), mem.get("bias"),
+            *_factor_code_tensors(mem.get("L_codes"), mem.get("R_codes")))
+
+
+def _run(entry, workspace_entry, a, out, device, ws):
+    """The wrappers' common tail: the workspace (sized by `workspace_entry` when None), the call, `out`."""
+    lib = load()
+    if ws is None:
+        ws = workspace(getattr(lib, workspace_entry)(ctypes.byref(a)), device)
+    _check(getattr(lib, entry)(ctypes.byref(a), _p(ws), ws.numel(), _stream(device)), entry)
+    return out
+
+
 def _fill_linear_args(a, x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, r, L_coded=False, R_coded=False):
     """The fields cq_linear_args and cq_linear_packed_args share; a coded factor's fp16 operand
     is not looked at."""
     need = _linear_need
-    fp16 = ((("L", L),) if r and not L_coded else ()) + ((("R", R),) if r and not R_coded else ())
+    fp16 = _fp16_factors(L, R, r, L_coded, R_coded)
     for name, t in (("x", x), ("codes", codes), ("y", y)) + fp16:
         need(t.dim() == 2 and t.stride(1) == 1, f"{name} must be a matrix with unit column stride")
     need(x.dtype == torch.float16, f"x must be fp16, got {x.dtype}")
@@ -1354,11 +1416,7 @@ def _fill_linear_args(a, x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits,
     need(x.shape[1] == n and tuple(y.shape) == (x.shape[0], m), f"x {tuple(x.shape)} / y {tuple(y.shape)} do not fit "
          f"(tokens, {n}) / (tokens, {m})")
     need(y.dtype in (torch.float32, torch.float16), f"y must be fp32 or fp16, got {y.dtype}")
-    if fp16:
-        need(all(t.dtype == torch.float16 for _, t in fp16),
-             "L and R must be fp16, got " + ", ".join(str(t.dtype) for _, t in fp16))
-        need(all(tuple(t.shape) == ((m, r) if name == "L" else (r, n)) for name, t in fp16),
-             " / ".join(f"{name} {tuple(t.shape)}" for name, t in fp16) + f" do not fit {(m, r)} / {(r, n)}")
+    _check_fp16_factors(fp16, m, r, n)
     if bias is not None:
         need(bias.dtype == torch.float32 and tuple(bias.shape) == (m,) and bias.is_contiguous(),
              f"bias must be a contiguous fp32 ({m},) vector, got {bias.dtype} {tuple(bias.shape)}")
@@ -1383,28 +1441,10 @@ def linear_packed_args(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, r
     L_codes / R_codes: (uint8 inference-layout codes with one row per m resp. r, scale, bits in
     {2, 4}); the fp16 L / R of a coded factor is None.  r: the rank, needed when both factors are
     coded (else taken from the fp16 one).  into: the struct to fill (a codebook struct's `p`)."""
-    need = _linear_need
-    if r is None:
-        need(L is not None or R is not None or (L_codes is None and R_codes is None),
-             "r is needed when both factors are coded")
-        r = L.shape[1] if L is not None else R.shape[0] if R is not None else 0
-    r = int(r)
-    if r:
-        need((L is None) != (L_codes is None), "give exactly one of L and L_codes")
-        need((R is None) != (R_codes is None), "give exactly one of R and R_codes")
+    r = _resolve_rank(L, R, L_codes, R_codes, r)
     a = _fill_linear_args(LinearPackedArgs() if into is None else into, x, codes, qscale, gscale, L, R, bias, y, m=m,
                           n=n, bits=bits, r=r, L_coded=L_codes is not None, R_coded=R_codes is not None)
-    a.l_bits = a.r_bits = 16
-    for what, spec, rows in (("L", L_codes, m), ("R", R_codes, r)):
-        if spec is None or not r:
-            continue
-        t, scale, fbits = spec
-        need(t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.uint8 and t.shape[0] == rows,
-             f"{what}_codes must be a uint8 matrix with {rows} rows and unit column stride")
-        setattr(a, what.lower() + "_bits", int(fbits))
-        setattr(a, what + "_codes", t.data_ptr())
-        setattr(a, what.lower() + "_code_stride", t.stride(0))
-        setattr(a, what.lower() + "scale", float(scale))
+    _fill_factor_codes(a, L_codes, R_codes, m, r)
     return a
 
 
@@ -1413,16 +1453,10 @@ def linear_packed_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits
     """y = x (gs (Q + L R))^T (+ bias) with either factor applied from its packed 2/4-bit codes
     (cq_linear_packed_forward); operands as `linear_packed_args`, ws as `linear_forward`.  No
     host synchronisation."""
-    _require_hip(x, codes, L, R, bias, y, None if L_codes is None else L_codes[0],
-                 None if R_codes is None else R_codes[0])
+    _require_hip(x, codes, L, R, bias, y, *_factor_code_tensors(L_codes, R_codes))
     a = linear_packed_args(x, codes, qscale, gscale, L, R, bias, y, m=m, n=n, bits=bits, r=r, L_codes=L_codes,
                            R_codes=R_codes)
-    lib = load()
-    if ws is None:
-        ws = workspace(lib.cq_linear_packed_workspace(ctypes.byref(a)), x.device)
-    _check(lib.cq_linear_packed_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)),
-           "cq_linear_packed_forward")
-    return y
+    return _run("cq_linear_packed_forward", "cq_linear_packed_workspace", a, y, x.device, ws)
 
 
 QFMT_UNIFORM = 0  # include/caldera_hip.h CQ_QFMT_UNIFORM: offset-binary uniform codes
@@ -1457,19 +1491,33 @@ def linear_codebook_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bi
                             R_codes=None, ws=None):
     """y = x (gs (Q + L R))^T (+ bias) with Q in q_format (cq_linear_codebook_forward); operands as
     `linear_codebook_args`, ws as `linear_forward`.  No host synchronisation."""
-    _require_hip(x, codes, L, R, bias, y, None if L_codes is None else L_codes[0],
-                 None if R_codes is None else R_codes[0])
+    _require_hip(x, codes, L, R, bias, y, *_factor_code_tensors(L_codes, R_codes))
     a = linear_codebook_args(x, codes, qscale, gscale, L, R, bias, y, m=m, n=n, bits=bits, q_format=q_format, r=r,
                              L_codes=L_codes, R_codes=R_codes)
-    lib = load()
-    if ws is None:
-        ws = workspace(lib.cq_linear_codebook_workspace(ctypes.byref(a)), x.device)
-    _check(lib.cq_linear_codebook_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)),
-           "cq_linear_codebook_forward")
-    return y
+    return _run("cq_linear_codebook_forward", "cq_linear_codebook_workspace", a, y, x.device, ws)
 
 
 LINEAR_GROUP_MAX = 8  # include/caldera_hip.h CQ_LINEAR_GROUP_MAX
+
+
+def _fill_member(into, x, mem, y, q_format, where, gate_m=None):
+    """A member dict (`linear_group_args`) into the struct `into`, with q_format's checks and
+    `linear_packed_args`'; its ValueError names `where`.  gate_m: the m a gated pair's member must have."""
+    try:
+        _check_q_format(q_format, mem["qscale"])
+        if gate_m is not None:
+            _linear_need(mem["m"] == gate_m, f"m {mem['m']} differs from gate's {gate_m}")
+        return linear_packed_args(x, mem["codes"], mem["qscale"], mem["gscale"], mem.get("L"), mem.get("R"),
+                                  mem.get("bias"), y, m=mem["m"], n=mem["n"], bits=mem["bits"], r=mem.get("r"),
+                                  L_codes=mem.get("L_codes"), R_codes=mem.get("R_codes"), into=into)
+    except ValueError as e:
+        raise ValueError(f"cq_linear: {where}: {str(e).removeprefix('cq_linear: ')}") from None
+
+
+def _need_same(a, ref, fields, where, ref_name):
+    for field in fields:
+        _linear_need(getattr(a, field) == getattr(ref, field),
+                     f"{where}: {field} {getattr(a, field)} differs from {ref_name}'s {getattr(ref, field)}")
 
 
 def linear_group_args(x, members, ys, q_format) -> LinearGroupArgs:
@@ -1487,22 +1535,13 @@ def linear_group_args(x, members, ys, q_format) -> LinearGroupArgs:
     arr = (LinearPackedArgs * len(members))()
     ranked = None
     for i, (mem, y) in enumerate(zip(members, ys)):
-        try:
-            _check_q_format(q_format, mem["qscale"])
-            a = linear_packed_args(x, mem["codes"], mem["qscale"], mem["gscale"], mem.get("L"), mem.get("R"),
-                                   mem.get("bias"), y, m=mem["m"], n=mem["n"], bits=mem["bits"], r=mem.get("r"),
-                                   L_codes=mem.get("L_codes"), R_codes=mem.get("R_codes"), into=arr[i])
-        except ValueError as e:
-            raise ValueError(f"cq_linear: group member {i}: {str(e).removeprefix('cq_linear: ')}") from None
-        for field in ("n", "bits", "y_dtype"):
-            need(getattr(a, field) == getattr(arr[0], field), f"group member {i}: {field} {getattr(a, field)} differs "
-                 f"from member 0's {getattr(arr[0], field)}")
+        where = f"group member {i}"
+        a = _fill_member(arr[i], x, mem, y, q_format, where)
+        _need_same(a, arr[0], ("n", "bits", "y_dtype"), where, "member 0")
         if a.r > 0:
             if ranked is None:
                 ranked = i
-            for field in ("l_bits", "r_bits"):
-                need(getattr(a, field) == getattr(arr[ranked], field), f"group member {i}: {field} "
-                     f"{getattr(a, field)} differs from member {ranked}'s {getattr(arr[ranked], field)}")
+            _need_same(a, arr[ranked], ("l_bits", "r_bits"), where, f"member {ranked}")
     g = LinearGroupArgs()
     g.count, g.q_format = len(members), int(q_format)
     g.members = ctypes.cast(arr, ctypes.POINTER(LinearPackedArgs))
@@ -1516,17 +1555,10 @@ def linear_group_forward(x, members, ys, q_format, ws=None):
     writes.  ws as `linear_forward`.  No host synchronisation."""
     members = list(members)
     for mem in members:
-        _require_hip(x, mem["codes"], mem.get("L"), mem.get("R"), mem.get("bias"),
-                     None if mem.get("L_codes") is None else mem["L_codes"][0],
-                     None if mem.get("R_codes") is None else mem["R_codes"][0])
+        _require_hip(x, *_member_tensors(mem))
     _require_hip(*ys)
     g = linear_group_args(x, members, ys, q_format)
-    lib = load()
-    if ws is None:
-        ws = workspace(lib.cq_linear_group_workspace(ctypes.byref(g)), x.device)
-    _check(lib.cq_linear_group_forward(ctypes.byref(g), _p(ws), ws.numel(), _stream(x.device)),
-           "cq_linear_group_forward")
-    return ys
+    return _run("cq_linear_group_forward", "cq_linear_group_workspace", g, ys, x.device, ws)
 
 
 ACT_IDENTITY = 0  # include/caldera_hip.h CQ_ACT_IDENTITY: h = g * u
@@ -1548,24 +1580,12 @@ def linear_glu_args(x, gate, up, h, q_format, act) -> LinearGluArgs:
     need(h.shape[0] <= 1 or h.stride(0) >= h.shape[1], f"glu: ldh {h.stride(0)} < m {h.shape[1]}")
     a = LinearGluArgs()
     for name, mem in (("gate", gate), ("up", up)):
-        p = getattr(a, name)
-        try:
-            _check_q_format(q_format, mem["qscale"])
-            need(mem["m"] == gate["m"], f"m {mem['m']} differs from gate's {gate['m']}")
-            # h stands in for y while the member's other operands are checked
-            linear_packed_args(x, mem["codes"], mem["qscale"], mem["gscale"], mem.get("L"), mem.get("R"),
-                               mem.get("bias"), h, m=mem["m"], n=mem["n"], bits=mem["bits"], r=mem.get("r"),
-                               L_codes=mem.get("L_codes"), R_codes=mem.get("R_codes"), into=p)
-        except ValueError as e:
-            raise ValueError(f"cq_linear: glu {name}: {str(e).removeprefix('cq_linear: ')}") from None
+        # h stands in for y while the member's other operands are checked
+        p = _fill_member(getattr(a, name), x, mem, h, q_format, f"glu {name}", gate_m=gate["m"])
         p.y, p.y_dtype, p.ldy = None, 0, 0
-        for field in ("n", "bits"):
-            need(getattr(p, field) == getattr(a.gate, field), f"glu {name}: {field} {getattr(p, field)} differs "
-                 f"from gate's {getattr(a.gate, field)}")
+        _need_same(p, a.gate, ("n", "bits"), f"glu {name}", "gate")
     if a.gate.r > 0 and a.up.r > 0:
-        for field in ("l_bits", "r_bits"):
-            need(getattr(a.up, field) == getattr(a.gate, field), f"glu up: {field} {getattr(a.up, field)} differs "
-                 f"from gate's {getattr(a.gate, field)}")
+        _need_same(a.up, a.gate, ("l_bits", "r_bits"), "glu up", "gate")
     a.q_format, a.act = int(q_format), int(act)
     a.h, a.ldh = h.data_ptr(), h.stride(0) if h.shape[0] > 1 else max(h.stride(0), h.shape[1])
     a.h_dtype = {torch.float32: CQ_F32, torch.float16: CQ_F16}[h.dtype]
@@ -1577,16 +1597,10 @@ def linear_glu_forward(x, gate, up, h, q_format, act=ACT_SILU, ws=None):
     (cq_linear_glu_forward): the pre-activations have the bits of the members' own fp32 outputs and are
     never written.  Operands as `linear_glu_args`, ws as `linear_forward`.  No host synchronisation."""
     for mem in (gate, up):
-        _require_hip(x, mem["codes"], mem.get("L"), mem.get("R"), mem.get("bias"),
-                     None if mem.get("L_codes") is None else mem["L_codes"][0],
-                     None if mem.get("R_codes") is None else mem["R_codes"][0])
+        _require_hip(x, *_member_tensors(mem))
     _require_hip(h)
     a = linear_glu_args(x, gate, up, h, q_format, act)
-    lib = load()
-    if ws is None:
-        ws = workspace(lib.cq_linear_glu_workspace(ctypes.byref(a)), x.device)
-    _check(lib.cq_linear_glu_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)), "cq_linear_glu_forward")
-    return h
+    return _run("cq_linear_glu_forward", "cq_linear_glu_workspace", a, h, x.device, ws)
 
 
 def linear_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, ws=None):
@@ -1595,11 +1609,7 @@ def linear_forward(x, codes, qscale, gscale, L, R, bias, y, *, m, n, bits, ws=No
     synchronisation."""
     _require_hip(x, codes, L, R, bias, y)
     a = linear_args(x, codes, qscale, gscale, L, R, bias, y, m=m, n=n, bits=bits)
-    lib = load()
-    if ws is None:
-        ws = workspace(lib.cq_linear_workspace(ctypes.byref(a)), x.device)
-    _check(lib.cq_linear_forward(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)), "cq_linear_forward")
-    return y
+    return _run("cq_linear_forward", "cq_linear_workspace", a, y, x.device, ws)
 
 
 def linear_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, u_out=None) -> LinearBackwardArgs:
@@ -1617,7 +1627,7 @@ def _fill_linear_backward_args(a, dy, codes, qscale, gscale, L, R, dx, *, m, n, 
     """The fields cq_linear_backward_args and cq_linear_packed_backward_args share; a coded
     factor's fp16 operand is not looked at."""
     need = _linear_need
-    fp16 = ((("L", L),) if r and not L_coded else ()) + ((("R", R),) if r and not R_coded else ())
+    fp16 = _fp16_factors(L, R, r, L_coded, R_coded)
     mats = (("dy", dy), ("codes", codes), ("dx", dx)) + fp16 + ((("u_out", u_out),) if r and u_out is not None else ())
     for name, t in mats:
         need(t.dim() == 2 and t.stride(1) == 1, f"{name} must be a matrix with unit column stride")
@@ -1626,11 +1636,7 @@ def _fill_linear_backward_args(a, dy, codes, qscale, gscale, L, R, dx, *, m, n, 
     need(dy.shape[1] == m and tuple(dx.shape) == (dy.shape[0], n), f"dy {tuple(dy.shape)} / dx {tuple(dx.shape)} do not "
          f"fit (tokens, {m}) / (tokens, {n})")
     need(dx.dtype in (torch.float32, torch.float16), f"dx must be fp32 or fp16, got {dx.dtype}")
-    if fp16:
-        need(all(t.dtype == torch.float16 for _, t in fp16),
-             "L and R must be fp16, got " + ", ".join(str(t.dtype) for _, t in fp16))
-        need(all(tuple(t.shape) == ((m, r) if name == "L" else (r, n)) for name, t in fp16),
-             " / ".join(f"{name} {tuple(t.shape)}" for name, t in fp16) + f" do not fit {(m, r)} / {(r, n)}")
+    _check_fp16_factors(fp16, m, r, n)
     a.dy, a.lddy = dy.data_ptr(), dy.stride(0)
     a.tokens, a.m, a.n, a.r = dy.shape[0], m, n, r
     a.bits = bits
@@ -1654,12 +1660,7 @@ def linear_backward_input(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, u_
     cq_linear_backward_workspace bytes (allocated here when None).  No host synchronisation."""
     _require_hip(dy, codes, L, R, dx, u_out)
     a = linear_backward_args(dy, codes, qscale, gscale, L, R, dx, m=m, n=n, bits=bits, u_out=u_out)
-    lib = load()
-    if ws is None:
-        ws = workspace(lib.cq_linear_backward_workspace(ctypes.byref(a)), dy.device)
-    _check(lib.cq_linear_backward_input(ctypes.byref(a), _p(ws), ws.numel(), _stream(dy.device)),
-           "cq_linear_backward_input")
-    return dx
+    return _run("cq_linear_backward_input", "cq_linear_backward_workspace", a, dx, dy.device, ws)
 
 
 def linear_packed_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, r=None, L_codes=None,
@@ -1668,29 +1669,11 @@ def linear_packed_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bi
     instead of fp16.  L_codes / R_codes: (uint8 inference-layout codes with one row per m resp. r,
     scale, bits in {2, 4}); the fp16 L / R of a coded factor is None.  r: the rank, needed when both
     factors are coded (else taken from the fp16 one).  into: the struct to fill (a codebook struct's `p`)."""
-    need = _linear_need
-    if r is None:
-        need(L is not None or R is not None or (L_codes is None and R_codes is None),
-             "r is needed when both factors are coded")
-        r = L.shape[1] if L is not None else R.shape[0] if R is not None else 0
-    r = int(r)
-    if r:
-        need((L is None) != (L_codes is None), "give exactly one of L and L_codes")
-        need((R is None) != (R_codes is None), "give exactly one of R and R_codes")
+    r = _resolve_rank(L, R, L_codes, R_codes, r)
     a = _fill_linear_backward_args(LinearPackedBackwardArgs() if into is None else into, dy, codes, qscale, gscale, L,
                                    R, dx, m=m, n=n, bits=bits, r=r, u_out=u_out, L_coded=L_codes is not None,
                                    R_coded=R_codes is not None)
-    a.l_bits = a.r_bits = 16
-    for what, spec, rows in (("L", L_codes, m), ("R", R_codes, r)):
-        if spec is None or not r:
-            continue
-        t, scale, fbits = spec
-        need(t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.uint8 and t.shape[0] == rows,
-             f"{what}_codes must be a uint8 matrix with {rows} rows and unit column stride")
-        setattr(a, what.lower() + "_bits", int(fbits))
-        setattr(a, what + "_codes", t.data_ptr())
-        setattr(a, what.lower() + "_code_stride", t.stride(0))
-        setattr(a, what.lower() + "scale", float(scale))
+    _fill_factor_codes(a, L_codes, R_codes, m, r)
     return a
 
 
@@ -1700,16 +1683,10 @@ def linear_packed_backward_input(dy, codes, qscale, gscale, L, R, dx, *, m, n, b
     (cq_linear_packed_backward_input); operands as `linear_packed_backward_args`.  u_out (T, r) fp32
     receives u~ = uscale dy lam, which carries a coded R's scale.  ws as `linear_backward_input`.  No
     host synchronisation."""
-    _require_hip(dy, codes, L, R, dx, u_out, None if L_codes is None else L_codes[0],
-                 None if R_codes is None else R_codes[0])
+    _require_hip(dy, codes, L, R, dx, u_out, *_factor_code_tensors(L_codes, R_codes))
     a = linear_packed_backward_args(dy, codes, qscale, gscale, L, R, dx, m=m, n=n, bits=bits, r=r, L_codes=L_codes,
                                     R_codes=R_codes, u_out=u_out)
-    lib = load()
-    if ws is None:
-        ws = workspace(lib.cq_linear_packed_backward_workspace(ctypes.byref(a)), dy.device)
-    _check(lib.cq_linear_packed_backward_input(ctypes.byref(a), _p(ws), ws.numel(), _stream(dy.device)),
-           "cq_linear_packed_backward_input")
-    return dx
+    return _run("cq_linear_packed_backward_input", "cq_linear_packed_backward_workspace", a, dx, dy.device, ws)
 
 
 def linear_codebook_backward_args(dy, codes, qscale, gscale, L, R, dx, *, m, n, bits, q_format, r=None, L_codes=None,
@@ -1729,16 +1706,10 @@ def linear_codebook_backward_input(dy, codes, qscale, gscale, L, R, dx, *, m, n,
     """dx = dy (gs (Q + L R)) with Q in q_format (cq_linear_codebook_backward_input); operands as
     `linear_codebook_backward_args`, u_out and ws as `linear_packed_backward_input`.  No host
     synchronisation."""
-    _require_hip(dy, codes, L, R, dx, u_out, None if L_codes is None else L_codes[0],
-                 None if R_codes is None else R_codes[0])
+    _require_hip(dy, codes, L, R, dx, u_out, *_factor_code_tensors(L_codes, R_codes))
     a = linear_codebook_backward_args(dy, codes, qscale, gscale, L, R, dx, m=m, n=n, bits=bits, q_format=q_format,
                                       r=r, L_codes=L_codes, R_codes=R_codes, u_out=u_out)
-    lib = load()
-    if ws is None:
-        ws = workspace(lib.cq_linear_codebook_backward_workspace(ctypes.byref(a)), dy.device)
-    _check(lib.cq_linear_codebook_backward_input(ctypes.byref(a), _p(ws), ws.numel(), _stream(dy.device)),
-           "cq_linear_codebook_backward_input")
-    return dx
+    return _run("cq_linear_codebook_backward_input", "cq_linear_codebook_backward_workspace", a, dx, dy.device, ws)
 
 
 def linear_dequant_args(codes, qscale, gscale, L, R, w, *, m, n, bits, q_format, r=None, L_codes=None,
@@ -1750,25 +1721,14 @@ def linear_dequant_args(codes, qscale, gscale, L, R, w, *, m, n, bits, q_format,
     packed and codebook builders' host-side checks."""
     need = _linear_need
     _check_q_format(q_format, qscale)
-    if r is None:
-        need(L is not None or R is not None or (L_codes is None and R_codes is None),
-             "r is needed when both factors are coded")
-        r = L.shape[1] if L is not None else R.shape[0] if R is not None else 0
-    r = int(r)
-    if r:
-        need((L is None) != (L_codes is None), "give exactly one of L and L_codes")
-        need((R is None) != (R_codes is None), "give exactly one of R and R_codes")
-    fp16 = ((("L", L),) if r and L_codes is None else ()) + ((("R", R),) if r and R_codes is None else ())
+    r = _resolve_rank(L, R, L_codes, R_codes, r)
+    fp16 = _fp16_factors(L, R, r, L_codes is not None, R_codes is not None)
     for name, t in (("codes", codes), ("w", w)) + fp16:
         need(t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1), f"{name} must be a matrix with unit column stride")
     need(codes.dtype == torch.uint8 and codes.shape[0] == m, "codes must be uint8 with one row per output")
     need(tuple(w.shape) == (m, n), f"w {tuple(w.shape)} does not fit {(m, n)}")
     need(w.dtype in _ACT_DT, f"w must be fp32, fp16 or bf16, got {w.dtype}")
-    if fp16:
-        need(all(t.dtype == torch.float16 for _, t in fp16),
-             "L and R must be fp16, got " + ", ".join(str(t.dtype) for _, t in fp16))
-        need(all(tuple(t.shape) == ((m, r) if name == "L" else (r, n)) for name, t in fp16),
-             " / ".join(f"{name} {tuple(t.shape)}" for name, t in fp16) + f" do not fit {(m, r)} / {(r, n)}")
+    _check_fp16_factors(fp16, m, r, n)
     a = LinearDequantArgs()
     a.m, a.n, a.r = m, n, r
     a.bits, a.q_format = bits, int(q_format)
@@ -1777,17 +1737,7 @@ def linear_dequant_args(codes, qscale, gscale, L, R, w, *, m, n, bits, q_format,
     for name, t in fp16:
         setattr(a, name, t.data_ptr())
         setattr(a, "ld" + name.lower(), t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
-    a.l_bits = a.r_bits = 16
-    for what, spec, rows in (("L", L_codes, m), ("R", R_codes, r)):
-        if spec is None or not r:
-            continue
-        t, scale, fbits = spec
-        need(t.dim() == 2 and t.stride(1) == 1 and t.dtype == torch.uint8 and t.shape[0] == rows,
-             f"{what}_codes must be a uint8 matrix with {rows} rows and unit column stride")
-        setattr(a, what.lower() + "_bits", int(fbits))
-        setattr(a, what + "_codes", t.data_ptr())
-        setattr(a, what.lower() + "_code_stride", t.stride(0))
-        setattr(a, what.lower() + "scale", float(scale))
+    _fill_factor_codes(a, L_codes, R_codes, m, r)
     a.w, a.w_dtype = w.data_ptr(), _ACT_DT[w.dtype]
     a.ldw = w.stride(0) if m > 1 else max(w.stride(0), n)
     return a
@@ -1796,7 +1746,7 @@ def linear_dequant_args(codes, qscale, gscale, L, R, w, *, m, n, bits, q_format,
 def linear_dequant(codes, qscale, gscale, L, R, w, *, m, n, bits, q_format, r=None, L_codes=None, R_codes=None):
     """w = gs (Q + L R), the dense weight of a packed layer (cq_linear_dequant); operands as
     `linear_dequant_args`.  No workspace, no host synchronisation."""
-    _require_hip(codes, L, R, w, None if L_codes is None else L_codes[0], None if R_codes is None else R_codes[0])
+    _require_hip(codes, L, R, w, *_factor_code_tensors(L_codes, R_codes))
     a = linear_dequant_args(codes, qscale, gscale, L, R, w, m=m, n=n, bits=bits, q_format=q_format, r=r,
                             L_codes=L_codes, R_codes=R_codes)
     _check(load().cq_linear_dequant(ctypes.byref(a), _stream(w.device)), "cq_linear_dequant")

@@ -33,7 +33,8 @@ STAMP = OUT + ".srchash"  # content hash of the sources the .so was built from
 
 
 def _deps():
-    return ([os.path.join(CSRC, s) for s in SOURCES + ["cq_common.h", "cq_x3.h", "cq_x3_tile.h", "cq_nf.h", "cq_linear_tile.h"]]
+    headers = ["cq_common.h", "cq_x3.h", "cq_x3_tile.h", "cq_nf.h", "cq_linear_tile.h", "cq_codes.h", "cq_linear_host.h"]
+    return ([os.path.join(CSRC, s) for s in SOURCES + headers]
             + [os.path.join(HERE, "..", "include", "caldera_hip.h")])
 
 

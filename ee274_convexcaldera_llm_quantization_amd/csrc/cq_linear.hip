@@ -46,16 +46,13 @@
 #include <cstdio>
 #include <type_traits>
 
+#include "cq_codes.h"
 #include "cq_common.h"
+#include "cq_linear_host.h"
 #include "cq_nf.h"
 
 namespace cq {
 namespace {
-
-using h8 = __attribute__((ext_vector_type(8))) _Float16;
-using h2 = __attribute__((ext_vector_type(2))) _Float16;
-using f4 = __attribute__((ext_vector_type(4))) float;
-using u4 = __attribute__((ext_vector_type(4))) uint32_t;
 
 constexpr int kDecodeMax = CQ_LINEAR_DECODE_MAX_TOKENS;
 constexpr int kDecodeWaves = 8;    // K split of a decode workgroup (chunks interleaved over its waves)
@@ -92,52 +89,11 @@ __device__ __forceinline__ const LinP& member(const GroupP& g, int off) {
     return *reinterpret_cast<const LinP*>(reinterpret_cast<const char*>(g.m) + off);
 }
 
-// elements k .. k + 7 of a row, zero at and beyond lim (lim = 0: nothing is read)
-__device__ __forceinline__ h8 ld8(const _Float16* row, int64_t k, int64_t lim, bool al) {
-    if (al && k + 8 <= lim) return *reinterpret_cast<const h8*>(row + k);
-    h8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (k < lim) {  // a ragged end or an unaligned row: element by element
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (k + j < lim) v[j] = row[k + j];
-    }
-    return v;
-}
-
-// fp16 magic numbers: 0x6400 | f is 1024 + f for a 10-bit field f, so a code field left where
-// it sits in the word (f = code << sh) becomes 1024 + (code << sh); one multiply by 2^-sh and
-// one subtraction of (1024 >> sh) + k, both exact in fp16, give code - k.
-__device__ __forceinline__ uint32_t pair(uint32_t uu, uint32_t mask) { return (uu & mask) | 0x64006400u; }
-__device__ __forceinline__ uint32_t scale_off(uint32_t p, h2 sc, h2 off) {
-    const h2 v = __builtin_bit_cast(h2, p) * sc + off;
-    return __builtin_bit_cast(uint32_t, v);
-}
-
-// B fragment jj of a lane's 16 bytes of codes (offset-binary, MSB-first): 8 consecutive codes
+// B fragment jj of a lane's 16 bytes of codes: 8 consecutive codes (cq_codes.h)
 template <int BITS>
 __device__ __forceinline__ h8 expand(const u4 q, int jj) {
-    u4 o;
-    if constexpr (BITS == 2) {
-        const uint32_t word = q[jj >> 1];
-        // both halves hold the fragment's two bytes
-        uint32_t uu = (jj & 1) ? ((word >> 16) | (word & 0xffff0000u)) : ((word & 0xffffu) | (word << 16));
-        const h2 sa = {(_Float16)(1.0f / 64), (_Float16)(1.0f / 16)}, oa = {(_Float16)-17.0f, (_Float16)-65.0f};
-        const h2 sb = {(_Float16)0.25f, (_Float16)1.0f}, ob = {(_Float16)-257.0f, (_Float16)-1025.0f};
-        o[0] = scale_off(pair(uu, 0x003000C0u), sa, oa);
-        o[1] = scale_off(pair(uu, 0x0003000Cu), sb, ob);
-        uu >>= 8;
-        o[2] = scale_off(pair(uu, 0x003000C0u), sa, oa);
-        o[3] = scale_off(pair(uu, 0x0003000Cu), sb, ob);
-    } else {
-        const uint32_t word = q[jj];
-        const uint32_t u0 = (word & 0xffffu) | (word << 16), u1 = (word >> 16) | (word & 0xffff0000u);
-        const h2 sa = {(_Float16)(1.0f / 16), (_Float16)1.0f}, oa = {(_Float16)-71.0f, (_Float16)-1031.0f};
-        o[0] = scale_off(pair(u0, 0x000F00F0u), sa, oa);
-        o[1] = scale_off(pair(u0 >> 8, 0x000F00F0u), sa, oa);
-        o[2] = scale_off(pair(u1, 0x000F00F0u), sa, oa);
-        o[3] = scale_off(pair(u1 >> 8, 0x000F00F0u), sa, oa);
-    }
-    return __builtin_bit_cast(h8, o);
+    if constexpr (BITS == 2) return expand<2>(q[jj >> 1], jj & 1);
+    else return expand<4>(q[jj], 0);
 }
 
 // WT: the weight rows of the K loop, 2 / 4 = packed codes, 16 = fp16.  ZP: the z product (the
@@ -499,10 +455,6 @@ linear_kernel(const ARG arg) {
 inline int64_t token_rows(int64_t T) {
     return T <= kDecodeMax ? 16 : ceil_div(T, kPrefillTiles * 16) * (kPrefillTiles * 16);
 }
-inline int64_t r32_of(int64_t r) { return ceil_div(r, 32) * 32; }
-inline bool al16(const void* ptr, int64_t ld_elems) {
-    return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld_elems % 8 == 0;
-}
 
 constexpr int kPrefillWaves = 4;   // waves per prefill workgroup (codes; the z product has one)
 
@@ -513,58 +465,67 @@ inline int64_t x_extent(const LinP& p) {
     return p.T <= kDecodeMax ? groups : ceil_div(groups, ZP ? 1 : kPrefillWaves * kPrefillGroups);
 }
 
-template <int WT, int QF, int LB, bool ZP>
-void launch(const LinP& p, hipStream_t s) {
-    if (p.T <= kDecodeMax) {
-        constexpr int NW = ZP ? kDecodeWavesZ : kDecodeWaves;
-        const dim3 grid((unsigned)x_extent<ZP>(p), ZP ? kDecodeSplitZ : 1);
-        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, 1, 1, NW, true, LinP>), grid, dim3(NW * 64), 0, s, p);
-    } else {
-        constexpr int NW = ZP ? 1 : kPrefillWaves, RG = ZP ? 1 : kPrefillGroups;
-        const dim3 grid((unsigned)x_extent<ZP>(p), (unsigned)ceil_div(p.T, kPrefillTiles * 16));
-        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, kPrefillTiles, RG, NW, false, LinP>), grid, dim3(NW * 64), 0, s,
-                           p);
-    }
-}
-
-template <int WT, int QF>
-void launch_layer(const LinP& p, int l_bits, hipStream_t s) {
-    if (l_bits == 2) launch<WT, QF, 2, false>(p, s);
-    else if (l_bits == 4) launch<WT, QF, 4, false>(p, s);
-    else launch<WT, QF, 16, false>(p, s);
-}
-
-// `count` layers (1 .. CQ_LINEAR_GROUP_MAX, the same T and template parameters, each with a nonempty
-// grid of its own) in one grid: the members' x extents end to end, the y extent they share
-template <int WT, int QF, int LB, bool ZP>
-void launch_group(const LinP* ps, int count, hipStream_t s) {
-    GroupP g{};
+// `count` layers in one grid.  ARG = LinP: the one layer ps[0] on its own grid.  ARG = GroupP: 1 ..
+// CQ_LINEAR_GROUP_MAX layers (the same T and template parameters, each with a nonempty grid of its
+// own), the members' x extents end to end, the y extent they share.
+template <int WT, int QF, int LB, bool ZP, typename ARG>
+void launch(const LinP* ps, int count, hipStream_t s) {
+    ARG arg{};
     int64_t total = 0;
-    for (int i = 0; i < CQ_LINEAR_GROUP_MAX; ++i) {
-        g.first[i] = i < count ? (int32_t)total : INT32_MAX;
-        if (i < count) {
-            g.m[i] = ps[i];
-            total += x_extent<ZP>(ps[i]);
+    if constexpr (std::is_same_v<ARG, GroupP>) {
+        for (int i = 0; i < CQ_LINEAR_GROUP_MAX; ++i) {
+            arg.first[i] = i < count ? (int32_t)total : INT32_MAX;
+            if (i < count) {
+                arg.m[i] = ps[i];
+                total += x_extent<ZP>(ps[i]);
+            }
         }
+    } else {
+        arg = ps[0];
+        total = x_extent<ZP>(ps[0]);
     }
     const int64_t T = ps[0].T;
     if (T <= kDecodeMax) {
         constexpr int NW = ZP ? kDecodeWavesZ : kDecodeWaves;
         const dim3 grid((unsigned)total, ZP ? kDecodeSplitZ : 1);
-        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, 1, 1, NW, true, GroupP>), grid, dim3(NW * 64), 0, s, g);
+        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, 1, 1, NW, true, ARG>), grid, dim3(NW * 64), 0, s, arg);
     } else {
         constexpr int NW = ZP ? 1 : kPrefillWaves, RG = ZP ? 1 : kPrefillGroups;
         const dim3 grid((unsigned)total, (unsigned)ceil_div(T, kPrefillTiles * 16));
-        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, kPrefillTiles, RG, NW, false, GroupP>), grid, dim3(NW * 64), 0,
-                           s, g);
+        hipLaunchKernelGGL((linear_kernel<WT, QF, LB, ZP, kPrefillTiles, RG, NW, false, ARG>), grid, dim3(NW * 64), 0, s,
+                           arg);
     }
 }
 
-template <int WT, int QF>
-void launch_group_layers(const LinP* ps, int count, int l_bits, hipStream_t s) {
-    if (l_bits == 2) launch_group<WT, QF, 2, false>(ps, count, s);
-    else if (l_bits == 4) launch_group<WT, QF, 4, false>(ps, count, s);
-    else launch_group<WT, QF, 16, false>(ps, count, s);
+// the z launch over the layers zs[0 .. count) with factors, R as fp16 rows (r_bits = 16) or codes
+template <typename ARG>
+int launch_z(const LinP* zs, int count, int r_bits, hipStream_t s, const char* who) {
+    if (r_bits == 16) launch<16, CQ_QFMT_UNIFORM, 16, true, ARG>(zs, count, s);
+    else if (r_bits == 2) launch<2, CQ_QFMT_UNIFORM, 16, true, ARG>(zs, count, s);
+    else launch<4, CQ_QFMT_UNIFORM, 16, true, ARG>(zs, count, s);
+    char what[64];
+    snprintf(what, sizeof what, "%s (z)", who);
+    return check_launch(what);
+}
+
+// the runtime triple (bits, nf, l_bits) of a code + L launch as template arguments: calls
+// f(WT, QF, LB) with integral constants
+template <int V>
+using Const = std::integral_constant<int, V>;
+template <class F>
+void with_formats(int bits, bool nf, int l_bits, F f) {
+    auto with_lb = [&](auto wt, auto qf) {
+        if (l_bits == 2) f(wt, qf, Const<2>{});
+        else if (l_bits == 4) f(wt, qf, Const<4>{});
+        else f(wt, qf, Const<16>{});
+    };
+    if (nf) {
+        if (bits == 2) with_lb(Const<2>{}, Const<CQ_QFMT_NF>{});
+        else with_lb(Const<4>{}, Const<CQ_QFMT_NF>{});
+    } else {
+        if (bits == 2) with_lb(Const<2>{}, Const<CQ_QFMT_UNIFORM>{});
+        else with_lb(Const<4>{}, Const<CQ_QFMT_UNIFORM>{});
+    }
 }
 
 // Gated pair (cq_linear_glu_forward): h = act(v_g) * v_u with v_g, v_u the fp32 values linear_kernel's
@@ -919,56 +880,23 @@ void launch_glu(const GluP& a, hipStream_t s) {
     }
 }
 
-template <int WT, int QF>
-void launch_glu_layers(const GluP& a, int l_bits, hipStream_t s) {
-    if (l_bits == 2) launch_glu<WT, QF, 2>(a, s);
-    else if (l_bits == 4) launch_glu<WT, QF, 4>(a, s);
-    else launch_glu<WT, QF, 16>(a, s);
-}
-
-inline bool coded(int bits) { return bits == 2 || bits == 4; }
-inline float kmax(int bits) { return (float)((1 << (bits - 1)) - 1); }
-
-// one factor's codes: rows of `cols` codes in the inference layout, one finite scale >= 0
-int validate_factor(const char* name, int bits, const uint8_t* codes, int64_t stride, int64_t cols, float scale) {
-    CQ_REQUIRE(codes != nullptr, "cq_linear: null %s codes with %s bits = %d", name, name, bits);
-    CQ_REQUIRE((reinterpret_cast<uintptr_t>(codes) & 15) == 0 && stride % 16 == 0,
-               "cq_linear: %s codes and their row stride must be 16-byte aligned (inference layout)", name);
-    CQ_REQUIRE(stride >= (cols * bits + 7) / 8, "cq_linear: %s code row stride %lld < %lld bytes", name,
-               (long long)stride, (long long)((cols * bits + 7) / 8));
-    CQ_REQUIRE(std::isfinite(scale) && scale >= 0.f, "cq_linear: %s scale %g is not finite and >= 0", name, (double)scale);
-    return CQ_OK;
-}
-
 // with_y = false: y, y_dtype and ldy are neither used nor checked (a member of cq_linear_glu_args)
 int validate(const cq_linear_packed_args* a, bool with_y = true) {
+    const char* who = "cq_linear";
     CQ_REQUIRE(a != nullptr, "cq_linear: null args");
     CQ_REQUIRE(a->bits == 2 || a->bits == 4, "cq_linear: bits %d not in {2, 4}", a->bits);
-    CQ_REQUIRE((coded(a->l_bits) || a->l_bits == 16) && (coded(a->r_bits) || a->r_bits == 16),
-               "cq_linear: factor bits L %d / R %d not in {2, 4, 16}", a->l_bits, a->r_bits);
+    if (int st = validate_factor_bits(who, a->l_bits, a->r_bits)) return st;
     const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
     CQ_REQUIRE(a->tokens >= 0 && a->m > 0 && a->n > 0 && a->r >= 0, "cq_linear: bad shape tokens=%lld m=%lld n=%lld r=%lld",
                (long long)a->tokens, (long long)a->m, (long long)a->n, (long long)a->r);
-    CQ_REQUIRE(a->r <= CQ_LINEAR_MAX_RANK, "cq_linear: rank %lld > %d", (long long)a->r, CQ_LINEAR_MAX_RANK);
+    if (int st = validate_rank(who, a->r)) return st;
     CQ_REQUIRE(a->tokens <= (int64_t)65535 * 64 && a->m <= ((int64_t)1 << 31), "cq_linear: shape too large");
     CQ_REQUIRE(!with_y || a->y_dtype == CQ_F32 || a->y_dtype == CQ_F16, "cq_linear: y dtype %d not fp32 / fp16",
                a->y_dtype);
     CQ_REQUIRE(a->x && a->codes && (!with_y || a->y), "cq_linear: null x / codes / y");
-    CQ_REQUIRE(a->r == 0 || ((lcoded || a->L) && (rcoded || a->R)), "cq_linear: null L / R with r = %lld",
-               (long long)a->r);
-    if (lcoded)
-        if (int st = validate_factor("L", a->l_bits, a->L_codes, a->l_code_stride, a->r, a->lscale)) return st;
-    if (rcoded)
-        if (int st = validate_factor("R", a->r_bits, a->R_codes, a->r_code_stride, a->n, a->rscale)) return st;
-    CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->codes) & 15) == 0 && a->code_stride % 16 == 0,
-               "cq_linear: codes and their row stride must be 16-byte aligned (inference layout)");
-    CQ_REQUIRE(a->code_stride >= (a->n * a->bits + 7) / 8, "cq_linear: code row stride %lld < %lld bytes",
-               (long long)a->code_stride, (long long)((a->n * a->bits + 7) / 8));
-    CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->x) & 1) == 0 && (reinterpret_cast<uintptr_t>(a->L) & 1) == 0 &&
-                   (reinterpret_cast<uintptr_t>(a->R) & 1) == 0,
-               "cq_linear: misaligned fp16 pointer");
-    CQ_REQUIRE((!with_y || (reinterpret_cast<uintptr_t>(a->y) & (a->y_dtype == CQ_F16 ? 1 : 3)) == 0) &&
-                   (reinterpret_cast<uintptr_t>(a->bias) & 3) == 0,
+    if (int st = validate_operands(a, who, lcoded, rcoded)) return st;
+    if (int st = validate_fp16_pointers(who, a->x, a->L, a->R)) return st;
+    CQ_REQUIRE((!with_y || !misaligned(a->y, a->y_dtype == CQ_F16 ? 1 : 3)) && !misaligned(a->bias, 3),
                "cq_linear: misaligned y / bias pointer");
     CQ_REQUIRE(a->ldx >= a->n && (!with_y || a->ldy >= a->m) &&
                    (a->r == 0 || ((lcoded || a->ldl >= a->r) && (rcoded || a->ldr >= a->n))),
@@ -998,18 +926,9 @@ cq_linear_packed_args with_fp16_factors(const cq_linear_args* a) {
     return b;
 }
 
-int check_workspace(size_t need, const void* ws, size_t ws_bytes, const char* who) {
-    if (need) {
-        CQ_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
-                   "%s: workspace must be 16-byte aligned", who);
-        if (ws_bytes < need) return set_error(CQ_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
-    }
-    return CQ_OK;
-}
-
 // The kernels' parameters of one validated layer on its own workspace ws: z, the z product (used
-// for r > 0 only), and p, codes + L + epilogue.  Shared by the single-layer and the grouped entry,
-// so a grouped member's parameters are the ones it runs with alone.
+// for r > 0 only), and p, codes + L + epilogue.  Shared by every entry, so a grouped member's
+// parameters are the ones it runs with alone.
 void layer_params(const cq_linear_packed_args* a, bool nf, void* ws, LinP& z, LinP& p) {
     const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
     p = LinP{};
@@ -1022,10 +941,7 @@ void layer_params(const cq_linear_packed_args* a, bool nf, void* ws, LinP& z, Li
     p.r32 = r32_of(a->r);
     _Float16* zh = reinterpret_cast<_Float16*>(ws);
     _Float16* zl = zh ? zh + token_rows(a->tokens) * p.r32 : nullptr;
-    // the coded factors' scale / k (one fp32 division each), multiplied in fp32
-    p.zscale = 1.0f;
-    if (lcoded) p.zscale = a->lscale / kmax(a->l_bits);
-    if (rcoded) p.zscale = lcoded ? p.zscale * (a->rscale / kmax(a->r_bits)) : a->rscale / kmax(a->r_bits);
+    p.zscale = factor_scale(a, lcoded, rcoded);
     z = p;  // z = x R^T as split halves
     if (a->r > 0) {
         z.rows = a->r;
@@ -1055,8 +971,7 @@ void layer_params(const cq_linear_packed_args* a, bool nf, void* ws, LinP& z, Li
     p.zp = reinterpret_cast<const float*>(ws);
     p.zh = zh;
     p.zl = zl;
-    // one fp32 division: s / k, or s / D with the level table's denominator
-    p.sk = a->qscale / (nf ? (a->bits == 4 ? kNF4D : kNF2D) : kmax(a->bits));
+    p.sk = code_scale(a->qscale, a->bits, nf);
     p.gs = a->gscale;
     p.bias = a->bias;
     p.y = a->y;
@@ -1064,55 +979,104 @@ void layer_params(const cq_linear_packed_args* a, bool nf, void* ws, LinP& z, Li
     p.ldy = a->ldy;
 }
 
-int validate_format(const cq_linear_packed_args* a, int q_format, const char* who) {
-    CQ_REQUIRE(q_format == CQ_QFMT_UNIFORM || q_format == CQ_QFMT_NF, "%s: unknown q_format %d", who, q_format);
-    CQ_REQUIRE(q_format != CQ_QFMT_NF || (std::isfinite(a->qscale) && a->qscale >= 0.f),
-               "%s: NF scale %g is not finite and >= 0", who, (double)a->qscale);
+// the layers of one call, in member order: the one layer, a group's members, or a pair's gate and up
+struct Members {
+    const cq_linear_packed_args* m[CQ_LINEAR_GROUP_MAX];
+    int count;
+};
+Members members_of(const cq_linear_group_args* g) {
+    Members ms{};
+    for (ms.count = 0; ms.count < g->count; ++ms.count) ms.m[ms.count] = &g->members[ms.count];
+    return ms;
+}
+Members members_of(const cq_linear_glu_args* a) { return Members{{&a->gate, &a->up}, 2}; }
+
+// the call's workspace: the members' own, at 16-byte aligned offsets (offs, may be null) in member order
+size_t group_offsets(const Members& ms, size_t* offs) {
+    size_t total = 0;
+    for (int i = 0; i < ms.count; ++i) {
+        if (offs) offs[i] = total;
+        total += align_up(workspace_bytes(ms.m[i]->tokens, ms.m[i]->r), 16);
+    }
+    return total;
+}
+
+// The kernels' parameters of validated members on the workspace ws: ps[i] is member i's, zs[0 .. nz)
+// the z products of the members with factors, whose formats l_bits / r_bits are (validate_members:
+// all the same; 16 = fp16 rows).
+void prepare_members(const Members& ms, bool nf, void* ws, const size_t* offs, LinP* zs, LinP* ps, int& nz, int& l_bits,
+                     int& r_bits) {
+    nz = 0, l_bits = r_bits = 16;
+    for (int i = 0; i < ms.count; ++i) {
+        const cq_linear_packed_args* a = ms.m[i];
+        LinP z;
+        layer_params(a, nf, static_cast<char*>(ws) + offs[i], z, ps[i]);
+        if (a->r > 0) {
+            zs[nz++] = z;
+            l_bits = coded(a->l_bits) ? a->l_bits : 16;
+            r_bits = coded(a->r_bits) ? a->r_bits : 16;
+        }
+    }
+}
+
+// What the members of a group or a pair must pass, decided on the host before any launch: each its
+// own checks (its message with `entry` and its name in front) and q_format's, then the fields that
+// all share with the first member, and the factor formats with the first member that has factors.
+int validate_members(const char* entry, const char* const* names, const Members& ms, int q_format, bool with_y,
+                     bool same_m) {
+    int ranked = -1;  // the first member with factors
+    for (int i = 0; i < ms.count; ++i) {
+        const cq_linear_packed_args* a = ms.m[i];
+        char who[64];
+        snprintf(who, sizeof who, "%s: %s", entry, names[i]);
+        if (int st = validate(a, with_y)) {
+            char msg[400];
+            snprintf(msg, sizeof msg, "%s", cq_last_error());
+            return set_error(st, "%s: %s", who, msg);
+        }
+        if (int st = validate_format(who, q_format, a->qscale)) return st;
+#define CQ_SAME(field, fmt, cast, ref)                                                                           \
+    CQ_REQUIRE(a->field == ms.m[ref]->field, "%s: " #field " " fmt " differs from %s's " fmt, who, (cast)a->field, \
+               names[ref], (cast)ms.m[ref]->field)
+        CQ_SAME(x, "%p", const void*, 0);
+        CQ_SAME(ldx, "%lld", long long, 0);
+        CQ_SAME(tokens, "%lld", long long, 0);
+        CQ_SAME(n, "%lld", long long, 0);
+        if (same_m) CQ_SAME(m, "%lld", long long, 0);
+        CQ_SAME(bits, "%d", int, 0);
+        if (with_y) CQ_SAME(y_dtype, "%d", int, 0);
+        if (a->r > 0) {
+            if (ranked < 0) ranked = i;
+            CQ_SAME(l_bits, "%d", int, ranked);
+            CQ_SAME(r_bits, "%d", int, ranked);
+        }
+#undef CQ_SAME
+    }
     return CQ_OK;
 }
 
 int forward(const cq_linear_packed_args* a, int q_format, void* ws, size_t ws_bytes, void* stream, const char* who) {
     if (int st = validate(a)) return st;
-    if (int st = validate_format(a, q_format, who)) return st;
-    const bool nf = q_format == CQ_QFMT_NF;
+    if (int st = validate_format(who, q_format, a->qscale)) return st;
     if (a->tokens == 0) return CQ_OK;
     if (int st = check_workspace(workspace_bytes(a->tokens, a->r), ws, ws_bytes, who)) return st;
-    const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
     hipStream_t s = as_stream(stream);
+    const size_t off = 0;
     LinP z, p;
-    layer_params(a, nf, ws, z, p);
-    if (a->r > 0) {
-        if (!rcoded) launch<16, CQ_QFMT_UNIFORM, 16, true>(z, s);
-        else if (a->r_bits == 2) launch<2, CQ_QFMT_UNIFORM, 16, true>(z, s);
-        else launch<4, CQ_QFMT_UNIFORM, 16, true>(z, s);
-        char what[64];
-        snprintf(what, sizeof what, "%s (z)", who);
-        if (int st = check_launch(what)) return st;
-    }
-    const int l_bits = lcoded ? a->l_bits : 16;
-    if (nf) {
-        if (a->bits == 2) launch_layer<2, CQ_QFMT_NF>(p, l_bits, s);
-        else launch_layer<4, CQ_QFMT_NF>(p, l_bits, s);
-    } else {
-        if (a->bits == 2) launch_layer<2, CQ_QFMT_UNIFORM>(p, l_bits, s);
-        else launch_layer<4, CQ_QFMT_UNIFORM>(p, l_bits, s);
-    }
+    int nz, l_bits, r_bits;
+    prepare_members(Members{{a}, 1}, q_format == CQ_QFMT_NF, ws, &off, &z, &p, nz, l_bits, r_bits);
+    if (nz > 0)
+        if (int st = launch_z<LinP>(&z, 1, r_bits, s, who)) return st;
+    with_formats(a->bits, q_format == CQ_QFMT_NF, l_bits,
+                 [&](auto wt, auto qf, auto lb) { launch<wt(), qf(), lb(), false, LinP>(&p, 1, s); });
     return check_launch(who);
 }
 
 constexpr const char* kGroupWho = "cq_linear_group_forward";
+constexpr const char* kGroupNames[] = {"member 0", "member 1", "member 2", "member 3",
+                                       "member 4", "member 5", "member 6", "member 7"};
+static_assert(sizeof kGroupNames / sizeof *kGroupNames == CQ_LINEAR_GROUP_MAX, "one name per member");
 
-// the group's workspace: the members' own, at 16-byte aligned offsets (offs, may be null) in member order
-size_t group_offsets(const cq_linear_group_args* g, size_t* offs) {
-    size_t total = 0;
-    for (int i = 0; i < g->count; ++i) {
-        if (offs) offs[i] = total;
-        total += align_up(workspace_bytes(g->members[i].tokens, g->members[i].r), 16);
-    }
-    return total;
-}
-
-// cq_linear_group_forward's decision, made on the host before any launch
 int validate_group(const cq_linear_group_args* g) {
     CQ_REQUIRE(g != nullptr, "%s: null args", kGroupWho);
     CQ_REQUIRE(g->count >= 1 && g->count <= CQ_LINEAR_GROUP_MAX, "%s: count %d not in 1 .. %d", kGroupWho, g->count,
@@ -1120,167 +1084,63 @@ int validate_group(const cq_linear_group_args* g) {
     CQ_REQUIRE(g->members != nullptr, "%s: null members", kGroupWho);
     CQ_REQUIRE(g->q_format == CQ_QFMT_UNIFORM || g->q_format == CQ_QFMT_NF, "%s: unknown q_format %d", kGroupWho,
                g->q_format);
-    const cq_linear_packed_args* a0 = &g->members[0];
-    const cq_linear_packed_args* ranked = nullptr;  // the first member with factors
-    int ranked_i = -1;
-    for (int i = 0; i < g->count; ++i) {
-        const cq_linear_packed_args* a = &g->members[i];
-        char who[64];
-        snprintf(who, sizeof who, "%s: member %d", kGroupWho, i);
-        if (int st = validate(a)) {  // the member's own message, with its index in front
-            char msg[400];
-            snprintf(msg, sizeof msg, "%s", cq_last_error());
-            return set_error(st, "%s: %s", who, msg);
-        }
-        if (int st = validate_format(a, g->q_format, who)) return st;
-#define CQ_GROUP_SAME(field, fmt, cast)                                                                            \
-    CQ_REQUIRE(a->field == a0->field, "%s: " #field " " fmt " differs from member 0's " fmt, who, (cast)a->field, \
-               (cast)a0->field)
-        CQ_GROUP_SAME(x, "%p", const void*);
-        CQ_GROUP_SAME(ldx, "%lld", long long);
-        CQ_GROUP_SAME(tokens, "%lld", long long);
-        CQ_GROUP_SAME(n, "%lld", long long);
-        CQ_GROUP_SAME(bits, "%d", int);
-        CQ_GROUP_SAME(y_dtype, "%d", int);
-#undef CQ_GROUP_SAME
-        if (a->r > 0) {
-            if (!ranked) ranked = a, ranked_i = i;
-            CQ_REQUIRE(a->l_bits == ranked->l_bits, "%s: l_bits %d differs from member %d's %d", who, a->l_bits,
-                       ranked_i, ranked->l_bits);
-            CQ_REQUIRE(a->r_bits == ranked->r_bits, "%s: r_bits %d differs from member %d's %d", who, a->r_bits,
-                       ranked_i, ranked->r_bits);
-        }
-    }
-    return CQ_OK;
+    return validate_members(kGroupWho, kGroupNames, members_of(g), g->q_format, true, false);
 }
 
 int group_forward(const cq_linear_group_args* g, void* ws, size_t ws_bytes, void* stream) {
     if (int st = validate_group(g)) return st;
     if (g->members[0].tokens == 0) return CQ_OK;
+    const Members ms = members_of(g);
     size_t offs[CQ_LINEAR_GROUP_MAX];
-    if (int st = check_workspace(group_offsets(g, offs), ws, ws_bytes, kGroupWho)) return st;
+    if (int st = check_workspace(group_offsets(ms, offs), ws, ws_bytes, kGroupWho)) return st;
     const bool nf = g->q_format == CQ_QFMT_NF;
     hipStream_t s = as_stream(stream);
     LinP zs[CQ_LINEAR_GROUP_MAX], ps[CQ_LINEAR_GROUP_MAX];
-    int nz = 0, l_bits = 16, r_bits = 16;
-    for (int i = 0; i < g->count; ++i) {
-        const cq_linear_packed_args* a = &g->members[i];
-        LinP z;
-        layer_params(a, nf, static_cast<char*>(ws) + offs[i], z, ps[i]);
-        if (a->r > 0) {  // the factor formats are the ranked members' (validate_group: all the same)
-            zs[nz++] = z;
-            l_bits = coded(a->l_bits) ? a->l_bits : 16;
-            r_bits = coded(a->r_bits) ? a->r_bits : 16;
-        }
-    }
-    if (nz > 0) {  // one z launch over the members with factors
-        if (r_bits == 16) launch_group<16, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
-        else if (r_bits == 2) launch_group<2, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
-        else launch_group<4, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
-        if (int st = check_launch("cq_linear_group_forward (z)")) return st;
-    }
-    const int bits = g->members[0].bits;
-    if (nf) {
-        if (bits == 2) launch_group_layers<2, CQ_QFMT_NF>(ps, g->count, l_bits, s);
-        else launch_group_layers<4, CQ_QFMT_NF>(ps, g->count, l_bits, s);
-    } else {
-        if (bits == 2) launch_group_layers<2, CQ_QFMT_UNIFORM>(ps, g->count, l_bits, s);
-        else launch_group_layers<4, CQ_QFMT_UNIFORM>(ps, g->count, l_bits, s);
-    }
+    int nz, l_bits, r_bits;
+    prepare_members(ms, nf, ws, offs, zs, ps, nz, l_bits, r_bits);
+    if (nz > 0)  // one z launch over the members with factors
+        if (int st = launch_z<GroupP>(zs, nz, r_bits, s, kGroupWho)) return st;
+    with_formats(ms.m[0]->bits, nf, l_bits,
+                 [&](auto wt, auto qf, auto lb) { launch<wt(), qf(), lb(), false, GroupP>(ps, ms.count, s); });
     return check_launch(kGroupWho);
 }
 
 constexpr const char* kGluWho = "cq_linear_glu_forward";
+constexpr const char* kGluNames[] = {"gate", "up"};
 
-inline const cq_linear_packed_args* glu_member(const cq_linear_glu_args* a, int i) { return i ? &a->up : &a->gate; }
-
-// the pair's workspace: the grouped entry's layout for the two members gate, up
-size_t glu_offsets(const cq_linear_glu_args* a, size_t* offs) {
-    size_t total = 0;
-    for (int i = 0; i < 2; ++i) {
-        if (offs) offs[i] = total;
-        total += align_up(workspace_bytes(glu_member(a, i)->tokens, glu_member(a, i)->r), 16);
-    }
-    return total;
-}
-
-// cq_linear_glu_forward's decision, made on the host before any launch
 int validate_glu(const cq_linear_glu_args* a) {
     CQ_REQUIRE(a != nullptr, "%s: null args", kGluWho);
     CQ_REQUIRE(a->q_format == CQ_QFMT_UNIFORM || a->q_format == CQ_QFMT_NF, "%s: unknown q_format %d", kGluWho,
                a->q_format);
     CQ_REQUIRE(a->act == CQ_ACT_IDENTITY || a->act == CQ_ACT_SILU, "%s: unknown act %d", kGluWho, a->act);
     CQ_REQUIRE(a->h_dtype == CQ_F32 || a->h_dtype == CQ_F16, "%s: h_dtype %d not fp32 / fp16", kGluWho, a->h_dtype);
-    const cq_linear_packed_args* g = &a->gate;
-    for (int i = 0; i < 2; ++i) {
-        const cq_linear_packed_args* m = glu_member(a, i);
-        char who[64];
-        snprintf(who, sizeof who, "%s: %s", kGluWho, i ? "up" : "gate");
-        if (int st = validate(m, false)) {  // the member's own message, with its name in front
-            char msg[400];
-            snprintf(msg, sizeof msg, "%s", cq_last_error());
-            return set_error(st, "%s: %s", who, msg);
-        }
-        if (int st = validate_format(m, a->q_format, who)) return st;
-#define CQ_GLU_SAME(field, fmt, cast) \
-    CQ_REQUIRE(m->field == g->field, "%s: " #field " " fmt " differs from gate's " fmt, who, (cast)m->field, (cast)g->field)
-        CQ_GLU_SAME(x, "%p", const void*);
-        CQ_GLU_SAME(ldx, "%lld", long long);
-        CQ_GLU_SAME(tokens, "%lld", long long);
-        CQ_GLU_SAME(n, "%lld", long long);
-        CQ_GLU_SAME(m, "%lld", long long);
-        CQ_GLU_SAME(bits, "%d", int);
-        if (m->r > 0 && g->r > 0) {
-            CQ_GLU_SAME(l_bits, "%d", int);
-            CQ_GLU_SAME(r_bits, "%d", int);
-        }
-#undef CQ_GLU_SAME
-    }
+    if (int st = validate_members(kGluWho, kGluNames, members_of(a), a->q_format, false, true)) return st;
     CQ_REQUIRE(a->h != nullptr, "%s: null h", kGluWho);
-    CQ_REQUIRE((reinterpret_cast<uintptr_t>(a->h) & (a->h_dtype == CQ_F16 ? 1 : 3)) == 0, "%s: misaligned h pointer",
-               kGluWho);
-    CQ_REQUIRE(a->ldh >= g->m, "%s: ldh %lld < m %lld", kGluWho, (long long)a->ldh, (long long)g->m);
+    CQ_REQUIRE(!misaligned(a->h, a->h_dtype == CQ_F16 ? 1 : 3), "%s: misaligned h pointer", kGluWho);
+    CQ_REQUIRE(a->ldh >= a->gate.m, "%s: ldh %lld < m %lld", kGluWho, (long long)a->ldh, (long long)a->gate.m);
     return CQ_OK;
 }
 
 int glu_forward(const cq_linear_glu_args* a, void* ws, size_t ws_bytes, void* stream) {
     if (int st = validate_glu(a)) return st;
     if (a->gate.tokens == 0) return CQ_OK;
+    const Members ms = members_of(a);
     size_t offs[2];
-    if (int st = check_workspace(glu_offsets(a, offs), ws, ws_bytes, kGluWho)) return st;
+    if (int st = check_workspace(group_offsets(ms, offs), ws, ws_bytes, kGluWho)) return st;
     const bool nf = a->q_format == CQ_QFMT_NF;
     hipStream_t s = as_stream(stream);
+    LinP zs[2], ps[2];
+    int nz, l_bits, r_bits;
+    prepare_members(ms, nf, ws, offs, zs, ps, nz, l_bits, r_bits);
     GluP gp{};
-    LinP zs[2];
-    int nz = 0, l_bits = 16, r_bits = 16;
-    for (int i = 0; i < 2; ++i) {
-        const cq_linear_packed_args* m = glu_member(a, i);
-        LinP z;
-        layer_params(m, nf, static_cast<char*>(ws) + offs[i], z, i ? gp.u : gp.g);
-        if (m->r > 0) {  // the factor formats are the ranked members' (validate_glu: the same)
-            zs[nz++] = z;
-            l_bits = coded(m->l_bits) ? m->l_bits : 16;
-            r_bits = coded(m->r_bits) ? m->r_bits : 16;
-        }
-    }
+    gp.g = ps[0], gp.u = ps[1];
     gp.act = a->act;
     gp.h = a->h;
     gp.h_f16 = a->h_dtype == CQ_F16;
     gp.ldh = a->ldh;
-    if (nz > 0) {  // the grouped z launch over the members with factors, unchanged
-        if (r_bits == 16) launch_group<16, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
-        else if (r_bits == 2) launch_group<2, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
-        else launch_group<4, CQ_QFMT_UNIFORM, 16, true>(zs, nz, s);
-        if (int st = check_launch("cq_linear_glu_forward (z)")) return st;
-    }
-    const int bits = a->gate.bits;
-    if (nf) {
-        if (bits == 2) launch_glu_layers<2, CQ_QFMT_NF>(gp, l_bits, s);
-        else launch_glu_layers<4, CQ_QFMT_NF>(gp, l_bits, s);
-    } else {
-        if (bits == 2) launch_glu_layers<2, CQ_QFMT_UNIFORM>(gp, l_bits, s);
-        else launch_glu_layers<4, CQ_QFMT_UNIFORM>(gp, l_bits, s);
-    }
+    if (nz > 0)  // the grouped z launch over the members with factors, unchanged
+        if (int st = launch_z<GroupP>(zs, nz, r_bits, s, kGluWho)) return st;
+    with_formats(a->gate.bits, nf, l_bits, [&](auto wt, auto qf, auto lb) { launch_glu<wt(), qf(), lb()>(gp, s); });
     return check_launch(kGluWho);
 }
 
@@ -1309,7 +1169,7 @@ extern "C" int cq_linear_packed_forward(const cq_linear_packed_args* a, void* ws
 
 extern "C" size_t cq_linear_group_workspace(const cq_linear_group_args* g) {
     if (g == nullptr || g->members == nullptr || g->count < 1 || g->count > CQ_LINEAR_GROUP_MAX) return 0;
-    return group_offsets(g, nullptr);
+    return group_offsets(members_of(g), nullptr);
 }
 
 extern "C" int cq_linear_group_forward(const cq_linear_group_args* g, void* ws, size_t ws_bytes, void* stream) {
@@ -1326,7 +1186,7 @@ extern "C" int cq_linear_codebook_forward(const cq_linear_codebook_args* a, void
 }
 
 extern "C" size_t cq_linear_glu_workspace(const cq_linear_glu_args* a) {
-    return a == nullptr ? 0 : glu_offsets(a, nullptr);
+    return a == nullptr ? 0 : group_offsets(members_of(a), nullptr);
 }
 
 extern "C" int cq_linear_glu_forward(const cq_linear_glu_args* a, void* ws, size_t ws_bytes, void* stream) {

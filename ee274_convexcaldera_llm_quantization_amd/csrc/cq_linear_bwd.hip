@@ -46,6 +46,7 @@
 #include <type_traits>
 
 #include "cq_common.h"
+#include "cq_linear_host.h"
 #include "cq_nf.h"
 // the chunk image, its loaders and the code expansion: shared with cq_linear_dequant.hip
 #include "cq_linear_tile.h"
@@ -234,58 +235,26 @@ __global__ __launch_bounds__(kWaves * 64) void linear_bwd_kernel(const BwdP p) {
     }
 }
 
-inline int64_t r32_of(int64_t r) { return ceil_div(r, 32) * 32; }
-inline bool al16(const void* ptr, int64_t ld_elems) {
-    return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld_elems % 8 == 0;
-}
-inline bool misaligned(const void* ptr, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(ptr) & mask) != 0; }
-
 // the halves of u: a function of tokens and r alone
 size_t workspace_bytes(int64_t tokens, int64_t r) {
     if (r <= 0 || tokens <= 0) return 0;
     return (size_t)(2 * tokens * r32_of(r)) * sizeof(uint16_t);
 }
 
-inline bool coded(int bits) { return bits == 2 || bits == 4; }
-inline float kmax(int bits) { return (float)((1 << (bits - 1)) - 1); }
-
-// one factor's codes: rows of `cols` codes in the inference layout, one finite scale >= 0
-// (cq_linear_packed_forward's cases)
-int validate_factor(const char* who, const char* name, int bits, const uint8_t* codes, int64_t stride, int64_t cols,
-                    float scale) {
-    CQ_REQUIRE(codes != nullptr, "%s: null %s codes with %s bits = %d", who, name, name, bits);
-    CQ_REQUIRE(!misaligned(codes, 15) && stride % 16 == 0,
-               "%s: %s codes and their row stride must be 16-byte aligned (inference layout)", who, name);
-    CQ_REQUIRE(stride >= (cols * bits + 7) / 8, "%s: %s code row stride %lld < %lld bytes", who, name, (long long)stride,
-               (long long)((cols * bits + 7) / 8));
-    CQ_REQUIRE(std::isfinite(scale) && scale >= 0.f, "%s: %s scale %g is not finite and >= 0", who, name, (double)scale);
-    return CQ_OK;
-}
-
 int validate(const cq_linear_packed_backward_args* a, const char* who) {
     CQ_REQUIRE(a != nullptr, "%s: null args", who);
     CQ_REQUIRE(a->bits == 2 || a->bits == 4, "%s: bits %d not in {2, 4}", who, a->bits);
-    CQ_REQUIRE((coded(a->l_bits) || a->l_bits == 16) && (coded(a->r_bits) || a->r_bits == 16),
-               "%s: factor bits L %d / R %d not in {2, 4, 16}", who, a->l_bits, a->r_bits);
+    if (int st = validate_factor_bits(who, a->l_bits, a->r_bits)) return st;
     const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
     CQ_REQUIRE(a->tokens >= 0 && a->m > 0 && a->n > 0 && a->r >= 0, "%s: bad shape tokens=%lld m=%lld n=%lld r=%lld", who,
                (long long)a->tokens, (long long)a->m, (long long)a->n, (long long)a->r);
-    CQ_REQUIRE(a->r <= CQ_LINEAR_MAX_RANK, "%s: rank %lld > %d", who, (long long)a->r, CQ_LINEAR_MAX_RANK);
+    if (int st = validate_rank(who, a->r)) return st;
     CQ_REQUIRE(a->tokens <= ((int64_t)1 << 31) && a->n <= (int64_t)65535 * kCols, "%s: shape too large", who);
     CQ_REQUIRE(a->dx_dtype == CQ_F32 || a->dx_dtype == CQ_F16, "%s: dx dtype %d not fp32 / fp16", who, a->dx_dtype);
     CQ_REQUIRE(a->dy && a->codes && a->dx, "%s: null dy / codes / dx", who);
-    CQ_REQUIRE(a->r == 0 || ((lcoded || a->L) && (rcoded || a->R)), "%s: null L / R with r = %lld", who, (long long)a->r);
-    if (lcoded)
-        if (int st = validate_factor(who, "L", a->l_bits, a->L_codes, a->l_code_stride, a->r, a->lscale)) return st;
-    if (rcoded)
-        if (int st = validate_factor(who, "R", a->r_bits, a->R_codes, a->r_code_stride, a->n, a->rscale)) return st;
-    CQ_REQUIRE(!misaligned(a->codes, 15) && a->code_stride % 16 == 0,
-               "%s: codes and their row stride must be 16-byte aligned (inference layout)", who);
-    CQ_REQUIRE(a->code_stride >= (a->n * a->bits + 7) / 8, "%s: code row stride %lld < %lld bytes", who,
-               (long long)a->code_stride, (long long)((a->n * a->bits + 7) / 8));
+    if (int st = validate_operands(a, who, lcoded, rcoded)) return st;
     // a coded factor's fp16 pointer and leading dimension are not looked at
-    CQ_REQUIRE(!misaligned(a->dy, 1) && (lcoded || !misaligned(a->L, 1)) && (rcoded || !misaligned(a->R, 1)),
-               "%s: misaligned fp16 pointer", who);
+    if (int st = validate_fp16_pointers(who, a->dy, lcoded ? nullptr : a->L, rcoded ? nullptr : a->R)) return st;
     CQ_REQUIRE(!misaligned(a->dx, a->dx_dtype == CQ_F16 ? 1 : 3) && !misaligned(a->u_out, 3),
                "%s: misaligned dx / u_out pointer", who);
     CQ_REQUIRE(a->lddy >= a->m && a->lddx >= a->n &&
@@ -328,16 +297,10 @@ void launch_main(const BwdP& p, int r_bits, hipStream_t s) {
 int backward(const cq_linear_packed_backward_args* a, int q_format, void* ws, size_t ws_bytes, void* stream,
              const char* who) {
     if (int st = validate(a, who)) return st;
-    CQ_REQUIRE(q_format == CQ_QFMT_UNIFORM || q_format == CQ_QFMT_NF, "%s: unknown q_format %d", who, q_format);
+    if (int st = validate_format(who, q_format, a->qscale)) return st;
     const bool nf = q_format == CQ_QFMT_NF;
-    CQ_REQUIRE(!nf || (std::isfinite(a->qscale) && a->qscale >= 0.f), "%s: NF scale %g is not finite and >= 0", who,
-               (double)a->qscale);
-    const size_t need = workspace_bytes(a->tokens, a->r);
-    if (need) {
-        CQ_REQUIRE(ws != nullptr && (reinterpret_cast<uintptr_t>(ws) & 15) == 0, "%s: workspace must be 16-byte aligned",
-                   who);
-        CQ_REQUIRE(ws_bytes >= need, "%s: workspace %zu < %zu", who, ws_bytes, need);
-    }
+    // this entry reports a workspace that is too small as CQ_EINVAL
+    if (int st = check_workspace(workspace_bytes(a->tokens, a->r), ws, ws_bytes, who, CQ_EINVAL)) return st;
     if (a->tokens == 0) return CQ_OK;
     const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
     hipStream_t s = as_stream(stream);
@@ -349,10 +312,7 @@ int backward(const cq_linear_packed_backward_args* a, int q_format, void* ws, si
     p.r32 = r32_of(a->r);
     p.uh = reinterpret_cast<_Float16*>(ws);
     p.ul = p.uh ? p.uh + a->tokens * p.r32 : nullptr;
-    // the coded factors' scale / k (one fp32 division each), multiplied in fp32
-    p.uscale = 1.0f;
-    if (lcoded) p.uscale = a->lscale / kmax(a->l_bits);
-    if (rcoded) p.uscale = lcoded ? p.uscale * (a->rscale / kmax(a->r_bits)) : a->rscale / kmax(a->r_bits);
+    p.uscale = factor_scale(a, lcoded, rcoded);
     if (a->r > 0) {  // u~ = uscale dy lam: fp32 to u_out, split halves to the workspace
         BwdP u = p;
         u.u_out = a->u_out;
@@ -372,8 +332,7 @@ int backward(const cq_linear_packed_backward_args* a, int q_format, void* ws, si
     p.w = Src{a->codes, a->code_stride, 1, a->m, a->n};
     if (rcoded) p.R = Src{a->R_codes, a->r_code_stride, 1, a->r, a->n};
     else p.R = Src{a->R, a->ldr, a->r > 0 && al16(a->R, a->ldr), a->r, a->n};
-    // one fp32 division: s / k, or s / D with the level table's denominator
-    p.sk = a->qscale / (nf ? (a->bits == 4 ? kNF4D : kNF2D) : kmax(a->bits));
+    p.sk = code_scale(a->qscale, a->bits, nf);
     p.gs = a->gscale;
     p.dx = a->dx;
     p.dx_f16 = a->dx_dtype == CQ_F16;

@@ -31,6 +31,7 @@
 #include <cmath>
 #include <cstdio>
 
+#include "cq_linear_host.h"
 #include "cq_linear_tile.h"
 
 namespace cq {
@@ -221,37 +222,14 @@ __global__ __launch_bounds__(kWaves * 64) void linear_dequant_kernel(const DqP p
     }
 }
 
-inline bool al16(const void* ptr, int64_t ld_elems) {
-    return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0 && ld_elems % 8 == 0;
-}
-inline bool misaligned(const void* ptr, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(ptr) & mask) != 0; }
-inline bool coded(int bits) { return bits == 2 || bits == 4; }
-inline float kmax(int bits) { return (float)((1 << (bits - 1)) - 1); }
-
-// one factor's codes: rows of `cols` codes in the inference layout, one finite scale >= 0
-// (cq_linear_packed_forward's cases)
-int validate_factor(const char* who, const char* name, int bits, const uint8_t* codes, int64_t stride, int64_t cols,
-                    float scale) {
-    CQ_REQUIRE(codes != nullptr, "%s: null %s codes with %s bits = %d", who, name, name, bits);
-    CQ_REQUIRE(!misaligned(codes, 15) && stride % 16 == 0,
-               "%s: %s codes and their row stride must be 16-byte aligned (inference layout)", who, name);
-    CQ_REQUIRE(stride >= (cols * bits + 7) / 8, "%s: %s code row stride %lld < %lld bytes", who, name, (long long)stride,
-               (long long)((cols * bits + 7) / 8));
-    CQ_REQUIRE(std::isfinite(scale) && scale >= 0.f, "%s: %s scale %g is not finite and >= 0", who, name, (double)scale);
-    return CQ_OK;
-}
-
 int validate(const cq_linear_dequant_args* a, const char* who) {
     CQ_REQUIRE(a != nullptr, "%s: null args", who);
     CQ_REQUIRE(a->bits == 2 || a->bits == 4, "%s: bits %d not in {2, 4}", who, a->bits);
-    CQ_REQUIRE(a->q_format == CQ_QFMT_UNIFORM || a->q_format == CQ_QFMT_NF, "%s: unknown q_format %d", who, a->q_format);
-    CQ_REQUIRE(a->q_format != CQ_QFMT_NF || (std::isfinite(a->qscale) && a->qscale >= 0.f),
-               "%s: NF scale %g is not finite and >= 0", who, (double)a->qscale);
-    CQ_REQUIRE((coded(a->l_bits) || a->l_bits == 16) && (coded(a->r_bits) || a->r_bits == 16),
-               "%s: factor bits L %d / R %d not in {2, 4, 16}", who, a->l_bits, a->r_bits);
+    if (int st = validate_format(who, a->q_format, a->qscale)) return st;
+    if (int st = validate_factor_bits(who, a->l_bits, a->r_bits)) return st;
     CQ_REQUIRE(a->m >= 0 && a->n >= 0 && a->r >= 0, "%s: bad shape m=%lld n=%lld r=%lld", who, (long long)a->m,
                (long long)a->n, (long long)a->r);
-    CQ_REQUIRE(a->r <= CQ_LINEAR_MAX_RANK, "%s: rank %lld > %d", who, (long long)a->r, CQ_LINEAR_MAX_RANK);
+    if (int st = validate_rank(who, a->r)) return st;
     CQ_REQUIRE(a->m <= ((int64_t)1 << 31) && a->n <= (int64_t)65535 * kCols, "%s: shape too large", who);
     CQ_REQUIRE(a->w_dtype == CQ_F32 || a->w_dtype == CQ_F16 || a->w_dtype == CQ_BF16,
                "%s: w dtype %d not fp32 / fp16 / bf16", who, a->w_dtype);
@@ -260,18 +238,11 @@ int validate(const cq_linear_dequant_args* a, const char* who) {
     if (a->m == 0 || a->n == 0) return CQ_OK;
     const bool lcoded = a->r > 0 && coded(a->l_bits), rcoded = a->r > 0 && coded(a->r_bits);
     CQ_REQUIRE(a->codes && a->w, "%s: null codes / w", who);
-    CQ_REQUIRE(a->r == 0 || ((lcoded || a->L) && (rcoded || a->R)), "%s: null L / R with r = %lld", who, (long long)a->r);
-    if (lcoded)
-        if (int st = validate_factor(who, "L", a->l_bits, a->L_codes, a->l_code_stride, a->r, a->lscale)) return st;
-    if (rcoded)
-        if (int st = validate_factor(who, "R", a->r_bits, a->R_codes, a->r_code_stride, a->n, a->rscale)) return st;
-    CQ_REQUIRE(!misaligned(a->codes, 15) && a->code_stride % 16 == 0,
-               "%s: codes and their row stride must be 16-byte aligned (inference layout)", who);
-    CQ_REQUIRE(a->code_stride >= (a->n * a->bits + 7) / 8, "%s: code row stride %lld < %lld bytes", who,
-               (long long)a->code_stride, (long long)((a->n * a->bits + 7) / 8));
+    if (int st = validate_operands(a, who, lcoded, rcoded)) return st;
     // a coded factor's fp16 pointer and leading dimension are not looked at
-    CQ_REQUIRE(a->r == 0 || ((lcoded || !misaligned(a->L, 1)) && (rcoded || !misaligned(a->R, 1))),
-               "%s: misaligned fp16 pointer", who);
+    if (int st = validate_fp16_pointers(who, nullptr, lcoded || a->r == 0 ? nullptr : a->L,
+                                        rcoded || a->r == 0 ? nullptr : a->R))
+        return st;
     CQ_REQUIRE(!misaligned(a->w, a->w_dtype == CQ_F32 ? 3 : 1), "%s: misaligned w pointer", who);
     CQ_REQUIRE(a->r == 0 || ((lcoded || a->ldl >= a->r) && (rcoded || a->ldr >= a->n)),
                "%s: leading dimension smaller than the row", who);
@@ -318,13 +289,9 @@ extern "C" int cq_linear_dequant(const cq_linear_dequant_args* a, void* stream) 
     else p.L = a->L, p.lstride = a->ldl, p.l_al = a->r > 0 && al16(a->L, a->ldl);
     if (rcoded) p.R = Src{a->R_codes, a->r_code_stride, 1, a->r, a->n};
     else p.R = Src{a->R, a->ldr, a->r > 0 && al16(a->R, a->ldr), a->r, a->n};
-    // one fp32 division: s / k, or s / D with the level table's denominator
-    p.qs = a->qscale / (nf ? (a->bits == 4 ? kNF4D : kNF2D) : kmax(a->bits));
+    p.qs = code_scale(a->qscale, a->bits, nf);
     p.gs = a->gscale;
-    // the coded factors' scale / k (one fp32 division each), multiplied in fp32
-    p.fscale = 1.0f;
-    if (lcoded) p.fscale = a->lscale / kmax(a->l_bits);
-    if (rcoded) p.fscale = lcoded ? p.fscale * (a->rscale / kmax(a->r_bits)) : a->rscale / kmax(a->r_bits);
+    p.fscale = factor_scale(a, lcoded, rcoded);
     p.w = a->w, p.ldw = a->ldw;
     // a lane's 4 columns start at a multiple of 4: one store when every row does too
     const uintptr_t piece = a->w_dtype == CQ_F32 ? 16 : 8;
