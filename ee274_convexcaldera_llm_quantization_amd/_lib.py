@@ -187,6 +187,21 @@ class HadamardGluArgs(ctypes.Structure):
     ]
 
 
+class HadamardSignedArgs(ctypes.Structure):
+    """cq_hadamard_signed_args: cq_hadamard_args and the two int8 sign vectors (device pointers or NULL)."""
+    _fields_ = [("a", HadamardArgs), ("sign_in", c_vp), ("sign_out", c_vp)]
+
+
+class HadamardSignedGroupArgs(ctypes.Structure):
+    """cq_hadamard_signed_group_args: `members` points at a host array of `count` cq_hadamard_signed_args."""
+    _fields_ = [("count", ctypes.c_int32), ("members", ctypes.POINTER(HadamardSignedArgs))]
+
+
+class HadamardSignedGluArgs(ctypes.Structure):
+    """cq_hadamard_signed_glu_args: cq_hadamard_glu_args and the output signs of the gate and up transforms."""
+    _fields_ = [("a", HadamardGluArgs), ("sign_g", c_vp), ("sign_u", c_vp)]
+
+
 _SIGS = {
     "cq_abi_version": (c_int, []),
     "cq_last_error": (ctypes.c_char_p, []),
@@ -285,6 +300,9 @@ _SIGS = {
     "cq_hadamard_rows": (c_int, [ctypes.POINTER(HadamardArgs), c_vp]),
     "cq_hadamard_group_rows": (c_int, [ctypes.POINTER(HadamardGroupArgs), c_vp]),
     "cq_hadamard_glu_rows": (c_int, [ctypes.POINTER(HadamardGluArgs), c_vp]),
+    "cq_hadamard_signed_rows": (c_int, [ctypes.POINTER(HadamardSignedArgs), c_vp]),
+    "cq_hadamard_signed_group_rows": (c_int, [ctypes.POINTER(HadamardSignedGroupArgs), c_vp]),
+    "cq_hadamard_signed_glu_rows": (c_int, [ctypes.POINTER(HadamardSignedGluArgs), c_vp]),
     # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
     "cq_gemm_x3_skip": (c_int, [ctypes.POINTER(X3Args), c_vp]),
     "cq_gram_f64_masked": (c_int, [c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_i64,
@@ -1883,4 +1901,110 @@ def hadamard_glu_rows(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=None, act=
     _require_hip(g, u, h, bias_g, bias_u)
     a = hadamard_glu_args(g, u, h, n_in=n_in, n_out=n_out, P=P, bias_g=bias_g, bias_u=bias_u, act=act)
     _check(load().cq_hadamard_glu_rows(ctypes.byref(a), _stream(g.device)), "cq_hadamard_glu_rows")
+    return h
+
+
+# ---------------------------------------------------------------------------- randomised Hadamard transform
+def _sign_ptr(who, name, sign, length, device):
+    """Device pointer of the int8 sign vector `sign` (at least `length` entries, contiguous, on `device`), 0
+    for None.  ValueError in `who`'s name otherwise."""
+    if sign is None:
+        return 0
+    def need(cond, what):
+        if not cond:
+            raise ValueError(f"{who}: {name} {what}")
+    need(isinstance(sign, torch.Tensor) and sign.dtype == torch.int8,
+         f"must be an int8 tensor, got {getattr(sign, 'dtype', type(sign).__name__)}")
+    need(sign.dim() == 1 and sign.is_contiguous(), f"must be a contiguous vector, got shape {tuple(sign.shape)}")
+    need(sign.numel() >= length, f"has {sign.numel()} entries, fewer than the {length} the transform reads")
+    need(sign.device == device, f"is on {sign.device}, the transform's operands on {device}")
+    return sign.data_ptr()
+
+
+def hadamard_signed_args(x, y, *, n_in, n_out, P, bias=None, sign_in=None, sign_out=None, into=None,
+                         who="cq_hadamard_signed_rows") -> HadamardSignedArgs:
+    """cq_hadamard_signed_args: `hadamard_args`' operands and checks, and sign_in (>= n_in,) / sign_out
+    (>= n_out,): contiguous int8 vectors on x's device, or None.  An entry flips its element iff it is
+    negative."""
+    s = HadamardSignedArgs() if into is None else into
+    try:
+        hadamard_args(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias, into=s.a)
+    except ValueError as e:
+        raise ValueError(f"{who}: {str(e).removeprefix('cq_hadamard_rows: ')}") from None
+    s.sign_in = _sign_ptr(who, "sign_in", sign_in, n_in, x.device)
+    s.sign_out = _sign_ptr(who, "sign_out", sign_out, n_out, x.device)
+    return s
+
+
+def hadamard_signed_rows(x, y, *, n_in, n_out, P, bias=None, sign_in=None, sign_out=None):
+    """y[t, :n_out] = sign_out * (H_P pad(sign_in * x[t, :n_in]))[:n_out] / sqrt(P) (+ bias): the randomised
+    Hadamard transform of every row (cq_hadamard_signed_rows).  Both flips are exact; with both vectors
+    None the bits are `hadamard_rows`'.  x and y must not overlap.  No workspace, no host synchronisation."""
+    a = hadamard_signed_args(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias, sign_in=sign_in, sign_out=sign_out)
+    _require_hip(x, y, bias, sign_in, sign_out)
+    _check(load().cq_hadamard_signed_rows(ctypes.byref(a), _stream(x.device)), "cq_hadamard_signed_rows")
+    return y
+
+
+def hadamard_signed_group_args(members) -> HadamardSignedGroupArgs:
+    """cq_hadamard_signed_group_args of 1 .. HADAMARD_GROUP_MAX transforms.  members: one dict per transform
+    with `hadamard_signed_args`' arguments as keys (x, y, n_in, n_out, P and optionally bias, sign_in,
+    sign_out); `hadamard_group_args`' rules.  The struct keeps the member array alive."""
+    who = "cq_hadamard_signed_group_rows"
+    members = list(members)
+    if not 1 <= len(members) <= HADAMARD_GROUP_MAX:
+        raise ValueError(f"{who}: count {len(members)} not in 1 .. {HADAMARD_GROUP_MAX}")
+    arr = (HadamardSignedArgs * len(members))()
+    for i, mem in enumerate(members):
+        s = hadamard_signed_args(mem["x"], mem["y"], n_in=mem["n_in"], n_out=mem["n_out"], P=mem["P"],
+                                 bias=mem.get("bias"), sign_in=mem.get("sign_in"), sign_out=mem.get("sign_out"),
+                                 into=arr[i], who=f"{who}: member {i}")
+        for field in ("rows", "P"):
+            if getattr(s.a, field) != getattr(arr[0].a, field):
+                raise ValueError(f"{who}: member {i}: {field} {getattr(s.a, field)} differs from member 0's "
+                                 f"{getattr(arr[0].a, field)}")
+    g = HadamardSignedGroupArgs()
+    g.count = len(members)
+    g.members = ctypes.cast(arr, ctypes.POINTER(HadamardSignedArgs))
+    g._members = arr
+    return g
+
+
+def hadamard_signed_group_rows(members):
+    """The signed transforms `members` (see `hadamard_signed_group_args`) in one launch
+    (cq_hadamard_signed_group_rows): each member's y receives, bit for bit, what `hadamard_signed_rows`
+    writes on the same arguments.  No member's y may overlap an x or another y."""
+    members = list(members)
+    g = hadamard_signed_group_args(members)
+    for mem in members:
+        _require_hip(mem["x"], mem["y"], mem.get("bias"), mem.get("sign_in"), mem.get("sign_out"))
+    _check(load().cq_hadamard_signed_group_rows(ctypes.byref(g), _stream(members[0]["x"].device)),
+           "cq_hadamard_signed_group_rows")
+    return [mem["y"] for mem in members]
+
+
+def hadamard_signed_glu_args(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=None, act=ACT_SILU, sign_g=None,
+                             sign_u=None) -> HadamardSignedGluArgs:
+    """cq_hadamard_signed_glu_args: `hadamard_glu_args`' operands and checks, and sign_g / sign_u (>= n_out,):
+    contiguous int8 vectors on g's device, or None."""
+    who = "cq_hadamard_signed_glu_rows"
+    s = HadamardSignedGluArgs()
+    try:
+        s.a = hadamard_glu_args(g, u, h, n_in=n_in, n_out=n_out, P=P, bias_g=bias_g, bias_u=bias_u, act=act)
+    except ValueError as e:
+        raise ValueError(f"{who}: {str(e).removeprefix('cq_hadamard_glu_rows: ')}") from None
+    s.sign_g = _sign_ptr(who, "sign_g", sign_g, n_out, g.device)
+    s.sign_u = _sign_ptr(who, "sign_u", sign_u, n_out, g.device)
+    return s
+
+
+def hadamard_signed_glu_rows(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=None, act=ACT_SILU, sign_g=None,
+                             sign_u=None):
+    """`hadamard_glu_rows` with output signs: h = a(sign_g * (H g / sqrt(P)) + bias_g) * (sign_u * (H u / sqrt(P))
+    + bias_u) (cq_hadamard_signed_glu_rows); the pre-activations have the bits of `hadamard_signed_rows`' fp32
+    outputs with sign_out = sign_g resp. sign_u.  With both None the bits are `hadamard_glu_rows`'."""
+    a = hadamard_signed_glu_args(g, u, h, n_in=n_in, n_out=n_out, P=P, bias_g=bias_g, bias_u=bias_u, act=act,
+                                 sign_g=sign_g, sign_u=sign_u)
+    _require_hip(g, u, h, bias_g, bias_u, sign_g, sign_u)
+    _check(load().cq_hadamard_signed_glu_rows(ctypes.byref(a), _stream(g.device)), "cq_hadamard_signed_glu_rows")
     return h

@@ -33,7 +33,13 @@
 // cq_hadamard_group_rows runs up to eight such transforms of the same rows and P in one launch of the
 // same kernels (the member is blockIdx.y), and cq_hadamard_glu_rows two of them -- the rows of gate and
 // of up -- with h = a(v_g) * v_u as the epilogue of kernels of its own built from the same stages.
+//
+// The cq_hadamard_signed_* entries run the randomised transform diag(s_out) H diag(s_in): the same kernel
+// bodies instantiated on parameter types that carry the two int8 sign vectors (HadSP and the structs built
+// from it).  Only the chunk load and the scale step differ, by overload on the parameter type, so the
+// unsigned instantiations are the text they were and the stage order is still a function of P alone.
 #include <cmath>
+#include <type_traits>
 
 #include "cq_common.h"
 
@@ -52,20 +58,41 @@ struct HadP {
     float c;
 };
 
+// cq_hadamard_signed_rows: an element of x is negated iff its byte of sign_in is negative, a finished sum
+// iff its byte of sign_out is (either may be null: no flips).  si_vec / so_vec: the vector is 4-byte
+// aligned, so the four bytes of a whole chunk may be one load.
+struct HadSP : HadP {
+    const int8_t* sign_in;
+    const int8_t* sign_out;
+    int si_vec, so_vec;
+};
+
 // cq_hadamard_group_rows' kernel argument: the members with something to write, by value.  They share
 // rows and P (the template instantiation and the grid's x extent); blockIdx.y is the member.
 struct HadGroupP {
     HadP m[CQ_HADAMARD_GROUP_MAX];
 };
+struct HadSGroupP {
+    HadSP m[CQ_HADAMARD_GROUP_MAX];
+};
 __device__ __forceinline__ const HadP& member(const HadP& p) { return p; }
 __device__ __forceinline__ const HadP& member(const HadGroupP& g) {
     return *reinterpret_cast<const HadP*>(reinterpret_cast<const char*>(g.m) + blockIdx.y * sizeof(HadP));
+}
+__device__ __forceinline__ const HadSP& member(const HadSP& p) { return p; }
+__device__ __forceinline__ const HadSP& member(const HadSGroupP& g) {
+    return *reinterpret_cast<const HadSP*>(reinterpret_cast<const char*>(g.m) + blockIdx.y * sizeof(HadSP));
 }
 
 // cq_hadamard_glu_rows' kernel argument: g and u are the two transforms as cq_hadamard_rows would run
 // them (x = the row of gate resp. up, bias, n_in, c); g's y fields and n_out describe h, u's y is unused.
 struct HadGluP {
     HadP g, u;
+    int act;
+};
+// cq_hadamard_signed_glu_rows': g.sign_out and u.sign_out are sign_g and sign_u, the sign_in are null
+struct HadSGluP {
+    HadSP g, u;
     int act;
 };
 
@@ -104,6 +131,34 @@ __device__ __forceinline__ void load4(const HadP& p, const char* row, int i0, fl
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = (i0 + k < p.n_in) ? load1(row, p.x_dt, i0 + k) : 0.0f;
+}
+
+// The four sign bytes of the columns [i0, i0 + 4) as one word, byte k in bits 8k .. 8k + 7; zero (no flip) for
+// a null vector and for columns >= n, whose bytes are not read.  A whole chunk of an aligned vector is one
+// 4-byte load, anything else the scalar path (the same word).
+__device__ __forceinline__ uint32_t sign_word(const int8_t* sign, int vec, int n, int i0) {
+    if (sign == nullptr) return 0u;
+    if (vec && i0 + 4 <= n) return *reinterpret_cast<const uint32_t*>(sign + i0);
+    uint32_t s = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (i0 + k < n) s |= (uint32_t)(uint8_t)sign[i0 + k] << (8 * k);
+    return s;
+}
+
+// v[k] negated where byte k of the sign word is negative: the byte's top bit goes into the float's sign bit,
+// which is exact for every value
+__device__ __forceinline__ void flip4(uint32_t s, float* v) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = __uint_as_float(__float_as_uint(v[k]) ^ ((s << (24 - 8 * k)) & 0x80000000u));
+}
+
+// the signed transform's load: sign_in is applied to x as it is widened.  The sign word is asked for first,
+// so that its load is in flight beside x's and not behind it
+__device__ __forceinline__ void load4(const HadSP& p, const char* row, int i0, float* v) {
+    const uint32_t s = sign_word(p.sign_in, p.si_vec, p.n_in, i0);
+    load4(static_cast<const HadP&>(p), row, i0, v);
+    flip4(s, v);
 }
 
 // o = c * v (+ bias) for the columns [i0, i0 + 4), i0 < n_out: the fp32 values before the output rounding
@@ -206,10 +261,26 @@ __device__ __forceinline__ void store4(const HadP& p, char* row, int i0, const f
     }
 }
 
+// The signed transform's scale step: o = s_out * (c * v) (+ bias).  The flip is applied to v: c * (-v) and
+// -(c * v) are the same bits (IEEE multiplication is sign-symmetric), and the unsigned text then serves.
+__device__ __forceinline__ void scaled4(const HadSP& p, int i0, const float* v, float* o) {
+    float w[4] = {v[0], v[1], v[2], v[3]};
+    flip4(sign_word(p.sign_out, p.so_vec, p.n_out, i0), w);
+    scaled4(static_cast<const HadP&>(p), i0, w, o);
+}
+
+__device__ __forceinline__ void store4(const HadSP& p, char* row, int i0, const float* v) {
+    if (i0 >= p.n_out) return;
+    float w[4] = {v[0], v[1], v[2], v[3]};
+    flip4(sign_word(p.sign_out, p.so_vec, p.n_out, i0), w);
+    store4(static_cast<const HadP&>(p), row, i0, w);
+}
+
 // h = a(v_g) * v_u of the columns [i0, i0 + 4): v_g and v_u are store4's fp32 values of the two
 // transforms (scaled4 on each), a is the identity or e = expf(-v), d = 1 + e, v / d (the file is built
 // without contraction and with the correctly rounded division); one multiply, one rounding to h's type
-__device__ __forceinline__ void glu_store4(const HadGluP& a, char* hrow, int i0, const float* vg, const float* vu) {
+template <typename GLU>
+__device__ __forceinline__ void glu_store4(const GLU& a, char* hrow, int i0, const float* vg, const float* vu) {
     if (i0 >= a.g.n_out) return;
     float og[4], ou[4], h[4];
     scaled4(a.g, i0, vg, og);
@@ -281,7 +352,7 @@ constexpr int ilog2(int x) { return x <= 1 ? 0 : 1 + ilog2(x / 2); }
 // the same body, hence the same work in the same order as alone.
 template <int CH, typename ARG>
 __global__ __launch_bounds__(256) void hadamard_wave_kernel(const ARG arg) {
-    const HadP& p = member(arg);
+    const auto& p = member(arg);  // HadP, or HadSP in the signed entries' instantiations
     constexpr int kQBits = ilog2(CH);
     const int tid = threadIdx.x, lane = tid & 63;
     const int lg = CH == 1 ? p.lg_tl : 6;   // lane bits of a row's chunk index
@@ -318,13 +389,15 @@ __global__ __launch_bounds__(256) void hadamard_wave_kernel(const ARG arg) {
 // Every LDS access is 16 bytes per lane with consecutive lanes on consecutive slots.  The row
 // buffer is static LDS, 16 KB G (128 KB of the CU's 160 KB for P = 32768).
 // (P = 32768 at four teams would cap a lane at 128 registers, which the last stage's 32 values and their
-// stores do not fit without scratch: two teams)
-constexpr int block_teams(int G) { return G == 8 ? 2 : G; }
+// stores do not fit without scratch: two teams.  The signed single transform at P = 16384 is in the same
+// place with its sign words, 44 bytes of scratch at four teams: two teams there as well)
+template <typename ARG>
+constexpr int block_teams(int G) { return G == 8 || (G == 4 && std::is_same_v<ARG, HadSP>) ? 2 : G; }
 
 template <int G, typename ARG>
-__global__ __launch_bounds__(256 * block_teams(G)) void hadamard_block_kernel(const ARG arg) {
-    const HadP& p = member(arg);
-    constexpr int kTeams = block_teams(G), kThreads = 256 * kTeams;
+__global__ __launch_bounds__(256 * block_teams<ARG>(G)) void hadamard_block_kernel(const ARG arg) {
+    const auto& p = member(arg);  // HadP, or HadSP in the signed entries' instantiations
+    constexpr int kTeams = block_teams<ARG>(G), kThreads = 256 * kTeams;
     __shared__ float4 rowbuf[G * 1024];
     const int tid = threadIdx.x & 255, lane = tid & 63, w = tid >> 6, team = threadIdx.x >> 8;
     const size_t xes = p.x_dt == CQ_F32 ? 4 : 2, yes = p.y_dt == CQ_F32 ? 4 : 2;
@@ -382,8 +455,9 @@ __global__ __launch_bounds__(256 * block_teams(G)) void hadamard_block_kernel(co
 
 // cq_hadamard_glu_rows, rows of up to 2048 values: hadamard_wave_kernel's stages run twice, on the row
 // of gate and on the row of up, into two register sets; the epilogue takes both.
-template <int CH>
-__global__ __launch_bounds__(256) void hadamard_wave_glu_kernel(const HadGluP a) {
+// GLU: HadGluP, or HadSGluP (cq_hadamard_signed_glu_rows)
+template <int CH, typename GLU>
+__global__ __launch_bounds__(256) void hadamard_wave_glu_kernel(const GLU a) {
     constexpr int kQBits = ilog2(CH);
     const int tid = threadIdx.x, lane = tid & 63;
     const int lg = CH == 1 ? a.g.lg_tl : 6;
@@ -423,8 +497,8 @@ __global__ __launch_bounds__(256) void hadamard_wave_glu_kernel(const HadGluP a)
 // and the stores do not fit without scratch: two teams, as hadamard_block_kernel has at P = 32768)
 constexpr int glu_teams(int G) { return G == 4 ? 2 : G; }
 
-template <int G>
-__global__ __launch_bounds__(256 * glu_teams(G)) void hadamard_block_glu_kernel(const HadGluP a) {
+template <int G, typename GLU>
+__global__ __launch_bounds__(256 * glu_teams(G)) void hadamard_block_glu_kernel(const GLU a) {
     static_assert(G == 1 || G == 2 || G == 4, "two row buffers of 16 KB G must fit the CU's LDS");
     constexpr int kTeams = glu_teams(G), kThreads = 256 * kTeams;
     __shared__ float4 rowbuf[2 * G * 1024];
@@ -436,7 +510,7 @@ __global__ __launch_bounds__(256 * glu_teams(G)) void hadamard_block_glu_kernel(
 #pragma unroll 1
         for (int sg = team; sg < 2 * G; sg += kTeams) {  // gate's sub-rows, then up's: 2 G / kTeams passes for
             const int s = sg >= G, g = sg - s * G;       // every team, so the barrier is uniform
-            const HadP& p = s ? a.u : a.g;
+            const auto& p = s ? a.u : a.g;
             const char* xrow = p.x + (size_t)row * (size_t)p.ldx * (p.x_dt == CQ_F32 ? 4 : 2);
             float4* buf = rowbuf + sg * 1024;
             float v[16];
@@ -497,7 +571,7 @@ void launch_wave(const ARG& arg, int64_t rows, int lg_tl, unsigned ny, hipStream
 template <int G, typename ARG>
 void launch_block(const ARG& arg, int64_t rows, unsigned ny, hipStream_t s) {
     hipLaunchKernelGGL((hadamard_block_kernel<G, ARG>), dim3((unsigned)(rows < kMaxGridRows ? rows : kMaxGridRows), ny),
-                       dim3(256 * block_teams(G)), 0, s, arg);
+                       dim3(256 * block_teams<ARG>(G)), 0, s, arg);
 }
 
 // lg: log2 of the row's chunks of four (0 for P <= 4)
@@ -524,16 +598,16 @@ void launch_rows(const ARG& arg, int64_t rows, int lg, unsigned ny, hipStream_t 
     }
 }
 
-template <int CH>
-void launch_wave_glu(const HadGluP& a, hipStream_t s) {
+template <int CH, typename GLU>
+void launch_wave_glu(const GLU& a, hipStream_t s) {
     const int64_t wgs = ceil_div(a.g.rows, (int64_t)(256 >> a.g.lg_tl));
-    hipLaunchKernelGGL((hadamard_wave_glu_kernel<CH>), dim3((unsigned)(wgs < kMaxGridRows ? wgs : kMaxGridRows)),
+    hipLaunchKernelGGL((hadamard_wave_glu_kernel<CH, GLU>), dim3((unsigned)(wgs < kMaxGridRows ? wgs : kMaxGridRows)),
                        dim3(256), 0, s, a);
 }
 
-template <int G>
-void launch_block_glu(const HadGluP& a, hipStream_t s) {
-    hipLaunchKernelGGL((hadamard_block_glu_kernel<G>),
+template <int G, typename GLU>
+void launch_block_glu(const GLU& a, hipStream_t s) {
+    hipLaunchKernelGGL((hadamard_block_glu_kernel<G, GLU>),
                        dim3((unsigned)(a.g.rows < kMaxGridRows ? a.g.rows : kMaxGridRows)), dim3(256 * glu_teams(G)), 0, s,
                        a);
 }
@@ -595,6 +669,87 @@ HadP params(const cq_hadamard_args* a) {
     return p;
 }
 
+// the signed kernels' parameters: `params` and the two sign vectors (either may be null)
+HadSP signed_params(const cq_hadamard_args* a, const int8_t* sign_in, const int8_t* sign_out) {
+    HadSP p{};
+    static_cast<HadP&>(p) = params(a);
+    p.sign_in = sign_in, p.sign_out = sign_out;
+    p.si_vec = reinterpret_cast<uintptr_t>(sign_in) % 4 == 0;
+    p.so_vec = reinterpret_cast<uintptr_t>(sign_out) % 4 == 0;
+    return p;
+}
+
+// a group member's transform and its kernel parameters, for both group entries
+const cq_hadamard_args& args_of(const cq_hadamard_args& m) { return m; }
+const cq_hadamard_args& args_of(const cq_hadamard_signed_args& m) { return m.a; }
+HadP params_of(const cq_hadamard_args& m) { return params(&m); }
+HadSP params_of(const cq_hadamard_signed_args& m) { return signed_params(&m.a, m.sign_in, m.sign_out); }
+
+// cq_hadamard_group_rows (GP = HadGroupP, M = cq_hadamard_args) and cq_hadamard_signed_group_rows
+template <typename GP, typename M>
+int group_rows(const char* kWho, int count, const M* members, void* stream) {
+    CQ_REQUIRE(count >= 1 && count <= CQ_HADAMARD_GROUP_MAX, "%s: count = %d is not in [1, %d]", kWho, count,
+               CQ_HADAMARD_GROUP_MAX);
+    CQ_REQUIRE(members != nullptr, "%s: null members", kWho);
+    const cq_hadamard_args* m0 = &args_of(members[0]);
+    char who[64];
+    for (int i = 0; i < count; ++i) {
+        const cq_hadamard_args* m = &args_of(members[i]);
+        snprintf(who, sizeof who, "%s: member %d", kWho, i);
+        if (const int st = validate(m, who)) return st;
+        CQ_REQUIRE(m->rows == m0->rows, "%s: rows = %lld differs from member 0's %lld", who, (long long)m->rows,
+                   (long long)m0->rows);
+        CQ_REQUIRE(m->P == m0->P, "%s: P = %lld differs from member 0's %lld", who, (long long)m->P, (long long)m0->P);
+    }
+    if (m0->rows == 0) return CQ_OK;
+    GP arg{};
+    unsigned ny = 0;
+    for (int i = 0; i < count; ++i) {
+        const cq_hadamard_args* m = &args_of(members[i]);
+        if (m->n_out == 0) continue;  // nothing to write: the member takes no part in the grid
+        CQ_REQUIRE(m->x != nullptr && m->y != nullptr, "%s: member %d: null x or y", kWho, i);
+        arg.m[ny++] = params_of(members[i]);
+    }
+    if (ny == 0) return CQ_OK;
+    launch_rows(arg, m0->rows, log2_chunks(m0->P), ny, as_stream(stream));
+    return check_launch(kWho);
+}
+
+// cq_hadamard_glu_rows (GLU = HadGluP; the signs are unused) and cq_hadamard_signed_glu_rows (HadSGluP)
+template <typename GLU>
+int glu_rows(const char* kWho, const cq_hadamard_glu_args* a, const int8_t* sign_g, const int8_t* sign_u,
+             void* stream) {
+    CQ_REQUIRE(a->act == CQ_ACT_IDENTITY || a->act == CQ_ACT_SILU, "%s: unknown act %d", kWho, a->act);
+    // the two transforms as cq_hadamard_rows' arguments, h standing for y in both: the single entry's checks
+    // on each, with the fields under this struct's names
+    const cq_hadamard_args ga{a->g, a->g_dtype, a->ldg, a->h, a->h_dtype, a->ldh, a->rows, a->n_in, a->n_out, a->P,
+                              a->bias_g};
+    const cq_hadamard_args ua{a->u, a->u_dtype, a->ldu, a->h, a->h_dtype, a->ldh, a->rows, a->n_in, a->n_out, a->P,
+                              a->bias_u};
+    if (const int st = validate(&ga, kWho, Names{"g", "h", "ldg", "ldh", "bias_g"}, CQ_HADAMARD_GLU_MAX_N)) return st;
+    if (const int st = validate(&ua, kWho, Names{"u", "h", "ldu", "ldh", "bias_u"}, CQ_HADAMARD_GLU_MAX_N)) return st;
+    if (a->rows == 0 || a->n_out == 0) return CQ_OK;
+    CQ_REQUIRE(a->g != nullptr && a->u != nullptr && a->h != nullptr, "%s: null g, u or h", kWho);
+    GLU p{};
+    if constexpr (std::is_same_v<GLU, HadSGluP>) {
+        p.g = signed_params(&ga, nullptr, sign_g), p.u = signed_params(&ua, nullptr, sign_u);
+    } else {
+        p.g = params(&ga), p.u = params(&ua);
+    }
+    p.act = a->act;
+    hipStream_t s = as_stream(stream);
+    switch (log2_chunks(a->P)) {
+        case 7: launch_wave_glu<2>(p, s); break;     // P = 512
+        case 8: launch_wave_glu<4>(p, s); break;     // 1024
+        case 9: launch_wave_glu<8>(p, s); break;     // 2048
+        case 10: launch_block_glu<1>(p, s); break;   // 4096
+        case 11: launch_block_glu<2>(p, s); break;   // 8192
+        case 12: launch_block_glu<4>(p, s); break;   // 16384
+        default: launch_wave_glu<1>(p, s); break;    // P <= 256
+    }
+    return check_launch(kWho);
+}
+
 }  // namespace
 }  // namespace cq
 
@@ -609,61 +764,37 @@ extern "C" int cq_hadamard_rows(const cq_hadamard_args* a, void* stream) {
     return check_launch("cq_hadamard_rows");
 }
 
+extern "C" int cq_hadamard_signed_rows(const cq_hadamard_signed_args* s, void* stream) {
+    static const char* kWho = "cq_hadamard_signed_rows";
+    CQ_REQUIRE(s != nullptr, "%s: null args", kWho);
+    const cq_hadamard_args* a = &s->a;
+    if (const int st = validate(a, kWho)) return st;
+    if (a->rows == 0 || a->n_out == 0) return CQ_OK;
+    CQ_REQUIRE(a->x != nullptr && a->y != nullptr, "%s: null x or y", kWho);
+    launch_rows(signed_params(a, s->sign_in, s->sign_out), a->rows, log2_chunks(a->P), 1, as_stream(stream));
+    return check_launch(kWho);
+}
+
 extern "C" int cq_hadamard_group_rows(const cq_hadamard_group_args* g, void* stream) {
     static const char* kWho = "cq_hadamard_group_rows";
     CQ_REQUIRE(g != nullptr, "%s: null args", kWho);
-    CQ_REQUIRE(g->count >= 1 && g->count <= CQ_HADAMARD_GROUP_MAX, "%s: count = %d is not in [1, %d]", kWho,
-               (int)g->count, CQ_HADAMARD_GROUP_MAX);
-    CQ_REQUIRE(g->members != nullptr, "%s: null members", kWho);
-    const cq_hadamard_args* m0 = &g->members[0];
-    char who[64];
-    for (int i = 0; i < g->count; ++i) {
-        const cq_hadamard_args* m = &g->members[i];
-        snprintf(who, sizeof who, "%s: member %d", kWho, i);
-        if (const int st = validate(m, who)) return st;
-        CQ_REQUIRE(m->rows == m0->rows, "%s: rows = %lld differs from member 0's %lld", who, (long long)m->rows,
-                   (long long)m0->rows);
-        CQ_REQUIRE(m->P == m0->P, "%s: P = %lld differs from member 0's %lld", who, (long long)m->P, (long long)m0->P);
-    }
-    if (m0->rows == 0) return CQ_OK;
-    HadGroupP arg{};
-    unsigned ny = 0;
-    for (int i = 0; i < g->count; ++i) {
-        const cq_hadamard_args* m = &g->members[i];
-        if (m->n_out == 0) continue;  // nothing to write: the member takes no part in the grid
-        CQ_REQUIRE(m->x != nullptr && m->y != nullptr, "%s: member %d: null x or y", kWho, i);
-        arg.m[ny++] = params(m);
-    }
-    if (ny == 0) return CQ_OK;
-    launch_rows(arg, m0->rows, log2_chunks(m0->P), ny, as_stream(stream));
-    return check_launch(kWho);
+    return group_rows<HadGroupP>(kWho, (int)g->count, g->members, stream);
+}
+
+extern "C" int cq_hadamard_signed_group_rows(const cq_hadamard_signed_group_args* g, void* stream) {
+    static const char* kWho = "cq_hadamard_signed_group_rows";
+    CQ_REQUIRE(g != nullptr, "%s: null args", kWho);
+    return group_rows<HadSGroupP>(kWho, (int)g->count, g->members, stream);
 }
 
 extern "C" int cq_hadamard_glu_rows(const cq_hadamard_glu_args* a, void* stream) {
     static const char* kWho = "cq_hadamard_glu_rows";
     CQ_REQUIRE(a != nullptr, "%s: null args", kWho);
-    CQ_REQUIRE(a->act == CQ_ACT_IDENTITY || a->act == CQ_ACT_SILU, "%s: unknown act %d", kWho, a->act);
-    // the two transforms as cq_hadamard_rows' arguments, h standing for y in both: the single entry's checks
-    // on each, with the fields under this struct's names
-    const cq_hadamard_args ga{a->g, a->g_dtype, a->ldg, a->h, a->h_dtype, a->ldh, a->rows, a->n_in, a->n_out, a->P,
-                              a->bias_g};
-    const cq_hadamard_args ua{a->u, a->u_dtype, a->ldu, a->h, a->h_dtype, a->ldh, a->rows, a->n_in, a->n_out, a->P,
-                              a->bias_u};
-    if (const int st = validate(&ga, kWho, Names{"g", "h", "ldg", "ldh", "bias_g"}, CQ_HADAMARD_GLU_MAX_N)) return st;
-    if (const int st = validate(&ua, kWho, Names{"u", "h", "ldu", "ldh", "bias_u"}, CQ_HADAMARD_GLU_MAX_N)) return st;
-    if (a->rows == 0 || a->n_out == 0) return CQ_OK;
-    CQ_REQUIRE(a->g != nullptr && a->u != nullptr && a->h != nullptr, "%s: null g, u or h", kWho);
-    HadGluP p{};
-    p.g = params(&ga), p.u = params(&ua), p.act = a->act;
-    hipStream_t s = as_stream(stream);
-    switch (log2_chunks(a->P)) {
-        case 7: launch_wave_glu<2>(p, s); break;     // P = 512
-        case 8: launch_wave_glu<4>(p, s); break;     // 1024
-        case 9: launch_wave_glu<8>(p, s); break;     // 2048
-        case 10: launch_block_glu<1>(p, s); break;   // 4096
-        case 11: launch_block_glu<2>(p, s); break;   // 8192
-        case 12: launch_block_glu<4>(p, s); break;   // 16384
-        default: launch_wave_glu<1>(p, s); break;    // P <= 256
-    }
-    return check_launch(kWho);
+    return glu_rows<HadGluP>(kWho, a, nullptr, nullptr, stream);
+}
+
+extern "C" int cq_hadamard_signed_glu_rows(const cq_hadamard_signed_glu_args* s, void* stream) {
+    static const char* kWho = "cq_hadamard_signed_glu_rows";
+    CQ_REQUIRE(s != nullptr, "%s: null args", kWho);
+    return glu_rows<HadSGluP>(kWho, &s->a, s->sign_g, s->sign_u, stream);
 }

@@ -38,6 +38,11 @@ A gated MLP block `down_proj(act(gate_proj(x)) * up_proj(x))` can become a `Cald
 pair runs as one z launch and one code + L launch whose epilogue applies the activation and the product
 (cq_linear_glu_forward), so neither pre-activation is written and the two elementwise launches are gone
 (`model.fuse_gated_mlps`).
+
+A Hadamard-basis layer may carry the +-1 sign vectors of the randomised transform
+H1 diag(su) pad(W) diag(sv) H2 (`HadamardCalderaLinear(sign_seeds=)`, `hadamard_sign_vector`): its transforms,
+its group's and its fused block's then run through the cq_hadamard_signed_* entries, which flip exactly;
+without seeds, the default, nothing about a layer changes.
 """
 from __future__ import annotations
 
@@ -324,7 +329,8 @@ class _HadamardLinearFunction(torch.autograd.Function):
     takes), the inner layer's backward gives the fp32 dx^ from the packed codes, and dx^ goes through
     cq_hadamard_rows (pc -> in_features) into x's dtype; no torch arithmetic on that path.  The
     inner factors' gradients come from the saved x^ and dy^: in the Hadamard basis, the one the
-    factors live in.  The bias is frozen.
+    factors live in.  The bias is frozen.  A signed layer takes cq_hadamard_signed_rows for both: dy
+    goes in with sign_in = su, dx comes out with sign_out = sv, and x^ and dy^ are those of the signed basis.
 
     One function and not three chained ones: autograd casts the gradient of an input to that
     input's dtype, so across an edge the fp32 dx^ of the fp16 x^ would be rounded to fp16 (and the
@@ -349,13 +355,19 @@ class _HadamardLinearFunction(torch.autograd.Function):
             gy2 = gy2.float()
         T = gy2.shape[0]
         dyh = torch.empty((T, pr), dtype=torch.float16, device=gy.device)
-        K.hadamard_rows(gy2, dyh, n_in=had.out_features, n_out=pr, P=pr)
+        if had.sign_seeds is None:
+            K.hadamard_rows(gy2, dyh, n_in=had.out_features, n_out=pr, P=pr)
+        else:
+            K.hadamard_signed_rows(gy2, dyh, n_in=had.out_features, n_out=pr, P=pr, sign_in=had.sign_out)
         dxh, dL, dR = _packed_backward(had.inner, dyh, xh, L16, R16, ctx.needs_input_grad[:3], torch.float32,
                                        ctx.factor_dtypes)
         dx = None
         if dxh is not None:
             dx2 = torch.empty((T, had.in_features), dtype=ctx.x2_dtype, device=gy.device)
-            K.hadamard_rows(dxh, dx2, n_in=pc, n_out=had.in_features, P=pc)
+            if had.sign_seeds is None:
+                K.hadamard_rows(dxh, dx2, n_in=pc, n_out=had.in_features, P=pc)
+            else:
+                K.hadamard_signed_rows(dxh, dx2, n_in=pc, n_out=had.in_features, P=pc, sign_out=had.sign_in)
             dx = dx2.to(ctx.x_dtype).reshape(ctx.x_shape)
         return dx, dL, dR, None
 
@@ -721,6 +733,42 @@ def _next_pow2(n: int) -> int:
     return 1 << (int(n) - 1).bit_length()
 
 
+SIGN_SEED_LIMIT = 1 << 53  # seeds are ints in [0, 2^53): they survive JSON (a results file's `extra`)
+_M64 = (1 << 64) - 1
+
+
+def mix64(x: int) -> int:
+    """The 64-bit mix function of the sign vectors (splitmix64's), all arithmetic mod 2^64."""
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def _check_sign_seed(seed, what="seed"):
+    if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < SIGN_SEED_LIMIT:
+        raise ValueError(f"hadamard_sign_vector: {what} {seed!r} is not an int in [0, 2^53)")
+    return seed
+
+
+def hadamard_sign_vector(seed: int, length: int) -> torch.Tensor:
+    """The +-1 vector (int8, CPU) of the randomised Hadamard transform for `seed`, an int in [0, 2^53):
+    element i is -1 iff bit 63 of mix64(mix64(seed) + i) is set.  A counter-based hash this project defines,
+    so a results file that stores the seed does not depend on a library's generator; a vector is a prefix
+    of any longer one of the same seed."""
+    import numpy as np
+    _check_sign_seed(seed)
+    length = int(length)
+    if length < 0:
+        raise ValueError(f"hadamard_sign_vector: length {length} is negative")
+    x = np.arange(length, dtype=np.uint64) + np.uint64(mix64(seed))  # uint64 arrays wrap mod 2^64
+    x = x + np.uint64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    x = x ^ (x >> np.uint64(31))
+    return torch.from_numpy(np.where((x >> np.uint64(63)).astype(bool), -1, 1).astype(np.int8))
+
+
 class HadamardCalderaLinear(torch.nn.Module):
     """A layer decomposed in the Hadamard basis (`model.apply_caldera_quantization(packed=True,
     packed_hadamard=True)`): `inner` is the CalderaLinear of W~ ~ gs (Q + L R) ~ H1 pad(W) H2 on
@@ -738,9 +786,23 @@ class HadamardCalderaLinear(torch.nn.Module):
     Training: with grad mode on and x requiring grad (or the inner factors trainable) forward
     runs the same launches with a graph (`_HadamardLinearFunction`); the backward transforms dy
     and dx with cq_hadamard_rows around the inner layer's input gradient, and the inner fp16
-    factors train in the Hadamard basis (`enable_factor_training`).  The bias stays frozen."""
+    factors train in the Hadamard basis (`enable_factor_training`).  The bias stays frozen.
 
-    def __init__(self, inner: CalderaLinear, in_features: int, out_features: int, bias=None):
+    sign_seeds = (seed_out, seed_in), two ints in [0, 2^53): the layer is one of the randomised transform
+    W~ ~ H1 diag(su) pad(W) diag(sv) H2 with su = hadamard_sign_vector(seed_out, out_features) and
+    sv = hadamard_sign_vector(seed_in, in_features), held as the int8 buffers `sign_out` and `sign_in`, and
+
+        y = su * (H1 (W~ (H2 (sv * pad(x)))))[:out_features] + bias
+
+    through cq_hadamard_signed_rows for both transforms (the flips are exact; the backward mirrors them: dy
+    goes in with sign_in = su, dx comes out with sign_out = sv, the factor gradients stay in the signed
+    basis).  Extra state gains "sign_seeds".  With None, the default, there are no such buffers, no such key,
+    and the launches are the unsigned entries': nothing about the layer differs from one built without the
+    keyword."""
+
+    sign_seeds = None  # the class default: a layer unpickled from before the keyword is unsigned
+
+    def __init__(self, inner: CalderaLinear, in_features: int, out_features: int, bias=None, sign_seeds=None):
         super().__init__()
         m, n = int(out_features), int(in_features)
         pr, pc = _next_pow2(m), _next_pow2(n)
@@ -758,6 +820,15 @@ class HadamardCalderaLinear(torch.nn.Module):
         self.in_features, self.out_features = n, m
         self.inner = inner
         self.register_buffer("bias", None if bias is None else bias.detach().to(torch.float32).contiguous())
+        self.sign_seeds = None
+        if sign_seeds is not None:
+            seeds = tuple(sign_seeds)
+            if len(seeds) != 2:
+                raise ValueError(f"HadamardCalderaLinear: sign_seeds {sign_seeds!r} is not (seed_out, seed_in)")
+            self.sign_seeds = (_check_sign_seed(seeds[0], "seed_out"), _check_sign_seed(seeds[1], "seed_in"))
+            dev = inner.codes.device
+            self.register_buffer("sign_out", hadamard_sign_vector(self.sign_seeds[0], m).to(dev))
+            self.register_buffer("sign_in", hadamard_sign_vector(self.sign_seeds[1], n).to(dev))
 
     def _apply(self, fn, *args, **kwargs):
         """As `CalderaLinear._apply`: moves follow the model, dtype casts (`model.half()`) leave the
@@ -773,44 +844,59 @@ class HadamardCalderaLinear(torch.nn.Module):
 
     # ------------------------------------------------------------------ constructors
     @classmethod
-    def from_decomposition(cls, dec, Q_bits, original_shape, bias=None, L_bits=None, R_bits=None, Q_method="uniform"):
+    def from_decomposition(cls, dec, Q_bits, original_shape, bias=None, L_bits=None, R_bits=None, Q_method="uniform",
+                           sign_seeds=None):
         """From the CalderaDecomposition of H1 pad(W) H2 (as `CalderaLinear.from_decomposition`
-        takes it, Q_method included) and W's own shape (out_features, in_features)."""
+        takes it, Q_method included) and W's own shape (out_features, in_features).  sign_seeds: the
+        (seed_out, seed_in) of the sign vectors when the decomposed matrix was H1 diag(su) pad(W) diag(sv) H2."""
         m, n = (int(v) for v in original_shape)
         if max(_next_pow2(m), _next_pow2(n)) > K.HADAMARD_MAX_N:
             raise ValueError(f"HadamardCalderaLinear: padded shape {(_next_pow2(m), _next_pow2(n))} exceeds "
                              f"{K.HADAMARD_MAX_N} (cq_hadamard_rows' largest transform)")
         inner = CalderaLinear.from_decomposition(dec, Q_bits, None, L_bits=L_bits, R_bits=R_bits, Q_method=Q_method)
-        return cls(inner, n, m, bias)
+        return cls(inner, n, m, bias, sign_seeds)
 
     @classmethod
     def from_result(cls, res, bias=None):
         """From a `sharding.MatrixResult` of the padded layer whose extra["hadamard"] holds the
-        original [out_features, in_features] (what `to_result` writes)."""
+        original [out_features, in_features] and, for a signed layer, extra["hadamard_signs"] the
+        [seed_out, seed_in] (what `to_result` writes)."""
         shape = (res.extra or {}).get("hadamard")
         if shape is None or len(shape) != 2:
             raise ValueError(f"HadamardCalderaLinear.from_result: {res.name}: extra has no \"hadamard\": [m, n]")
         m, n = int(shape[0]), int(shape[1])
-        return cls(CalderaLinear.from_result(res, None), n, m, bias)
+        signs = (res.extra or {}).get("hadamard_signs")
+        if signs is not None and len(signs) != 2:
+            raise ValueError(f"HadamardCalderaLinear.from_result: {res.name}: extra[\"hadamard_signs\"] {signs!r} is not "
+                             "[seed_out, seed_in]")
+        return cls(CalderaLinear.from_result(res, None), n, m, bias,
+                   None if signs is None else (int(signs[0]), int(signs[1])))
 
     def to_result(self, name: str):
         """`inner.to_result(name)` (the padded layer) with extra["hadamard"] = [out_features,
-        in_features]; `from_result` inverts it."""
+        in_features] and, for a signed layer, extra["hadamard_signs"] = [seed_out, seed_in];
+        `from_result` inverts it."""
         res = self.inner.to_result(name)
         res.extra = dict(res.extra or {})
         res.extra["hadamard"] = [self.out_features, self.in_features]
+        if self.sign_seeds is not None:
+            res.extra["hadamard_signs"] = list(self.sign_seeds)
         return res
 
     # ------------------------------------------------------------------ state
     def get_extra_state(self):
-        return {"in_features": self.in_features, "out_features": self.out_features}
+        state = {"in_features": self.in_features, "out_features": self.out_features}
+        if self.sign_seeds is not None:
+            state["sign_seeds"] = tuple(self.sign_seeds)
+        return state
 
     def set_extra_state(self, state):
         for key, v in state.items():
-            setattr(self, key, v)
+            setattr(self, key, tuple(v) if key == "sign_seeds" else v)
 
     def extra_repr(self):
-        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}"
+        signs = "" if self.sign_seeds is None else f", sign_seeds={self.sign_seeds}"
+        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}{signs}"
 
     def packed_bytes(self) -> int:
         """Bytes a forward streams for the weights: the inner layer's (+ bias)."""
@@ -818,19 +904,23 @@ class HadamardCalderaLinear(torch.nn.Module):
 
     def dense_weight(self) -> torch.Tensor:
         """(H1 inner.dense_weight() H2)[:out_features, :in_features] as dense fp32, by torch ops
-        (checks and baselines only)."""
+        (checks and baselines only); a signed layer's rows and columns carry su and sv."""
         from .model import normalized_hadamard
         Wt = self.inner.dense_weight()
         pr, pc = self.padded_shape
         H1, H2 = normalized_hadamard(pr, Wt.device), normalized_hadamard(pc, Wt.device)
-        return (H1 @ Wt @ H2)[:self.out_features, :self.in_features].contiguous()
+        W = (H1 @ Wt @ H2)[:self.out_features, :self.in_features]
+        if self.sign_seeds is not None:
+            W = W * self.sign_out.to(W.device, torch.float32)[:, None] * self.sign_in.to(W.device, torch.float32)[None, :]
+        return W.contiguous()
 
     def materialize(self, dtype=torch.float16, out=None) -> torch.Tensor:
         """(H1 W~ H2)[:out_features, :in_features] as a dense device tensor by kernels alone: the inner
         layer's `materialize` in fp32, cq_hadamard_rows on its rows (W~ H2, cut to in_features
         columns), then on the rows of the transposed result (H1 that, cut to out_features), which is
-        rounded once to dtype (fp16, bf16 or fp32).  Not a hot path: two fp32 temporaries of the
-        padded size.  out: as `CalderaLinear.materialize`."""
+        rounded once to dtype (fp16, bf16 or fp32).  A signed layer takes cq_hadamard_signed_rows for both,
+        with sign_out = sv on the first and su on the second.  Not a hot path: two fp32 temporaries of
+        the padded size.  out: as `CalderaLinear.materialize`."""
         if out is not None and not out.is_cuda:
             raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
         if out is not None:
@@ -841,10 +931,16 @@ class HadamardCalderaLinear(torch.nn.Module):
         m, n = self.out_features, self.in_features
         Wt = self.inner.materialize(torch.float32)
         A = torch.empty((pr, n), dtype=torch.float32, device=Wt.device)
-        K.hadamard_rows(Wt, A, n_in=pc, n_out=n, P=pc)
+        if self.sign_seeds is None:
+            K.hadamard_rows(Wt, A, n_in=pc, n_out=n, P=pc)
+        else:
+            K.hadamard_signed_rows(Wt, A, n_in=pc, n_out=n, P=pc, sign_out=self.sign_in)
         At = A.t().contiguous()
         Wo = torch.empty((n, m), dtype=dtype, device=Wt.device)
-        K.hadamard_rows(At, Wo, n_in=pr, n_out=m, P=pr)
+        if self.sign_seeds is None:
+            K.hadamard_rows(At, Wo, n_in=pr, n_out=m, P=pr)
+        else:
+            K.hadamard_signed_rows(At, Wo, n_in=pr, n_out=m, P=pr, sign_out=self.sign_out)
         if out is None:
             return Wo.t().contiguous()
         if tuple(out.shape) != (m, n):
@@ -887,7 +983,11 @@ class HadamardCalderaLinear(torch.nn.Module):
         y32 = torch.empty((T, pr), dtype=torch.float32, device=x.device)
         _launch_packed(self.inner, xh, y32, L16, R16)
         y = torch.empty((T, self.out_features), dtype=x2.dtype, device=x.device)
-        K.hadamard_rows(y32, y, n_in=pr, n_out=self.out_features, P=pr, bias=self.bias)
+        if self.sign_seeds is None:
+            K.hadamard_rows(y32, y, n_in=pr, n_out=self.out_features, P=pr, bias=self.bias)
+        else:
+            K.hadamard_signed_rows(y32, y, n_in=pr, n_out=self.out_features, P=pr, bias=self.bias,
+                                   sign_out=self.sign_out)
         return x2, xh, y
 
     @property
@@ -1105,8 +1205,25 @@ def _hadamard_input(had, x):
     if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < n):
         x2 = x2.contiguous()
     xh = torch.empty((x2.shape[0], pc), dtype=torch.float16, device=x.device)
-    K.hadamard_rows(x2, xh, n_in=n, n_out=pc, P=pc)
+    if had.sign_seeds is None:
+        K.hadamard_rows(x2, xh, n_in=n, n_out=pc, P=pc)
+    else:  # x^ = H2 (sv * pad(x)): every signed layer with this in_features and seed_in takes it
+        K.hadamard_signed_rows(x2, xh, n_in=n, n_out=pc, P=pc, sign_in=had.sign_in)
     return x2, xh
+
+
+def _signs_fit(layers, labels):
+    """None when the `HadamardCalderaLinear` layers share one x^ -- all unsigned, or all signed with the same
+    seed_in -- else the reason for the first layer that does not, the layers called by `labels`."""
+    first = layers[0].sign_seeds
+    for had, label in zip(layers[1:], labels[1:]):
+        seeds = had.sign_seeds
+        if (seeds is None) != (first is None):
+            return (f"{label}: sign_seeds {seeds} but {labels[0]}'s are {first}: signed and unsigned layers do not "
+                    "share the input transform")
+        if seeds is not None and seeds[1] != first[1]:
+            return f"{label}: sign seed_in {seeds[1]} differs from {labels[0]}'s {first[1]}"
+    return None
 
 
 # The largest token count at which `HadamardLinearGroup` takes the grouped launches; None: no limit.  Measured on
@@ -1130,7 +1247,9 @@ class HadamardLinearGroup(_SharedInputGroup):
     members: 1 .. `_lib.HADAMARD_GROUP_MAX` `HadamardCalderaLinear` layers on one device that share
     in_features (hence pc and x^) and whose inner layers share bits and q_format and, among those with
     rank > 0, L_bits and R_bits; none of them in another group, none of their inner layers in a
-    `CalderaLinearGroup`.  ValueError names the member and the attribute.
+    `CalderaLinearGroup`; all unsigned, or all signed with one seed_in (they share x^; seed_out is per
+    member).  ValueError names the member and the attribute.  Signed members run the signed input transform
+    once and cq_hadamard_signed_group_rows; unsigned ones the launches they always had.
 
     The grouped launches are taken where they are the members' own inference launches (no autograd graph
     needed, no inner layer with trainable factors, no `dense_prefill_tokens` reached) and the token count
@@ -1159,6 +1278,8 @@ class HadamardLinearGroup(_SharedInputGroup):
                 raise ValueError(f"{who}: member {i}: in_features {had.in_features} differs from member 0's "
                                  f"{first.in_features}")
         why = _formats_fit([had.inner for had in members], [f"member {i}" for i in range(len(members))], "inner ")
+        if why is None:
+            why = _signs_fit(members, [f"member {i}" for i in range(len(members))])
         if why is not None:
             raise ValueError(f"{who}: {why}")
         self._adopt(members)
@@ -1181,12 +1302,16 @@ class HadamardLinearGroup(_SharedInputGroup):
         K.linear_group_forward(xh, [_group_operands(had.inner) for had in self.members], y32,
                                self.members[0].inner.q_format)
         ys = [torch.empty((T, had.out_features), dtype=x2.dtype, device=x.device) for had in self.members]
+        signed = self.members[0].sign_seeds is not None
         buckets = {}  # pr -> the members' transforms, in member order
         for had, v, y in zip(self.members, y32, ys):
             pr = had.padded_shape[0]
-            buckets.setdefault(pr, []).append(dict(x=v, y=y, n_in=pr, n_out=had.out_features, P=pr, bias=had.bias))
+            t = dict(x=v, y=y, n_in=pr, n_out=had.out_features, P=pr, bias=had.bias)
+            if signed:
+                t["sign_out"] = had.sign_out
+            buckets.setdefault(pr, []).append(t)
         for transforms in buckets.values():
-            K.hadamard_group_rows(transforms)
+            (K.hadamard_signed_group_rows if signed else K.hadamard_group_rows)(transforms)
         return tuple(y.to(x.dtype).reshape(*x.shape[:-1], had.out_features) for y, had in zip(ys, self.members))
 
 
@@ -1315,7 +1440,8 @@ def hadamard_glu_fit(gate, up):
     for attr in ("in_features", "out_features"):
         if getattr(up, attr) != getattr(gate, attr):
             return f"up_proj: {attr} {getattr(up, attr)} differs from gate_proj's {getattr(gate, attr)}"
-    return _formats_fit((gate.inner, up.inner), ("gate_proj", "up_proj"), "inner ")
+    return (_formats_fit((gate.inner, up.inner), ("gate_proj", "up_proj"), "inner ")
+            or _signs_fit((gate, up), ("gate_proj", "up_proj")))
 
 
 class HadamardGatedMLP(torch.nn.Module):
@@ -1328,7 +1454,9 @@ class HadamardGatedMLP(torch.nn.Module):
 
     gate_proj, up_proj: `HadamardCalderaLinear` layers on one device that share in_features and
     out_features and whose inner layers share bits and q_format and, when both have rank > 0, L_bits and
-    R_bits.  ValueError names the attribute.  down_proj: any module.  act: "silu" (the default) or
+    R_bits; both unsigned, or both signed with one seed_in (then the input transform and the gated output
+    transform are the signed entries, cq_hadamard_signed_glu_rows with the two layers' sign_out).
+    ValueError names the attribute.  down_proj: any module.  act: "silu" (the default) or
     "identity".  The three layers are submodules under exactly these names: state-dict keys are those of
     the original block.
 
@@ -1385,7 +1513,11 @@ class HadamardGatedMLP(torch.nn.Module):
         v = [torch.empty((T, pr), dtype=torch.float32, device=x.device) for _ in range(2)]
         K.linear_group_forward(xh, [_group_operands(gate.inner), _group_operands(up.inner)], v, gate.inner.q_format)
         h = torch.empty((T, m), dtype=x2.dtype, device=x.device)
-        K.hadamard_glu_rows(v[0], v[1], h, n_in=pr, n_out=m, P=pr, bias_g=gate.bias, bias_u=up.bias, act=act)
+        if gate.sign_seeds is None:
+            K.hadamard_glu_rows(v[0], v[1], h, n_in=pr, n_out=m, P=pr, bias_g=gate.bias, bias_u=up.bias, act=act)
+        else:
+            K.hadamard_signed_glu_rows(v[0], v[1], h, n_in=pr, n_out=m, P=pr, bias_g=gate.bias, bias_u=up.bias,
+                                       act=act, sign_g=gate.sign_out, sign_u=up.sign_out)
         return h.to(x.dtype).reshape(*x.shape[:-1], m)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

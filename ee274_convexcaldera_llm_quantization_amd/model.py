@@ -21,6 +21,7 @@ interleaves the groups on HIP streams), where the reference runs one caldera() p
 from __future__ import annotations
 
 import math
+import zlib
 from dataclasses import dataclass, field
 from typing import Callable, Sequence
 
@@ -114,24 +115,55 @@ def _next_pow2(n: int) -> int:
     return 1 << (n - 1).bit_length()
 
 
-def hadamard_transform(W: torch.Tensor, inverse: bool = False, original_shape=None):
+def hadamard_transform(W: torch.Tensor, inverse: bool = False, original_shape=None, signs=None):
     """main.py:108-133 on the device: forward pads W to powers of two and returns
     (H1 W H2, (rows, cols)); inverse returns (H1 W H2)[:rows, :cols] (H symmetric and
-    orthogonal).  Two fp32 HIP GEMMs."""
+    orthogonal).  Two fp32 HIP GEMMs.
+
+    signs = (su, sv), +-1 vectors of at least rows resp. cols entries (`linear.hadamard_sign_vector`): the
+    randomised transform H1 diag(su) pad(W) diag(sv) H2.  Forward flips W's rows and columns in the padded
+    matrix before the two GEMMs (the pad is zero), inverse flips the rows and columns of the cut result
+    after them; every flip is a multiplication by +-1, which is exact."""
     rows, cols = (W.shape if not inverse else original_shape)
     pr, pc = _next_pow2(rows), _next_pow2(cols)
     dev = W.device
     H1, H2 = normalized_hadamard(pr, dev), normalized_hadamard(pc, dev)
+    flip = None
+    if signs is not None:
+        su, sv = (s.to(dev, torch.float32) for s in signs)
+        if su.dim() != 1 or sv.dim() != 1 or su.numel() < rows or sv.numel() < cols:
+            raise ValueError(f"hadamard_transform: signs {tuple(su.shape)}, {tuple(sv.shape)} do not cover {(rows, cols)}")
+        flip = su[:rows, None] * sv[None, :cols]
     if inverse:
         Wp = W.float().contiguous()
     else:
         Wp = torch.zeros((pr, pc), dtype=torch.float32, device=dev)
-        Wp[:rows, :cols] = W.float()
+        Wp[:rows, :cols] = W.float() if flip is None else W.float() * flip
     T = K.gemm(H1, Wp, C=torch.empty((pr, pc), dtype=torch.float32, device=dev))
     out = K.gemm(T, H2, C=torch.empty((pr, pc), dtype=torch.float32, device=dev))
     if inverse:
-        return out[:rows, :cols]
+        return out[:rows, :cols] if flip is None else out[:rows, :cols] * flip
     return out, (rows, cols)
+
+
+def hadamard_sign_seeds(hadamard_signs: int, name: str, in_features: int):
+    """(seed_out, seed_in) of the layer `name` under `apply_caldera_quantization(hadamard_signs=...)`, with
+    mix64 = `linear.mix64` and b = mix64(hadamard_signs):
+
+        seed_in  = mix64(b + 2 in_features)                   >> 11
+        seed_out = mix64(b + 2 zlib.crc32(name.encode()) + 1) >> 11     (sums mod 2^64)
+
+    Both are below 2^53.  seed_in depends on (hadamard_signs, in_features) alone, so all layers that read one
+    activation share sv and with it the input transform (grouped and fused launches stay available);
+    seed_out is per module name."""
+    from .linear import SIGN_SEED_LIMIT, mix64
+    if isinstance(hadamard_signs, bool) or not isinstance(hadamard_signs, int) or not 0 <= hadamard_signs < SIGN_SEED_LIMIT:
+        raise ValueError(f"hadamard_signs {hadamard_signs!r} is not an int in [0, 2^53)")
+    b = mix64(hadamard_signs)
+    m64 = (1 << 64) - 1
+    seed_in = mix64((b + 2 * int(in_features)) & m64) >> 11
+    seed_out = mix64((b + 2 * zlib.crc32(name.encode()) + 1) & m64) >> 11
+    return seed_out, seed_in
 
 
 # ---------------------------------------------------------------------------- caller
@@ -186,7 +218,8 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                                max_batch: int = 64, keep_dtype: bool = True, decompose: Callable | None = None,
                                log: Callable | None = None, hadamard_gate: bool = False,
                                packed: bool = False, packed_factors: bool = False,
-                               packed_hadamard: bool = False) -> QuantizationReport:
+                               packed_hadamard: bool = False,
+                               hadamard_signs: int | None = None) -> QuantizationReport:
     """main.py:135-251 on the MI355X engine.
 
     hessians: {module name: diagonal (n,) or dense (n, n)} — `Hall` (a missing name raises
@@ -223,10 +256,26 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
       (H1 (Q + L R) H2)[:m, :n]; `packed_factors` composes with it.  Needs packed=True; not with
       `hadamard=True` (that is main.py's dense write-back) and not with `scale_W=True`; a padded
       dimension above `_lib.HADAMARD_MAX_N` raises ValueError.
+    hadamard_signs: with packed_hadamard=True, an int in [0, 2^53): decompose the randomised transform
+      H1 diag(su) pad(W) diag(sv) H2 (CALDERA's and QuIP#'s incoherence processing) and build signed
+      `linear.HadamardCalderaLinear` layers, each with the seeds `hadamard_sign_seeds(hadamard_signs, name,
+      in_features)`: seed_in from in_features alone, so q / k / v and gate / up still share their input
+      transform, seed_out from the module's name.  The decomposition, the recovered weight and the error
+      gate are those of the signed transform; the Hessian is not transformed (as without signs).  Needs
+      packed_hadamard=True: otherwise, or for a value outside the range, ValueError before anything is
+      decomposed.  None, the default: the plain transform, as before.
     Returns the QuantizationReport (counters + per-layer outcomes)."""
     qp = quant_params if quant_params is not None else driver_params()
     if packed_hadamard and not packed:
         raise ValueError("apply_caldera_quantization: packed_hadamard=True needs packed=True")
+    if hadamard_signs is not None:
+        if not packed_hadamard:
+            raise ValueError("apply_caldera_quantization: hadamard_signs needs packed_hadamard=True (the sign vectors "
+                             "belong to the packed layer's transforms)")
+        try:
+            hadamard_sign_seeds(hadamard_signs, "", 1)
+        except ValueError as e:
+            raise ValueError(f"apply_caldera_quantization: {e}") from None
     if packed and hadamard:
         raise ValueError("apply_caldera_quantization: packed=True cannot be combined with hadamard=True (the dense "
                          "write-back of main.py); packed_hadamard=True runs the Hadamard branch packed")
@@ -264,6 +313,7 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
     for job in jobs:
         groups.setdefault(tuple(job[1].weight.shape), []).append(job)
     outcomes = {}
+    seeds = {}    # name -> (seed_out, seed_in) with hadamard_signs
     batches = []  # (jobs, Ws, shapes, H)
     with torch.no_grad():
         for key, members in groups.items():
@@ -276,7 +326,9 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                     if transform:  # main.py:224-232: transform, decompose the fp32 transform
                         if hj is not None and _next_pow2(W.shape[1]) != W.shape[1]:
                             raise ValueError(f"{name}: Hadamard padding changes n ({W.shape[1]}) but H is n x n")
-                        Wt, shp = hadamard_transform(W.to(device))
+                        if hadamard_signs is not None:
+                            seeds[name] = hadamard_sign_seeds(hadamard_signs, name, W.shape[1])
+                        Wt, shp = hadamard_transform(W.to(device), signs=_sign_vectors(seeds.get(name), W.shape))
                         Ws.append(Wt)
                         shapes.append(shp)
                     else:
@@ -294,7 +346,8 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                 dev = W.device if W.device.type == "cuda" else torch.device(device)
                 out = _reconstruct(dec, dev)
                 if transform:
-                    out = hadamard_transform(out, inverse=True, original_shape=shapes[i]).contiguous()
+                    out = hadamard_transform(out, inverse=True, original_shape=shapes[i],
+                                             signs=_sign_vectors(seeds.get(name), shapes[i])).contiguous()
                 err = _rel_error(W.to(dev), out)
                 if hadamard and not hadamard_gate:
                     # main.py:221-240: the Hadamard branch always writes the recovered
@@ -310,7 +363,8 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                     bias = getattr(module, "bias", None)
                     if packed_hadamard:
                         lin = HadamardCalderaLinear.from_decomposition(dec, qp.Q_bits, shapes[i], bias=bias,
-                                                                       Q_method=q_method, **fbits)
+                                                                       Q_method=q_method, sign_seeds=seeds.get(name),
+                                                                       **fbits)
                     else:
                         lin = CalderaLinear.from_decomposition(dec, qp.Q_bits, bias=bias, Q_method=q_method, **fbits)
                     _set_module(model, name, lin.to(W.device))
@@ -329,6 +383,14 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
     return rep
 
 
+def _sign_vectors(seeds, shape):
+    """`hadamard_transform`'s signs for a layer of `shape` with the seeds (seed_out, seed_in), None for None."""
+    if seeds is None:
+        return None
+    from .linear import hadamard_sign_vector
+    return hadamard_sign_vector(seeds[0], shape[0]), hadamard_sign_vector(seeds[1], shape[1])
+
+
 def _set_module(model: torch.nn.Module, name: str, new: torch.nn.Module):
     """Replace the submodule `name` (dotted, as named_modules gives it) of `model`."""
     parent_name, _, leaf = name.rpartition(".")
@@ -340,7 +402,8 @@ def apply_packed_results(model: torch.nn.Module, results, device=None) -> list:
     """Replace each `nn.Linear` named by a `sharding.MatrixResult` (e.g. from `load_results`) by
     a `linear.CalderaLinear` holding that result (the module's bias is kept); a result whose
     `extra` has "hadamard": [m, n] (a layer decomposed in the Hadamard basis, on the padded grid)
-    is matched against that original shape and becomes a `linear.HadamardCalderaLinear`.  device: where
+    is matched against that original shape and becomes a `linear.HadamardCalderaLinear` (a signed one, with
+    the same sign vectors, when `extra` also has "hadamard_signs": [seed_out, seed_in]).  device: where
     the new layers live (default: each replaced module's own device).  KeyError for a result
     whose module the model does not have; returns the replaced names.  A `linear.CalderaLinearGroup` that a
     replaced module belonged to is dissolved (a plain packed layer holds no `weight` and is refused by

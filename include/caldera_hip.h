@@ -1061,6 +1061,54 @@ typedef struct cq_hadamard_glu_args {
 
 int cq_hadamard_glu_rows(const cq_hadamard_glu_args* a, void* stream);
 
+/* Randomised Hadamard transform (ABI 5, additive): the three entries above with +-1 sign vectors, the
+ * transform CALDERA and QuIP# use for incoherence processing, y = diag(s_out) H diag(s_in) x:
+ *
+ *   y[t, i] = s_out[i] * (c * sum_{j < n_in} (-1)^popcount(i & j) s_in[j] x[t, j]) (+ bias[i])
+ *
+ * Contract (cq_hadamard_signed_rows):
+ *   - `a` is cq_hadamard_rows' argument and carries its whole contract and its CQ_EINVAL rules;
+ *   - sign_in (n_in int8) and sign_out (n_out int8) live on the device; either may be NULL (no flips on
+ *     that side).  An element is negated iff its byte is negative: the value of a non-negative byte does
+ *     not matter.  Bytes are read only inside [0, n_in) and [0, n_out); a whole chunk of four is one
+ *     4-byte load where the vector's address is a multiple of four, the scalar path otherwise;
+ *   - sign_in is applied to x as it is widened to fp32, sign_out to the finished c * sum, before the
+ *     bias and before the output rounding.  Both flips are exact (the float's sign bit), so
+ *       signed(x, sign_in = s, bias = b)  has the bits of  cq_hadamard_rows(s * x, bias = b),
+ *       signed(x, sign_out = s)           has the bits of  s * cq_hadamard_rows(x)   (no bias),
+ *     and with both pointers NULL the entry gives cq_hadamard_rows' bits.  The stage order is that of
+ *     cq_hadamard_rows: a function of P alone;
+ *   - the same kernels as the unsigned entries, instantiated on parameters that carry the two vectors; the
+ *     unsigned entries' code is not changed by it.
+ * cq_hadamard_signed_group_rows: cq_hadamard_group_rows' contract over members of this struct; member i's
+ * y has the bits cq_hadamard_signed_rows gives on the same member.
+ * cq_hadamard_signed_glu_rows: cq_hadamard_glu_rows' contract with v_g and v_u the fp32 values
+ * cq_hadamard_signed_rows forms with sign_out = sign_g resp. sign_u (n_out int8 each, either may be NULL,
+ * no input signs): the output signs of the gate and up transforms, applied before their biases, the
+ * activation and the product. */
+typedef struct cq_hadamard_signed_args {
+    cq_hadamard_args a;
+    const int8_t* sign_in;                     /* n_in int8 or NULL: x[t, j] is negated iff sign_in[j] < 0 */
+    const int8_t* sign_out;                    /* n_out int8 or NULL: c * sum is negated iff sign_out[i] < 0 */
+} cq_hadamard_signed_args;
+
+int cq_hadamard_signed_rows(const cq_hadamard_signed_args* a, void* stream);
+
+typedef struct cq_hadamard_signed_group_args {
+    int32_t count;                                 /* 1 .. CQ_HADAMARD_GROUP_MAX */
+    const cq_hadamard_signed_args* members;        /* host array of `count` transforms */
+} cq_hadamard_signed_group_args;
+
+int cq_hadamard_signed_group_rows(const cq_hadamard_signed_group_args* g, void* stream);
+
+typedef struct cq_hadamard_signed_glu_args {
+    cq_hadamard_glu_args a;
+    const int8_t* sign_g;                      /* n_out int8 or NULL: output signs of the gate transform */
+    const int8_t* sign_u;                      /* n_out int8 or NULL: output signs of the up transform */
+} cq_hadamard_signed_glu_args;
+
+int cq_hadamard_signed_glu_rows(const cq_hadamard_signed_glu_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
