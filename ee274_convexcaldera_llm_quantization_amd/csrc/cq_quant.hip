@@ -252,7 +252,8 @@ __global__ __launch_bounds__(kThreads) void quant_block_kernel(
                 if (BITS <= 8) reinterpret_cast<int8_t*>(codes)[e] = (int8_t)(int)c;
                 else reinterpret_cast<int16_t*>(codes)[e] = (int16_t)(int)c;
             }
-            if (deq) deq[e] = dequant(c, k, s);
+            // the reference dequantises the integer code: c = -0.0f (a small negative x) gives +0.0
+            if (deq) deq[e] = dequant(c + 0.0f, k, s);
         }
         if constexpr (BITS <= 4) if (packed) {
             // pack after codes are known: recompute per byte group (cheap, L1-resident)
@@ -343,7 +344,9 @@ __global__ __launch_bounds__(kThreads) void quant_known_kernel(
                 reinterpret_cast<short4*>(reinterpret_cast<int16_t*>(codes) + eb)[0] = c4;
             }
         }
-        if (deq) reinterpret_cast<float4*>(deq + eb)[0] = make_float4(ds[0], ds[1], ds[2], ds[3]);
+        // the reference dequantises the integer code: c = -0.0f (a small negative x) gives +0.0
+        if (deq) reinterpret_cast<float4*>(deq + eb)[0] =
+            make_float4(ds[0] + 0.0f, ds[1] + 0.0f, ds[2] + 0.0f, ds[3] + 0.0f);
         if (PACK) {
             const uint32_t q0 = (uint32_t)((int)cs[0] + (int)k), q1 = (uint32_t)((int)cs[1] + (int)k);
             const uint32_t q2 = (uint32_t)((int)cs[2] + (int)k), q3 = (uint32_t)((int)cs[3] + (int)k);
