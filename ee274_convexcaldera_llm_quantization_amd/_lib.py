@@ -1772,37 +1772,114 @@ def linear_dequant(codes, qscale, gscale, L, R, w, *, m, n, bits, q_format, r=No
 
 
 # ---------------------------------------------------------------------------- Hadamard transform
-HADAMARD_MAX_N = 32768  # include/caldera_hip.h CQ_HADAMARD_MAX_N
+HADAMARD_MAX_N = 32768      # include/caldera_hip.h CQ_HADAMARD_MAX_N
+HADAMARD_GROUP_MAX = 8      # CQ_HADAMARD_GROUP_MAX
+HADAMARD_GLU_MAX_N = 16384  # CQ_HADAMARD_GLU_MAX_N
+
+# The six builders below (rows, group, glu; unsigned and signed) are made of the four pieces that follow, and
+# every piece raises in the name `who` of the entry it is building for: a signed entry, or a group's
+# "<entry>: member i", passes its own name down instead of rewriting the callee's message.
 
 
-def _hadamard_need(cond, what):
-    if not cond:
-        raise ValueError(f"cq_hadamard_rows: {what}")
+def _hadamard_operand(a, who, name, t, cols, first):
+    """One activation operand of a transform, `t` called `name`: a (rows, cols) fp16 / bf16 / fp32 matrix with
+    unit column stride and the row count of the call's first operand, `first` = (its name, the tensor).
+    Fills a.<name>, a.<name>_dtype and a.ld<name>; a single row may have any stride, so its leading dimension
+    is raised to cols (the C entries refuse a smaller one)."""
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{who}: {name} must be a matrix with unit column stride")
+    dtype = _ACT_DT.get(t.dtype)
+    if dtype is None:
+        raise ValueError(f"{who}: {name} must be fp16, bf16 or fp32, got {t.dtype}")
+    rows, width = t.shape
+    if width != cols:
+        raise ValueError(f"{who}: {name} {tuple(t.shape)} does not have {cols} columns")
+    if rows != first[1].shape[0]:
+        raise ValueError(f"{who}: {first[0]} {tuple(first[1].shape)} and {name} {tuple(t.shape)} differ in rows")
+    setattr(a, name, t.data_ptr())
+    setattr(a, name + "_dtype", dtype)
+    setattr(a, "ld" + name, t.stride(0) if rows > 1 else max(t.stride(0), cols))
 
 
-def hadamard_args(x, y, *, n_in, n_out, P, bias=None, into=None) -> HadamardArgs:
+def _hadamard_extents(a, who, rows, n_in, n_out, P, max_P):
+    """a.rows, a.n_in, a.n_out, a.P of a transform of length P, a power of two up to max_P."""
+    P = int(P)
+    if not 1 <= P <= max_P or P & (P - 1):
+        raise ValueError(f"{who}: P = {P} is not a power of two in [1, {max_P}]")
+    if not (1 <= n_in <= P and 0 <= n_out <= P):
+        raise ValueError(f"{who}: n_in = {n_in} / n_out = {n_out} do not fit P = {P}")
+    a.rows, a.n_in, a.n_out, a.P = rows, n_in, n_out, P
+
+
+def _hadamard_bias(a, who, name, bias, n_out):
+    """a.<name> of a contiguous fp32 (n_out,) bias; None leaves the struct's NULL."""
+    if bias is not None:
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (n_out,) or not bias.is_contiguous():
+            raise ValueError(f"{who}: {name} must be a contiguous fp32 ({n_out},) vector, got {bias.dtype} "
+                             f"{tuple(bias.shape)}")
+        setattr(a, name, bias.data_ptr())
+
+
+def _hadamard_sign(s, who, name, sign, length, device):
+    """s.<name> of the int8 sign vector `sign` (at least `length` entries, contiguous, on `device`); None
+    leaves the struct's NULL."""
+    if sign is None:
+        return
+    if not isinstance(sign, torch.Tensor) or sign.dtype != torch.int8:
+        raise ValueError(f"{who}: {name} must be an int8 tensor, got {getattr(sign, 'dtype', type(sign).__name__)}")
+    if sign.dim() != 1 or not sign.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous vector, got shape {tuple(sign.shape)}")
+    if sign.numel() < length:
+        raise ValueError(f"{who}: {name} has {sign.numel()} entries, fewer than the {length} the transform reads")
+    if sign.device != device:
+        raise ValueError(f"{who}: {name} is on {sign.device}, the transform's operands on {device}")
+    setattr(s, name, sign.data_ptr())
+
+
+def _hadamard_group(who, members, member_args, Member, Group):
+    """The group struct `Group` over an array of 1 .. HADAMARD_GROUP_MAX `Member` structs.  member_args(mem, into,
+    who) fills one member from its dict, in the name "<who>: member i", and returns its cq_hadamard_args; the
+    members must share the row count and P.  The struct keeps the member array alive."""
+    members = list(members)
+    if not 1 <= len(members) <= HADAMARD_GROUP_MAX:
+        raise ValueError(f"{who}: count {len(members)} not in 1 .. {HADAMARD_GROUP_MAX}")
+    arr = (Member * len(members))()
+    first = None
+    for i, mem in enumerate(members):
+        a = member_args(mem, arr[i], f"{who}: member {i}")
+        first = a if first is None else first
+        for field in ("rows", "P"):
+            if getattr(a, field) != getattr(first, field):
+                raise ValueError(f"{who}: member {i}: {field} {getattr(a, field)} differs from member 0's "
+                                 f"{getattr(first, field)}")
+    g = Group()
+    g.count = len(members)
+    g.members = ctypes.cast(arr, ctypes.POINTER(Member))
+    g._members = arr
+    return g
+
+
+def _hadamard_run(name, build, tensors, built_first=False):
+    """The tail of the six wrappers: no CPU tensor among `tensors`, the struct from build(), the entry `name`
+    on the stream of the first tensor's device.  The unsigned wrappers look at the device before they build the
+    struct; the signed ones build first (built_first), so a wrong sign vector is reported before a CPU tensor."""
+    if not built_first:
+        _require_hip(*tensors)
+    a = build()
+    if built_first:
+        _require_hip(*tensors)
+    _check(getattr(load(), name)(ctypes.byref(a), _stream(tensors[0].device)), name)
+
+
+def hadamard_args(x, y, *, n_in, n_out, P, bias=None, into=None, who="cq_hadamard_rows") -> HadamardArgs:
     """cq_hadamard_args for x (rows, n_in) and y (rows, n_out), each fp16 / bf16 / fp32 and
     possibly a view with a row stride (unit column stride), bias (n_out,) fp32 or None.  into: the
-    (zeroed) struct to fill, e.g. an element of a member array."""
-    need = _hadamard_need
-    for name, t, cols in (("x", x, n_in), ("y", y, n_out)):
-        need(t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1), f"{name} must be a matrix with unit column stride")
-        need(t.dtype in _ACT_DT, f"{name} must be fp16, bf16 or fp32, got {t.dtype}")
-        need(t.shape[1] == cols, f"{name} {tuple(t.shape)} does not have {cols} columns")
-    need(x.shape[0] == y.shape[0], f"x {tuple(x.shape)} and y {tuple(y.shape)} differ in rows")
-    P = int(P)
-    need(1 <= P <= HADAMARD_MAX_N and P & (P - 1) == 0, f"P = {P} is not a power of two in [1, {HADAMARD_MAX_N}]")
-    need(1 <= n_in <= P and 0 <= n_out <= P, f"n_in = {n_in} / n_out = {n_out} do not fit P = {P}")
-    if bias is not None:
-        need(bias.dtype == torch.float32 and tuple(bias.shape) == (n_out,) and bias.is_contiguous(),
-             f"bias must be a contiguous fp32 ({n_out},) vector, got {bias.dtype} {tuple(bias.shape)}")
+    (zeroed) struct to fill, e.g. an element of a member array.  who: the entry the checks speak for."""
     a = HadamardArgs() if into is None else into
-    rows = x.shape[0]
-    a.x, a.x_dtype, a.ldx = x.data_ptr(), _ACT_DT[x.dtype], (x.stride(0) if rows > 1 else max(x.stride(0), n_in))
-    a.y, a.y_dtype, a.ldy = y.data_ptr(), _ACT_DT[y.dtype], (y.stride(0) if rows > 1 else max(y.stride(0), n_out))
-    a.rows, a.n_in, a.n_out, a.P = rows, n_in, n_out, P
-    if bias is not None:
-        a.bias = bias.data_ptr()
+    _hadamard_operand(a, who, "x", x, n_in, ("x", x))
+    _hadamard_operand(a, who, "y", y, n_out, ("x", x))
+    _hadamard_extents(a, who, x.shape[0], n_in, n_out, P, HADAMARD_MAX_N)
+    _hadamard_bias(a, who, "bias", bias, n_out)
     return a
 
 
@@ -1810,14 +1887,8 @@ def hadamard_rows(x, y, *, n_in, n_out, P, bias=None):
     """y[t, :n_out] = (H_P pad(x[t, :n_in]))[:n_out] / sqrt(P) (+ bias): the normalised
     Sylvester-Hadamard transform of every row (cq_hadamard_rows).  x and y must not overlap.
     No workspace, no host synchronisation."""
-    _require_hip(x, y, bias)
-    a = hadamard_args(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias)
-    _check(load().cq_hadamard_rows(ctypes.byref(a), _stream(x.device)), "cq_hadamard_rows")
+    _hadamard_run("cq_hadamard_rows", lambda: hadamard_args(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias), (x, y, bias))
     return y
-
-
-HADAMARD_GROUP_MAX = 8      # include/caldera_hip.h CQ_HADAMARD_GROUP_MAX
-HADAMARD_GLU_MAX_N = 16384  # CQ_HADAMARD_GLU_MAX_N
 
 
 def hadamard_group_args(members) -> HadamardGroupArgs:
@@ -1825,26 +1896,10 @@ def hadamard_group_args(members) -> HadamardGroupArgs:
     `hadamard_args`' arguments as keys (x, y, n_in, n_out, P and optionally bias).  Each member passes
     `hadamard_args`' host-side checks; the members must share the row count and P.  The struct keeps
     the member array alive."""
-    members = list(members)
-    if not 1 <= len(members) <= HADAMARD_GROUP_MAX:
-        raise ValueError(f"cq_hadamard_group_rows: count {len(members)} not in 1 .. {HADAMARD_GROUP_MAX}")
-    arr = (HadamardArgs * len(members))()
-    for i, mem in enumerate(members):
-        try:
-            a = hadamard_args(mem["x"], mem["y"], n_in=mem["n_in"], n_out=mem["n_out"], P=mem["P"],
-                              bias=mem.get("bias"), into=arr[i])
-        except ValueError as e:
-            raise ValueError(f"cq_hadamard_group_rows: member {i}: "
-                             f"{str(e).removeprefix('cq_hadamard_rows: ')}") from None
-        for field in ("rows", "P"):
-            if getattr(a, field) != getattr(arr[0], field):
-                raise ValueError(f"cq_hadamard_group_rows: member {i}: {field} {getattr(a, field)} differs from "
-                                 f"member 0's {getattr(arr[0], field)}")
-    g = HadamardGroupArgs()
-    g.count = len(members)
-    g.members = ctypes.cast(arr, ctypes.POINTER(HadamardArgs))
-    g._members = arr
-    return g
+    def member_args(mem, into, who):
+        return hadamard_args(mem["x"], mem["y"], n_in=mem["n_in"], n_out=mem["n_out"], P=mem["P"], bias=mem.get("bias"),
+                             into=into, who=who)
+    return _hadamard_group("cq_hadamard_group_rows", members, member_args, HadamardArgs, HadamardGroupArgs)
 
 
 def hadamard_group_rows(members):
@@ -1852,43 +1907,24 @@ def hadamard_group_rows(members):
     member's y receives, bit for bit, what `hadamard_rows` writes on the same arguments.  No member's y
     may overlap an x or another y.  No workspace, no host synchronisation."""
     members = list(members)
-    for mem in members:
-        _require_hip(mem["x"], mem["y"], mem.get("bias"))
-    g = hadamard_group_args(members)
-    _check(load().cq_hadamard_group_rows(ctypes.byref(g), _stream(members[0]["x"].device)), "cq_hadamard_group_rows")
+    _hadamard_run("cq_hadamard_group_rows", lambda: hadamard_group_args(members),
+                  [t for mem in members for t in (mem["x"], mem["y"], mem.get("bias"))])
     return [mem["y"] for mem in members]
 
 
-def hadamard_glu_args(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=None, act=ACT_SILU) -> HadamardGluArgs:
+def hadamard_glu_args(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=None, act=ACT_SILU, into=None,
+                      who="cq_hadamard_glu_rows") -> HadamardGluArgs:
     """cq_hadamard_glu_args for g and u (rows, n_in) and h (rows, n_out), each fp16 / bf16 / fp32 and
-    possibly a view with a row stride (unit column stride); bias_g / bias_u (n_out,) fp32 or None."""
-    def need(cond, what):
-        if not cond:
-            raise ValueError(f"cq_hadamard_glu_rows: {what}")
-    need(act in (ACT_IDENTITY, ACT_SILU), f"unknown act {act!r}")
+    possibly a view with a row stride (unit column stride); bias_g / bias_u (n_out,) fp32 or None.  into: the
+    (zeroed) struct to fill.  who: the entry the checks speak for."""
+    if act not in (ACT_IDENTITY, ACT_SILU):
+        raise ValueError(f"{who}: unknown act {act!r}")
+    a = HadamardGluArgs() if into is None else into
     for name, t, cols in (("g", g, n_in), ("u", u, n_in), ("h", h, n_out)):
-        need(t.dim() == 2 and (t.shape[1] <= 1 or t.stride(1) == 1), f"{name} must be a matrix with unit column stride")
-        need(t.dtype in _ACT_DT, f"{name} must be fp16, bf16 or fp32, got {t.dtype}")
-        need(t.shape[1] == cols, f"{name} {tuple(t.shape)} does not have {cols} columns")
-        need(t.shape[0] == g.shape[0], f"g {tuple(g.shape)} and {name} {tuple(t.shape)} differ in rows")
-    P = int(P)
-    need(1 <= P <= HADAMARD_GLU_MAX_N and P & (P - 1) == 0,
-         f"P = {P} is not a power of two in [1, {HADAMARD_GLU_MAX_N}]")
-    need(1 <= n_in <= P and 0 <= n_out <= P, f"n_in = {n_in} / n_out = {n_out} do not fit P = {P}")
-    for name, b in (("bias_g", bias_g), ("bias_u", bias_u)):
-        if b is not None:
-            need(b.dtype == torch.float32 and tuple(b.shape) == (n_out,) and b.is_contiguous(),
-                 f"{name} must be a contiguous fp32 ({n_out},) vector, got {b.dtype} {tuple(b.shape)}")
-    a = HadamardGluArgs()
-    rows = g.shape[0]
-    a.g, a.g_dtype, a.ldg = g.data_ptr(), _ACT_DT[g.dtype], (g.stride(0) if rows > 1 else max(g.stride(0), n_in))
-    a.u, a.u_dtype, a.ldu = u.data_ptr(), _ACT_DT[u.dtype], (u.stride(0) if rows > 1 else max(u.stride(0), n_in))
-    a.h, a.h_dtype, a.ldh = h.data_ptr(), _ACT_DT[h.dtype], (h.stride(0) if rows > 1 else max(h.stride(0), n_out))
-    a.rows, a.n_in, a.n_out, a.P = rows, n_in, n_out, P
-    if bias_g is not None:
-        a.bias_g = bias_g.data_ptr()
-    if bias_u is not None:
-        a.bias_u = bias_u.data_ptr()
+        _hadamard_operand(a, who, name, t, cols, ("g", g))
+    _hadamard_extents(a, who, g.shape[0], n_in, n_out, P, HADAMARD_GLU_MAX_N)
+    _hadamard_bias(a, who, "bias_g", bias_g, n_out)
+    _hadamard_bias(a, who, "bias_u", bias_u, n_out)
     a.act = int(act)
     return a
 
@@ -1898,41 +1934,22 @@ def hadamard_glu_rows(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=None, act=
     two pre-activations have the bits of `hadamard_rows`' fp32 outputs and are never written; a is the
     identity or silu, h is rounded once.  P <= HADAMARD_GLU_MAX_N.  h must not overlap g or u.  No
     workspace, no host synchronisation."""
-    _require_hip(g, u, h, bias_g, bias_u)
-    a = hadamard_glu_args(g, u, h, n_in=n_in, n_out=n_out, P=P, bias_g=bias_g, bias_u=bias_u, act=act)
-    _check(load().cq_hadamard_glu_rows(ctypes.byref(a), _stream(g.device)), "cq_hadamard_glu_rows")
+    _hadamard_run("cq_hadamard_glu_rows",
+                  lambda: hadamard_glu_args(g, u, h, n_in=n_in, n_out=n_out, P=P, bias_g=bias_g, bias_u=bias_u, act=act),
+                  (g, u, h, bias_g, bias_u))
     return h
 
 
 # ---------------------------------------------------------------------------- randomised Hadamard transform
-def _sign_ptr(who, name, sign, length, device):
-    """Device pointer of the int8 sign vector `sign` (at least `length` entries, contiguous, on `device`), 0
-    for None.  ValueError in `who`'s name otherwise."""
-    if sign is None:
-        return 0
-    def need(cond, what):
-        if not cond:
-            raise ValueError(f"{who}: {name} {what}")
-    need(isinstance(sign, torch.Tensor) and sign.dtype == torch.int8,
-         f"must be an int8 tensor, got {getattr(sign, 'dtype', type(sign).__name__)}")
-    need(sign.dim() == 1 and sign.is_contiguous(), f"must be a contiguous vector, got shape {tuple(sign.shape)}")
-    need(sign.numel() >= length, f"has {sign.numel()} entries, fewer than the {length} the transform reads")
-    need(sign.device == device, f"is on {sign.device}, the transform's operands on {device}")
-    return sign.data_ptr()
-
-
 def hadamard_signed_args(x, y, *, n_in, n_out, P, bias=None, sign_in=None, sign_out=None, into=None,
                          who="cq_hadamard_signed_rows") -> HadamardSignedArgs:
     """cq_hadamard_signed_args: `hadamard_args`' operands and checks, and sign_in (>= n_in,) / sign_out
     (>= n_out,): contiguous int8 vectors on x's device, or None.  An entry flips its element iff it is
     negative."""
     s = HadamardSignedArgs() if into is None else into
-    try:
-        hadamard_args(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias, into=s.a)
-    except ValueError as e:
-        raise ValueError(f"{who}: {str(e).removeprefix('cq_hadamard_rows: ')}") from None
-    s.sign_in = _sign_ptr(who, "sign_in", sign_in, n_in, x.device)
-    s.sign_out = _sign_ptr(who, "sign_out", sign_out, n_out, x.device)
+    hadamard_args(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias, into=s.a, who=who)
+    _hadamard_sign(s, who, "sign_in", sign_in, n_in, x.device)
+    _hadamard_sign(s, who, "sign_out", sign_out, n_out, x.device)
     return s
 
 
@@ -1940,9 +1957,10 @@ def hadamard_signed_rows(x, y, *, n_in, n_out, P, bias=None, sign_in=None, sign_
     """y[t, :n_out] = sign_out * (H_P pad(sign_in * x[t, :n_in]))[:n_out] / sqrt(P) (+ bias): the randomised
     Hadamard transform of every row (cq_hadamard_signed_rows).  Both flips are exact; with both vectors
     None the bits are `hadamard_rows`'.  x and y must not overlap.  No workspace, no host synchronisation."""
-    a = hadamard_signed_args(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias, sign_in=sign_in, sign_out=sign_out)
-    _require_hip(x, y, bias, sign_in, sign_out)
-    _check(load().cq_hadamard_signed_rows(ctypes.byref(a), _stream(x.device)), "cq_hadamard_signed_rows")
+    _hadamard_run("cq_hadamard_signed_rows",
+                  lambda: hadamard_signed_args(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias, sign_in=sign_in,
+                                               sign_out=sign_out),
+                  (x, y, bias, sign_in, sign_out), built_first=True)
     return y
 
 
@@ -1950,24 +1968,12 @@ def hadamard_signed_group_args(members) -> HadamardSignedGroupArgs:
     """cq_hadamard_signed_group_args of 1 .. HADAMARD_GROUP_MAX transforms.  members: one dict per transform
     with `hadamard_signed_args`' arguments as keys (x, y, n_in, n_out, P and optionally bias, sign_in,
     sign_out); `hadamard_group_args`' rules.  The struct keeps the member array alive."""
-    who = "cq_hadamard_signed_group_rows"
-    members = list(members)
-    if not 1 <= len(members) <= HADAMARD_GROUP_MAX:
-        raise ValueError(f"{who}: count {len(members)} not in 1 .. {HADAMARD_GROUP_MAX}")
-    arr = (HadamardSignedArgs * len(members))()
-    for i, mem in enumerate(members):
-        s = hadamard_signed_args(mem["x"], mem["y"], n_in=mem["n_in"], n_out=mem["n_out"], P=mem["P"],
-                                 bias=mem.get("bias"), sign_in=mem.get("sign_in"), sign_out=mem.get("sign_out"),
-                                 into=arr[i], who=f"{who}: member {i}")
-        for field in ("rows", "P"):
-            if getattr(s.a, field) != getattr(arr[0].a, field):
-                raise ValueError(f"{who}: member {i}: {field} {getattr(s.a, field)} differs from member 0's "
-                                 f"{getattr(arr[0].a, field)}")
-    g = HadamardSignedGroupArgs()
-    g.count = len(members)
-    g.members = ctypes.cast(arr, ctypes.POINTER(HadamardSignedArgs))
-    g._members = arr
-    return g
+    def member_args(mem, into, who):
+        return hadamard_signed_args(mem["x"], mem["y"], n_in=mem["n_in"], n_out=mem["n_out"], P=mem["P"],
+                                    bias=mem.get("bias"), sign_in=mem.get("sign_in"), sign_out=mem.get("sign_out"),
+                                    into=into, who=who).a
+    return _hadamard_group("cq_hadamard_signed_group_rows", members, member_args, HadamardSignedArgs,
+                           HadamardSignedGroupArgs)
 
 
 def hadamard_signed_group_rows(members):
@@ -1975,11 +1981,9 @@ def hadamard_signed_group_rows(members):
     (cq_hadamard_signed_group_rows): each member's y receives, bit for bit, what `hadamard_signed_rows`
     writes on the same arguments.  No member's y may overlap an x or another y."""
     members = list(members)
-    g = hadamard_signed_group_args(members)
-    for mem in members:
-        _require_hip(mem["x"], mem["y"], mem.get("bias"), mem.get("sign_in"), mem.get("sign_out"))
-    _check(load().cq_hadamard_signed_group_rows(ctypes.byref(g), _stream(members[0]["x"].device)),
-           "cq_hadamard_signed_group_rows")
+    _hadamard_run("cq_hadamard_signed_group_rows", lambda: hadamard_signed_group_args(members),
+                  [t for mem in members for t in (mem["x"], mem["y"], mem.get("bias"), mem.get("sign_in"),
+                                                  mem.get("sign_out"))], built_first=True)
     return [mem["y"] for mem in members]
 
 
@@ -1989,12 +1993,9 @@ def hadamard_signed_glu_args(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=Non
     contiguous int8 vectors on g's device, or None."""
     who = "cq_hadamard_signed_glu_rows"
     s = HadamardSignedGluArgs()
-    try:
-        s.a = hadamard_glu_args(g, u, h, n_in=n_in, n_out=n_out, P=P, bias_g=bias_g, bias_u=bias_u, act=act)
-    except ValueError as e:
-        raise ValueError(f"{who}: {str(e).removeprefix('cq_hadamard_glu_rows: ')}") from None
-    s.sign_g = _sign_ptr(who, "sign_g", sign_g, n_out, g.device)
-    s.sign_u = _sign_ptr(who, "sign_u", sign_u, n_out, g.device)
+    hadamard_glu_args(g, u, h, n_in=n_in, n_out=n_out, P=P, bias_g=bias_g, bias_u=bias_u, act=act, into=s.a, who=who)
+    _hadamard_sign(s, who, "sign_g", sign_g, n_out, g.device)
+    _hadamard_sign(s, who, "sign_u", sign_u, n_out, g.device)
     return s
 
 
@@ -2003,8 +2004,8 @@ def hadamard_signed_glu_rows(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=Non
     """`hadamard_glu_rows` with output signs: h = a(sign_g * (H g / sqrt(P)) + bias_g) * (sign_u * (H u / sqrt(P))
     + bias_u) (cq_hadamard_signed_glu_rows); the pre-activations have the bits of `hadamard_signed_rows`' fp32
     outputs with sign_out = sign_g resp. sign_u.  With both None the bits are `hadamard_glu_rows`'."""
-    a = hadamard_signed_glu_args(g, u, h, n_in=n_in, n_out=n_out, P=P, bias_g=bias_g, bias_u=bias_u, act=act,
-                                 sign_g=sign_g, sign_u=sign_u)
-    _require_hip(g, u, h, bias_g, bias_u, sign_g, sign_u)
-    _check(load().cq_hadamard_signed_glu_rows(ctypes.byref(a), _stream(g.device)), "cq_hadamard_signed_glu_rows")
+    _hadamard_run("cq_hadamard_signed_glu_rows",
+                  lambda: hadamard_signed_glu_args(g, u, h, n_in=n_in, n_out=n_out, P=P, bias_g=bias_g, bias_u=bias_u,
+                                                   act=act, sign_g=sign_g, sign_u=sign_u),
+                  (g, u, h, bias_g, bias_u, sign_g, sign_u), built_first=True)
     return h

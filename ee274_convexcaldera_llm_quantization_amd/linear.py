@@ -153,18 +153,39 @@ def check_dense_prefill_tokens(tokens):
     return tokens
 
 
+def _operands(lin, L16=None, R16=None):
+    """The factor operands the layer hands to every entry, (L, R, r, L_codes, R_codes): L / R the fp16 factor --
+    L16 / R16 when given (masters rounded to fp16, or the factors a backward saved), else the layer's buffer --
+    or None for a coded factor and at rank 0; L_codes / R_codes a coded factor as its (codes, scale, bits) and
+    None otherwise.  A coded factor's fp16 buffer is None and a rank-0 layer's is an (m, 0) / (0, n) tensor,
+    which no entry is given."""
+    r = lin.rank
+    if not r:
+        return None, None, 0, None, None
+    L_codes = None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits)
+    R_codes = None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits)
+    return (None if L_codes is not None else lin.L if L16 is None else L16,
+            None if R_codes is not None else lin.R if R16 is None else R16, r, L_codes, R_codes)
+
+
+def _entry_family(lin, r, L_codes, R_codes):
+    """Which entries run the layer, forward and backward alike: (prefix, keywords) with `_lib`'s
+    <prefix>forward / <prefix>backward_input and the keywords that family takes.  A codebook Q takes
+    linear_codebook_*, a uniform Q with a coded factor linear_packed_*, fp16 factors (or none) linear_*."""
+    m, n, bits = lin.out_features, lin.in_features, lin.bits
+    if lin.q_format != Q_FORMAT_UNIFORM:
+        return "linear_codebook_", dict(m=m, n=n, bits=bits, q_format=lin.q_format, r=r, L_codes=L_codes, R_codes=R_codes)
+    if L_codes is not None or R_codes is not None:
+        return "linear_packed_", dict(m=m, n=n, bits=bits, r=r, L_codes=L_codes, R_codes=R_codes)
+    return "linear_", dict(m=m, n=n, bits=bits)
+
+
 def _dequant(lin, w: torch.Tensor, L16=None, R16=None):
     """cq_linear_dequant of the layer into w (out_features, in_features) fp16 / bf16 / fp32.
     L16 / R16: the fp16 factors to use instead of the layer's buffers (masters rounded to fp16)."""
-    L = lin.L if L16 is None else L16
-    R = lin.R if R16 is None else R16
-    coded_l, coded_r = lin.L_codes is not None, lin.R_codes is not None
-    return K.linear_dequant(
-        lin.codes, lin.qscale, lin.gscale, L if lin.rank and not coded_l else None,
-        R if lin.rank and not coded_r else None, w, m=lin.out_features, n=lin.in_features, bits=lin.bits,
-        q_format=lin.q_format, r=lin.rank,
-        L_codes=(lin.L_codes, lin.lscale, lin.L_bits) if lin.rank and coded_l else None,
-        R_codes=(lin.R_codes, lin.rscale, lin.R_bits) if lin.rank and coded_r else None)
+    L, R, r, L_codes, R_codes = _operands(lin, L16, R16)
+    return K.linear_dequant(lin.codes, lin.qscale, lin.gscale, L, R, w, m=lin.out_features, n=lin.in_features,
+                            bits=lin.bits, q_format=lin.q_format, r=r, L_codes=L_codes, R_codes=R_codes)
 
 
 def _dense_scratch(lin, L16, R16):
@@ -207,24 +228,9 @@ def _launch_packed(lin, x2: torch.Tensor, y: torch.Tensor, L16=None, R16=None):
         y32 = torch.mm(x2, W16.t(), out_dtype=torch.float32)
         y32 += lin.bias
         return y.copy_(y32)
-    L = lin.L if L16 is None else L16
-    R = lin.R if R16 is None else R16
-    if lin.q_format != Q_FORMAT_UNIFORM:
-        K.linear_codebook_forward(
-            x2, lin.codes, lin.qscale, lin.gscale, L if lin.rank else None, R if lin.rank else None, lin.bias, y,
-            m=lin.out_features, n=lin.in_features, bits=lin.bits, q_format=lin.q_format, r=lin.rank,
-            L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
-            R_codes=None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits))
-    elif lin.rank and (lin.L_codes is not None or lin.R_codes is not None):
-        K.linear_packed_forward(
-            x2, lin.codes, lin.qscale, lin.gscale, L, R, lin.bias, y, m=lin.out_features,
-            n=lin.in_features, bits=lin.bits, r=lin.rank,
-            L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
-            R_codes=None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits))
-    else:
-        K.linear_forward(x2, lin.codes, lin.qscale, lin.gscale, L if lin.rank else None,
-                         R if lin.rank else None, lin.bias, y, m=lin.out_features, n=lin.in_features,
-                         bits=lin.bits)
+    L, R, *factors = _operands(lin, L16, R16)
+    prefix, kw = _entry_family(lin, *factors)
+    getattr(K, prefix + "forward")(x2, lin.codes, lin.qscale, lin.gscale, L, R, lin.bias, y, **kw)
     return y
 
 
@@ -240,7 +246,7 @@ def _packed_backward(lin, dy16, x2, L16, R16, needs, dx_dtype, factor_dtypes):
     dL = gs dy^T (x R^T) and dR = gs (dy L)^T x.  With `lin.dense_prefill_tokens` set and T >= it,
     dx2 = dy16 W16 by the dense GEMM on a fresh materialisation (`_launch_packed`'s rounding
     sequence: each weight to fp16 once, fp32 accumulation, one rounding to dx_dtype)."""
-    m, n, r, gs = lin.out_features, lin.in_features, lin.rank, lin.gscale
+    n, r, gs = lin.in_features, lin.rank, lin.gscale
     need_x, need_L, need_R = needs
     T = dy16.shape[0]
     dx2 = dL = dR = u = None
@@ -250,23 +256,14 @@ def _packed_backward(lin, dy16, x2, L16, R16, needs, dx_dtype, factor_dtypes):
             # the dense path of `_launch_packed`, mirrored: dx = dy16 W16 from a fresh materialisation
             # (the scratch buffer does not outlive the forward); u is left to the torch product below
             _mm_into(dy16, _dense_scratch(lin, L16, R16), dx2)
-        elif lin.q_format != Q_FORMAT_UNIFORM:
-            if r and need_R and lin.R_codes is None:
-                u = torch.empty((T, r), dtype=torch.float32, device=dy16.device)
-            K.linear_codebook_backward_input(
-                dy16, lin.codes, lin.qscale, gs, L16 if r else None, R16 if r else None, dx2, m=m, n=n, bits=lin.bits,
-                q_format=lin.q_format, r=r, u_out=u,
-                L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
-                R_codes=None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits))
-        elif r and (lin.L_codes is not None or lin.R_codes is not None):
-            K.linear_packed_backward_input(
-                dy16, lin.codes, lin.qscale, gs, L16, R16, dx2, m=m, n=n, bits=lin.bits, r=r,
-                L_codes=None if lin.L_codes is None else (lin.L_codes, lin.lscale, lin.L_bits),
-                R_codes=None if lin.R_codes is None else (lin.R_codes, lin.rscale, lin.R_bits))
         else:
-            if r and need_R:
+            L, R, *factors = _operands(lin, L16, R16)
+            prefix, kw = _entry_family(lin, *factors)
+            # u = dy L for dR, from the kernel that forms it anyway (not linear_packed_*: a layer with a coded
+            # factor trains none)
+            if need_R and R is not None and prefix != "linear_packed_":
                 u = torch.empty((T, r), dtype=torch.float32, device=dy16.device)
-            K.linear_backward_input(dy16, lin.codes, lin.qscale, gs, L16, R16, dx2, m=m, n=n, bits=lin.bits, u_out=u)
+            getattr(K, prefix + "backward_input")(dy16, lin.codes, lin.qscale, gs, L, R, dx2, u_out=u, **kw)
     # the factor gradients are T-reductions of T m r and T r n flops (r / n of the code term):
     # torch matmul in fp32, z and u kept in fp32
     if need_L:
@@ -287,6 +284,29 @@ def _rows(t, cols):
     return t2
 
 
+def _check_last_dim(x, n):
+    if x.shape[-1] != n:
+        raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {n}")
+
+
+def _fp16_rows(x, n):
+    """x as the fp16 (T, n) matrix with unit column stride the packed kernels read.  (The Hadamard transforms
+    read x in its own dtype and from rows that do not overlap: `_rows`, `_hadamard_input`.)"""
+    x2 = x.reshape(-1, n).to(torch.float16)
+    return x2 if x2.stride(1) == 1 else x2.contiguous()
+
+
+def _out_dtype(dtype):
+    """The dtype the packed kernels write for an activation of `dtype`: fp16 and fp32 as they are, anything
+    else is computed in fp32 and cast."""
+    return dtype if dtype in (torch.float16, torch.float32) else torch.float32
+
+
+def _like_input(y2, x, m):
+    """The (T, m) result y2 in x's dtype and with x's leading dimensions."""
+    return y2.to(x.dtype).reshape(*x.shape[:-1], m)
+
+
 class _PackedLinearFunction(torch.autograd.Function):
     """y = x (gs (Q + L R))^T (+ bias) with a graph: the forward is `CalderaLinear.forward`'s launch
     (cq_linear_forward, or cq_linear_packed_forward with a coded factor: the same bits), the
@@ -298,26 +318,22 @@ class _PackedLinearFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, L, R, lin):
-        m, n = lin.out_features, lin.in_features
-        x2 = x.reshape(-1, n).to(torch.float16)
-        if x2.stride(1) != 1:
-            x2 = x2.contiguous()
+        x2 = _fp16_rows(x, lin.in_features)
         L16, R16 = _fp16_factors(L, R)
-        ydt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
-        y = torch.empty((x2.shape[0], m), dtype=ydt, device=x.device)
+        y = torch.empty((x2.shape[0], lin.out_features), dtype=_out_dtype(x.dtype), device=x.device)
         _launch_packed(lin, x2, y, L16, R16)
         ctx.lin, ctx.x_shape, ctx.x_dtype = lin, x.shape, x.dtype
         ctx.factor_dtypes = (None if L is None else L.dtype, None if R is None else R.dtype)
         ctx.save_for_backward(x2, L16, R16)
-        return y.to(x.dtype).reshape(*x.shape[:-1], m)
+        return _like_input(y, x, lin.out_features)
 
     @staticmethod
     def backward(ctx, gy):
         lin = ctx.lin
         x2, L16, R16 = ctx.saved_tensors
         dy16 = _rows(gy, lin.out_features).to(torch.float16)  # once: every gradient uses these values
-        dxdt = ctx.x_dtype if ctx.x_dtype in (torch.float16, torch.float32) else torch.float32
-        dx2, dL, dR = _packed_backward(lin, dy16, x2, L16, R16, ctx.needs_input_grad[:3], dxdt, ctx.factor_dtypes)
+        dx2, dL, dR = _packed_backward(lin, dy16, x2, L16, R16, ctx.needs_input_grad[:3], _out_dtype(ctx.x_dtype),
+                                       ctx.factor_dtypes)
         dx = None if dx2 is None else dx2.to(ctx.x_dtype).reshape(ctx.x_shape)
         return dx, dL, dR, None
 
@@ -343,7 +359,7 @@ class _HadamardLinearFunction(torch.autograd.Function):
         ctx.had, ctx.x_shape, ctx.x_dtype, ctx.x2_dtype = had, x.shape, x.dtype, x2.dtype
         ctx.factor_dtypes = (None if L is None else L.dtype, None if R is None else R.dtype)
         ctx.save_for_backward(xh, L16, R16)
-        return y.to(x.dtype).reshape(*x.shape[:-1], had.out_features)
+        return _like_input(y, x, had.out_features)
 
     @staticmethod
     def backward(ctx, gy):
@@ -355,24 +371,61 @@ class _HadamardLinearFunction(torch.autograd.Function):
             gy2 = gy2.float()
         T = gy2.shape[0]
         dyh = torch.empty((T, pr), dtype=torch.float16, device=gy.device)
-        if had.sign_seeds is None:
-            K.hadamard_rows(gy2, dyh, n_in=had.out_features, n_out=pr, P=pr)
-        else:
-            K.hadamard_signed_rows(gy2, dyh, n_in=had.out_features, n_out=pr, P=pr, sign_in=had.sign_out)
+        _transform(had, gy2, dyh, n_in=had.out_features, n_out=pr, P=pr, sign_in="sign_out")
         dxh, dL, dR = _packed_backward(had.inner, dyh, xh, L16, R16, ctx.needs_input_grad[:3], torch.float32,
                                        ctx.factor_dtypes)
         dx = None
         if dxh is not None:
             dx2 = torch.empty((T, had.in_features), dtype=ctx.x2_dtype, device=gy.device)
-            if had.sign_seeds is None:
-                K.hadamard_rows(dxh, dx2, n_in=pc, n_out=had.in_features, P=pc)
-            else:
-                K.hadamard_signed_rows(dxh, dx2, n_in=pc, n_out=had.in_features, P=pc, sign_out=had.sign_in)
+            _transform(had, dxh, dx2, n_in=pc, n_out=had.in_features, P=pc, sign_out="sign_in")
             dx = dx2.to(ctx.x_dtype).reshape(ctx.x_shape)
         return dx, dL, dR, None
 
 
-class CalderaLinear(torch.nn.Module):
+class _GroupMember:
+    """What `CalderaLinear` and `HadamardCalderaLinear` share beside `torch.nn.Module`: the back-reference to a
+    group, the `forward` that defers to it, the head of `_forward_alone` and `_apply`.  A subclass provides
+    `_packed` (the `CalderaLinear` whose operands the kernels read: the layer itself, or `inner`),
+    `_with_graph(x, L, R)` (its autograd function) and `_without_graph(x, L16, R16)` (its inference launches)."""
+
+    @property
+    def group(self):
+        """The `CalderaLinearGroup` (for a `HadamardCalderaLinear`: the `HadamardLinearGroup`) this layer is a
+        member of, or None.  A plain attribute kept in `__dict__`: no buffer, no state, not a submodule."""
+        return self.__dict__.get("_group")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        group = self.__dict__.get("_group")
+        if group is not None:  # a member of a group: the set's launches for the whole group
+            return group._member_forward(self, x)
+        return self._forward_alone(x)
+
+    def _forward_alone(self, x: torch.Tensor) -> torch.Tensor:
+        """The layer's own launches, whether it is in a group or not."""
+        packed = self._packed
+        if not x.is_cuda or not packed.codes.is_cuda:
+            raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
+        _check_last_dim(x, self.in_features)
+        trainable = packed.factors_trainable
+        if torch.is_grad_enabled() and (x.requires_grad
+                                        or (trainable and (packed.L.requires_grad or packed.R.requires_grad))):
+            # a coded factor has no fp16 operand (None); rank 0 has none at all
+            return self._with_graph(x, packed.L if packed.rank else None, packed.R if packed.rank else None)
+        # no graph: the inference launches (on the masters rounded to fp16 while the factors train)
+        L16, R16 = _fp16_factors(packed.L, packed.R) if trainable else (None, None)
+        return self._without_graph(x, L16, R16)
+
+    def _apply(self, fn, *args, **kwargs):
+        """Moves follow the model (`.to(device)`, `.cuda()`); dtype casts do not: `model.half()` or
+        `.to(torch.bfloat16)` leave the codes, the fp16 factors, the int8 sign vectors and the fp32 bias as stored
+        (the kernels' operand types; a cast would only lose bits), forward returns x's dtype anyway."""
+        def keep_dtype(t):
+            out = fn(t)
+            return out if out.dtype == t.dtype else t.to(out.device)
+        return super()._apply(keep_dtype, *args, **kwargs)
+
+
+class CalderaLinear(_GroupMember, torch.nn.Module):
     """One compressed layer.  Buffers (so `state_dict()` carries them): `codes` (out_features,
     row_bytes) uint8 inference layout, `L` (out_features, rank) and `R` (rank, in_features) fp16,
     `bias` (out_features,) fp32 or None.  A factor given by its codes has `L_codes`
@@ -451,15 +504,6 @@ class CalderaLinear(torch.nn.Module):
         self.register_buffer("L_codes", packed["L"])
         self.register_buffer("R_codes", packed["R"])
         self.register_buffer("bias", None if bias is None else bias.detach().to(torch.float32).contiguous())
-
-    def _apply(self, fn, *args, **kwargs):
-        """Moves follow the model (`.to(device)`, `.cuda()`); dtype casts do not: `model.half()` or
-        `.to(torch.bfloat16)` leave the codes, the fp16 factors and the fp32 bias as stored (the
-        kernel's operand types; a cast would only lose bits), forward returns x's dtype anyway."""
-        def keep_dtype(t):
-            out = fn(t)
-            return out if out.dtype == t.dtype else t.to(out.device)
-        return super()._apply(keep_dtype, *args, **kwargs)
 
     # ------------------------------------------------------------------ constructors
     @classmethod
@@ -694,39 +738,19 @@ class CalderaLinear(torch.nn.Module):
                 self.register_buffer(name, stored)
         return self
 
-    # ------------------------------------------------------------------ forward
+    # ------------------------------------------------------------------ forward (`_GroupMember`)
     @property
-    def group(self):
-        """The `CalderaLinearGroup` this layer is a member of, or None.  A plain attribute kept in
-        `__dict__`: no buffer, no state, not a submodule."""
-        return self.__dict__.get("_group")
+    def _packed(self):
+        return self
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        group = self.__dict__.get("_group")
-        if group is not None:  # a member of a CalderaLinearGroup: one launch pair for the whole group
-            return group._member_forward(self, x)
-        return self._forward_alone(x)
+    def _with_graph(self, x, L, R):
+        return _PackedLinearFunction.apply(x, L, R, self)
 
-    def _forward_alone(self, x: torch.Tensor) -> torch.Tensor:
-        """The layer's own launches, whether it is in a group or not."""
-        if not x.is_cuda or not self.codes.is_cuda:
-            raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
-        if x.shape[-1] != self.in_features:
-            raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {self.in_features}")
-        trainable = self.factors_trainable
-        if torch.is_grad_enabled() and (x.requires_grad
-                                        or (trainable and (self.L.requires_grad or self.R.requires_grad))):
-            # a coded factor has no fp16 operand (None); rank 0 has none at all
-            return _PackedLinearFunction.apply(x, self.L if self.rank else None, self.R if self.rank else None, self)
-        # no graph: the inference launch (on the masters rounded to fp16 while the factors train)
-        L16, R16 = _fp16_factors(self.L, self.R) if trainable else (None, None)
-        x2 = x.reshape(-1, self.in_features).to(torch.float16)
-        if x2.stride(1) != 1:
-            x2 = x2.contiguous()
-        ydt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
-        y = torch.empty((x2.shape[0], self.out_features), dtype=ydt, device=x.device)
+    def _without_graph(self, x, L16, R16):
+        x2 = _fp16_rows(x, self.in_features)
+        y = torch.empty((x2.shape[0], self.out_features), dtype=_out_dtype(x.dtype), device=x.device)
         _launch_packed(self, x2, y, L16, R16)
-        return y.to(x.dtype).reshape(*x.shape[:-1], self.out_features)
+        return _like_input(y, x, self.out_features)
 
 
 def _next_pow2(n: int) -> int:
@@ -769,7 +793,7 @@ def hadamard_sign_vector(seed: int, length: int) -> torch.Tensor:
     return torch.from_numpy(np.where((x >> np.uint64(63)).astype(bool), -1, 1).astype(np.int8))
 
 
-class HadamardCalderaLinear(torch.nn.Module):
+class HadamardCalderaLinear(_GroupMember, torch.nn.Module):
     """A layer decomposed in the Hadamard basis (`model.apply_caldera_quantization(packed=True,
     packed_hadamard=True)`): `inner` is the CalderaLinear of W~ ~ gs (Q + L R) ~ H1 pad(W) H2 on
     the padded (pr, pc) = (next_pow2(out_features), next_pow2(in_features)) grid, H the
@@ -829,14 +853,6 @@ class HadamardCalderaLinear(torch.nn.Module):
             dev = inner.codes.device
             self.register_buffer("sign_out", hadamard_sign_vector(self.sign_seeds[0], m).to(dev))
             self.register_buffer("sign_in", hadamard_sign_vector(self.sign_seeds[1], n).to(dev))
-
-    def _apply(self, fn, *args, **kwargs):
-        """As `CalderaLinear._apply`: moves follow the model, dtype casts (`model.half()`) leave the
-        fp32 bias as stored (the inner layer keeps its own operands the same way)."""
-        def keep_dtype(t):
-            out = fn(t)
-            return out if out.dtype == t.dtype else t.to(out.device)
-        return super()._apply(keep_dtype, *args, **kwargs)
 
     @property
     def padded_shape(self):
@@ -931,16 +947,10 @@ class HadamardCalderaLinear(torch.nn.Module):
         m, n = self.out_features, self.in_features
         Wt = self.inner.materialize(torch.float32)
         A = torch.empty((pr, n), dtype=torch.float32, device=Wt.device)
-        if self.sign_seeds is None:
-            K.hadamard_rows(Wt, A, n_in=pc, n_out=n, P=pc)
-        else:
-            K.hadamard_signed_rows(Wt, A, n_in=pc, n_out=n, P=pc, sign_out=self.sign_in)
+        _transform(self, Wt, A, n_in=pc, n_out=n, P=pc, sign_out="sign_in")
         At = A.t().contiguous()
         Wo = torch.empty((n, m), dtype=dtype, device=Wt.device)
-        if self.sign_seeds is None:
-            K.hadamard_rows(At, Wo, n_in=pr, n_out=m, P=pr)
-        else:
-            K.hadamard_signed_rows(At, Wo, n_in=pr, n_out=m, P=pr, sign_out=self.sign_out)
+        _transform(self, At, Wo, n_in=pr, n_out=m, P=pr, sign_out="sign_out")
         if out is None:
             return Wo.t().contiguous()
         if tuple(out.shape) != (m, n):
@@ -983,68 +993,92 @@ class HadamardCalderaLinear(torch.nn.Module):
         y32 = torch.empty((T, pr), dtype=torch.float32, device=x.device)
         _launch_packed(self.inner, xh, y32, L16, R16)
         y = torch.empty((T, self.out_features), dtype=x2.dtype, device=x.device)
-        if self.sign_seeds is None:
-            K.hadamard_rows(y32, y, n_in=pr, n_out=self.out_features, P=pr, bias=self.bias)
-        else:
-            K.hadamard_signed_rows(y32, y, n_in=pr, n_out=self.out_features, P=pr, bias=self.bias,
-                                   sign_out=self.sign_out)
+        _transform(self, y32, y, n_in=pr, n_out=self.out_features, P=pr, bias=self.bias, sign_out="sign_out")
         return x2, xh, y
 
     @property
-    def group(self):
-        """The `HadamardLinearGroup` this layer is a member of, or None.  A plain attribute kept in
-        `__dict__`: no buffer, no state, not a submodule."""
-        return self.__dict__.get("_group")
+    def _packed(self):
+        return self.inner
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        group = self.__dict__.get("_group")
-        if group is not None:  # a member of a HadamardLinearGroup: the set's four launches
-            return group._member_forward(self, x)
-        return self._forward_alone(x)
+    def _with_graph(self, x, L, R):
+        return _HadamardLinearFunction.apply(x, L, R, self)
 
-    def _forward_alone(self, x: torch.Tensor) -> torch.Tensor:
-        """The layer's own launches, whether it is in a group or not."""
-        if not x.is_cuda or not self.inner.codes.is_cuda:
-            raise RuntimeError("CalderaLinear needs HIP device tensors (no CPU fallback)")
-        if x.shape[-1] != self.in_features:
-            raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {self.in_features}")
-        inner = self.inner
-        trainable = inner.factors_trainable
-        if torch.is_grad_enabled() and (x.requires_grad
-                                        or (trainable and (inner.L.requires_grad or inner.R.requires_grad))):
-            return _HadamardLinearFunction.apply(x, inner.L if inner.rank else None, inner.R if inner.rank else None,
-                                                 self)
-        # no graph: the inference launches (on the masters rounded to fp16 while the factors train)
-        L16, R16 = _fp16_factors(inner.L, inner.R) if trainable else (None, None)
-        y = self._forward_launches(x, L16, R16)[2]
-        return y.to(x.dtype).reshape(*x.shape[:-1], self.out_features)
+    def _without_graph(self, x, L16, R16):
+        return _like_input(self._forward_launches(x, L16, R16)[2], x, self.out_features)
 
 
 def _group_operands(lin):
     """`_lib.linear_group_args`' member dict of one layer: the operands `_launch_packed` passes."""
-    ranked = lin.rank > 0
-    return dict(codes=lin.codes, qscale=lin.qscale, gscale=lin.gscale,
-                L=lin.L if ranked and lin.L_codes is None else None,
-                R=lin.R if ranked and lin.R_codes is None else None, bias=lin.bias,
-                m=lin.out_features, n=lin.in_features, bits=lin.bits, r=lin.rank,
-                L_codes=(lin.L_codes, lin.lscale, lin.L_bits) if ranked and lin.L_codes is not None else None,
-                R_codes=(lin.R_codes, lin.rscale, lin.R_bits) if ranked and lin.R_codes is not None else None)
+    L, R, r, L_codes, R_codes = _operands(lin)
+    return dict(codes=lin.codes, qscale=lin.qscale, gscale=lin.gscale, L=L, R=R, bias=lin.bias, m=lin.out_features,
+                n=lin.in_features, bits=lin.bits, r=r, L_codes=L_codes, R_codes=R_codes)
+
+
+def _own_inference_launch(x, packed, limit) -> bool:
+    """Whether a grouped or fused launch of the `CalderaLinear` layers `packed` is their own inference launch
+    for x: no autograd graph is needed, the token count does not exceed `limit` (None: no limit), no layer has
+    trainable factors and no layer's `dense_prefill_tokens` is reached."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return False
+    T = x.numel() // max(x.shape[-1], 1)
+    if limit is not None and T > limit:
+        return False
+    return not any(lin.factors_trainable or _use_dense(lin, T) for lin in packed)
 
 
 class _SharedInputGroup:
     """The protocol `CalderaLinearGroup` and `HadamardLinearGroup` share: a plain object over layers that
     read the same activation; each member keeps a back-reference in its `__dict__["_group"]` and calls
-    `_member_forward` from its `forward`.  A subclass validates its members and then `_adopt`s them, and
-    provides `_grouped(x)` (whether the grouped launch is the members' own inference launch for x) and
-    `_launch(x)` (the grouped launches: the members' outputs in member order).  Members provide
-    `_forward_alone(x)`."""
+    `_member_forward` from its `forward`.  The members' rules that both groups have are checked here, in one
+    order; a subclass names its member type (`_member_type`) and the largest set (`_max_members`), words the
+    refusal of another type (`_wrong_type`), and adds its own rules: `_member_free(i, lin)` raises for a
+    member that is taken in some other way, `_misfit(members, labels)` gives the reason why the first
+    len(members) members do not fit one launch (or None), `_token_limit()` the largest token count of the
+    grouped launch (None: no limit).  It provides `_launch(x)` (the grouped launches: the members' outputs in
+    member order).  Members provide `_forward_alone(x)` and `_packed` (`_GroupMember`)."""
 
-    def _adopt(self, members):
+    def __init__(self, members):
+        members = list(members)
+        who, kind = type(self).__name__, self._member_type
+        if not 1 <= len(members) <= self._max_members():
+            raise ValueError(f"{who}: {len(members)} members, not 1 .. {self._max_members()}")
+        labels = [f"member {i}" for i in range(len(members))]
+        for i, lin in enumerate(members):
+            if not isinstance(lin, kind):
+                raise ValueError(f"{who}: member {i} {self._wrong_type(lin)}")
+            if any(lin is other for other in members[:i]):
+                raise ValueError(f"{who}: member {i} is given twice")
+            if lin.__dict__.get("_group") is not None:
+                raise ValueError(f"{who}: member {i} is already in a group (dissolve() it first)")
+            self._member_free(i, lin)
+            device, first = lin._packed.codes.device, members[0]
+            if device != first._packed.codes.device:
+                raise ValueError(f"{who}: member {i}: device {device} differs from member 0's "
+                                 f"{first._packed.codes.device}")
+            if lin.in_features != first.in_features:
+                raise ValueError(f"{who}: member {i}: in_features {lin.in_features} differs from member 0's "
+                                 f"{first.in_features}")
+            why = self._misfit(members[:i + 1], labels)
+            if why is not None:
+                raise ValueError(f"{who}: {why}")
         self.members = tuple(members)
         self._key = None    # (weakref of x, x._version, x.data_ptr()) of the kept outputs
         self._kept = {}     # id(member) -> its output for that x, until claimed
         for lin in self.members:
             lin.__dict__["_group"] = self
+
+    def _wrong_type(self, lin):
+        return f"is a {type(lin).__name__}, not a {self._member_type.__name__}"
+
+    def _member_free(self, i, lin):
+        pass
+
+    def _token_limit(self):
+        return None
+
+    def _grouped(self, x) -> bool:
+        """Whether the grouped launches are the members' own inference launches for this x."""
+        return _own_inference_launch(x, [lin._packed for lin in self.members], self._token_limit())
 
     def __len__(self):
         return len(self.members)
@@ -1123,53 +1157,28 @@ class CalderaLinearGroup(_SharedInputGroup):
     `copy.deepcopy` or pickling of a single grouped layer takes the group, and with it the siblings,
     along; copy the model that holds them all, or `dissolve()` first."""
 
-    def __init__(self, members):
-        members = list(members)
-        if not 1 <= len(members) <= K.LINEAR_GROUP_MAX:
-            raise ValueError(f"CalderaLinearGroup: {len(members)} members, not 1 .. {K.LINEAR_GROUP_MAX}")
-        first = None
-        for i, lin in enumerate(members):
-            if isinstance(lin, HadamardCalderaLinear):
-                raise ValueError(f"CalderaLinearGroup: member {i} is a HadamardCalderaLinear: its input and output "
-                                 "transforms are per layer, it cannot be grouped")
-            if not isinstance(lin, CalderaLinear):
-                raise ValueError(f"CalderaLinearGroup: member {i} is a {type(lin).__name__}, not a CalderaLinear")
-            if any(lin is other for other in members[:i]):
-                raise ValueError(f"CalderaLinearGroup: member {i} is given twice")
-            if lin.__dict__.get("_group") is not None:
-                raise ValueError(f"CalderaLinearGroup: member {i} is already in a group (dissolve() it first)")
-            if first is None:
-                first = lin
-            if lin.codes.device != first.codes.device:
-                raise ValueError(f"CalderaLinearGroup: member {i}: device {lin.codes.device} differs from member 0's "
-                                 f"{first.codes.device}")
-            if lin.in_features != first.in_features:
-                raise ValueError(f"CalderaLinearGroup: member {i}: in_features {lin.in_features} differs from "
-                                 f"member 0's {first.in_features}")
-            why = _formats_fit(members[:i + 1], [f"member {j}" for j in range(i + 1)])
-            if why is not None:
-                raise ValueError(f"CalderaLinearGroup: {why}")
-        self._adopt(members)
+    _member_type = CalderaLinear
 
-    def _grouped(self, x) -> bool:
-        """Whether the grouped launch is the members' own inference launch for this x."""
-        if torch.is_grad_enabled() and x.requires_grad:
-            return False
-        T = x.numel() // max(x.shape[-1], 1)
-        return not any(lin.factors_trainable or _use_dense(lin, T) for lin in self.members)
+    def _max_members(self):
+        return K.LINEAR_GROUP_MAX
+
+    def _wrong_type(self, lin):
+        if isinstance(lin, HadamardCalderaLinear):
+            return "is a HadamardCalderaLinear: its input and output transforms are per layer, it cannot be grouped"
+        return super()._wrong_type(lin)
+
+    def _misfit(self, members, labels):  # as each member is reached: the first misfit in member order is reported
+        return _formats_fit(members, labels)
 
     def _launch(self, x):
         """One cq_linear_group_forward on x: `CalderaLinear.forward`'s x handling and output dtype."""
         n = self.members[0].in_features
-        if x.shape[-1] != n:
-            raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {n}")
-        x2 = x.reshape(-1, n).to(torch.float16)
-        if x2.stride(1) != 1:
-            x2 = x2.contiguous()
-        ydt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
-        ys = [torch.empty((x2.shape[0], lin.out_features), dtype=ydt, device=x.device) for lin in self.members]
+        _check_last_dim(x, n)
+        x2 = _fp16_rows(x, n)
+        ys = [torch.empty((x2.shape[0], lin.out_features), dtype=_out_dtype(x.dtype), device=x.device)
+              for lin in self.members]
         K.linear_group_forward(x2, [_group_operands(lin) for lin in self.members], ys, self.members[0].q_format)
-        return tuple(y.to(x.dtype).reshape(*x.shape[:-1], lin.out_features) for y, lin in zip(ys, self.members))
+        return tuple(_like_input(y, x, lin.out_features) for y, lin in zip(ys, self.members))
 
 
 def _formats_fit(layers, labels, what=""):
@@ -1193,22 +1202,39 @@ def _formats_fit(layers, labels, what=""):
     return None
 
 
+def _hadamard_entry(had, name):
+    """(entry, signed): `_lib`'s hadamard_<name> for an unsigned layer, hadamard_signed_<name> for a signed one,
+    looked up when called.  The one place that tells the two apart: an unsigned layer launches the unsigned
+    entries, with their keywords."""
+    if had.sign_seeds is None:
+        return getattr(K, "hadamard_" + name), False
+    return getattr(K, "hadamard_signed_" + name), True
+
+
+def _transform(had, x, y, *, n_in, n_out, P, bias=None, sign_in=None, sign_out=None):
+    """cq_hadamard_rows on x into y for an unsigned layer, cq_hadamard_signed_rows for a signed one.  sign_in /
+    sign_out: which of the layer's vectors, "sign_in" (sv) or "sign_out" (su), flips the transform's input resp.
+    output (None: no flip); an unsigned layer has neither vector and its entry neither keyword."""
+    entry, signed = _hadamard_entry(had, "rows")
+    if not signed:
+        return entry(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias)
+    return entry(x, y, n_in=n_in, n_out=n_out, P=P, bias=bias, sign_in=sign_in and getattr(had, sign_in),
+                 sign_out=sign_out and getattr(had, sign_out))
+
+
 def _hadamard_input(had, x):
     """(x2, x^) of `HadamardCalderaLinear._forward_launches`: the (T, in_features) view of x the input
     transform reads and the fp16 (T, pc) transform every layer with this in_features takes."""
     n, pc = had.in_features, had.padded_shape[1]
-    if x.shape[-1] != n:
-        raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {n}")
+    _check_last_dim(x, n)
     x2 = x.reshape(-1, n)
     if x2.dtype not in (torch.float16, torch.bfloat16, torch.float32):
         x2 = x2.float()
-    if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < n):
+    if x2.stride(1) != 1 or (x2.shape[0] > 1 and x2.stride(0) < n):  # `_rows`' rule
         x2 = x2.contiguous()
     xh = torch.empty((x2.shape[0], pc), dtype=torch.float16, device=x.device)
-    if had.sign_seeds is None:
-        K.hadamard_rows(x2, xh, n_in=n, n_out=pc, P=pc)
-    else:  # x^ = H2 (sv * pad(x)): every signed layer with this in_features and seed_in takes it
-        K.hadamard_signed_rows(x2, xh, n_in=n, n_out=pc, P=pc, sign_in=had.sign_in)
+    # signed: x^ = H2 (sv * pad(x)), which every signed layer with this in_features and seed_in takes
+    _transform(had, x2, xh, n_in=n, n_out=pc, P=pc, sign_in="sign_in")
     return x2, xh
 
 
@@ -1256,42 +1282,22 @@ class HadamardLinearGroup(_SharedInputGroup):
     does not exceed `HADAMARD_GROUP_TOKEN_LIMIT`; otherwise every member runs alone.  The inner group
     entry is called on the inner layers' operands directly: no `CalderaLinearGroup` is made or disturbed."""
 
-    def __init__(self, members):
-        members = list(members)
-        who = "HadamardLinearGroup"
-        if not 1 <= len(members) <= K.HADAMARD_GROUP_MAX:
-            raise ValueError(f"{who}: {len(members)} members, not 1 .. {K.HADAMARD_GROUP_MAX}")
-        for i, had in enumerate(members):
-            if not isinstance(had, HadamardCalderaLinear):
-                raise ValueError(f"{who}: member {i} is a {type(had).__name__}, not a HadamardCalderaLinear")
-            if any(had is other for other in members[:i]):
-                raise ValueError(f"{who}: member {i} is given twice")
-            if had.__dict__.get("_group") is not None:
-                raise ValueError(f"{who}: member {i} is already in a group (dissolve() it first)")
-            if had.inner.__dict__.get("_group") is not None:
-                raise ValueError(f"{who}: member {i}: inner is in a CalderaLinearGroup (dissolve() it first)")
-            first = members[0]
-            if had.inner.codes.device != first.inner.codes.device:
-                raise ValueError(f"{who}: member {i}: device {had.inner.codes.device} differs from member 0's "
-                                 f"{first.inner.codes.device}")
-            if had.in_features != first.in_features:
-                raise ValueError(f"{who}: member {i}: in_features {had.in_features} differs from member 0's "
-                                 f"{first.in_features}")
-        why = _formats_fit([had.inner for had in members], [f"member {i}" for i in range(len(members))], "inner ")
-        if why is None:
-            why = _signs_fit(members, [f"member {i}" for i in range(len(members))])
-        if why is not None:
-            raise ValueError(f"{who}: {why}")
-        self._adopt(members)
+    _member_type = HadamardCalderaLinear
 
-    def _grouped(self, x) -> bool:
-        """Whether the grouped launches are the members' own inference launches for this x."""
-        if torch.is_grad_enabled() and x.requires_grad:
-            return False
-        T = x.numel() // max(x.shape[-1], 1)
-        if HADAMARD_GROUP_TOKEN_LIMIT is not None and T > HADAMARD_GROUP_TOKEN_LIMIT:
-            return False
-        return not any(had.inner.factors_trainable or _use_dense(had.inner, T) for had in self.members)
+    def _max_members(self):
+        return K.HADAMARD_GROUP_MAX
+
+    def _member_free(self, i, had):
+        if had.inner.__dict__.get("_group") is not None:
+            raise ValueError(f"{type(self).__name__}: member {i}: inner is in a CalderaLinearGroup (dissolve() it first)")
+
+    def _misfit(self, members, labels):  # on the whole set, after every member's own rules
+        if len(members) < len(labels):
+            return None
+        return _formats_fit([had.inner for had in members], labels, "inner ") or _signs_fit(members, labels)
+
+    def _token_limit(self):
+        return HADAMARD_GROUP_TOKEN_LIMIT
 
     def _launch(self, x):
         """`HadamardCalderaLinear._forward_launches` for every member: x^ once, the inner layers grouped,
@@ -1302,7 +1308,7 @@ class HadamardLinearGroup(_SharedInputGroup):
         K.linear_group_forward(xh, [_group_operands(had.inner) for had in self.members], y32,
                                self.members[0].inner.q_format)
         ys = [torch.empty((T, had.out_features), dtype=x2.dtype, device=x.device) for had in self.members]
-        signed = self.members[0].sign_seeds is not None
+        entry, signed = _hadamard_entry(self.members[0], "group_rows")
         buckets = {}  # pr -> the members' transforms, in member order
         for had, v, y in zip(self.members, y32, ys):
             pr = had.padded_shape[0]
@@ -1311,8 +1317,8 @@ class HadamardLinearGroup(_SharedInputGroup):
                 t["sign_out"] = had.sign_out
             buckets.setdefault(pr, []).append(t)
         for transforms in buckets.values():
-            (K.hadamard_signed_group_rows if signed else K.hadamard_group_rows)(transforms)
-        return tuple(y.to(x.dtype).reshape(*x.shape[:-1], had.out_features) for y, had in zip(ys, self.members))
+            entry(transforms)
+        return tuple(_like_input(y, x, had.out_features) for y, had in zip(ys, self.members))
 
 
 ACTIVATIONS = {"silu": K.ACT_SILU, "identity": K.ACT_IDENTITY}
@@ -1328,26 +1334,91 @@ def _act_torch(act: int, g: torch.Tensor) -> torch.Tensor:
     return torch.nn.functional.silu(g) if act == K.ACT_SILU else g
 
 
-def glu_fit(gate, up):
-    """None when the layers `gate` and `up` fit cq_linear_glu_forward, else the reason as a string that
-    names the attribute."""
+def _pair_fit(gate, up, kind, what="", refused=None):
+    """None when `gate` and `up` are two layers of type `kind` on one device with the same shape whose packed
+    layers fit one launch (`_formats_fit`, their attributes called "<what><attribute>"), else the reason as a
+    string that names the attribute.  refused: (another type, the words for a layer of it)."""
     for name, lin in (("gate_proj", gate), ("up_proj", up)):
-        if isinstance(lin, HadamardCalderaLinear):
-            return (f"{name} is a HadamardCalderaLinear: its input and output transforms are per layer, it does "
-                    "not fit the fused launch")
-        if not isinstance(lin, CalderaLinear):
-            return f"{name} is a {type(lin).__name__}, not a CalderaLinear"
+        if refused is not None and isinstance(lin, refused[0]):
+            return f"{name} {refused[1]}"
+        if not isinstance(lin, kind):
+            return f"{name} is a {type(lin).__name__}, not a {kind.__name__}"
     if gate is up:
         return "gate_proj and up_proj are the same layer"
-    if up.codes.device != gate.codes.device:
-        return f"up_proj: device {up.codes.device} differs from gate_proj's {gate.codes.device}"
+    packed = (gate._packed, up._packed)
+    if packed[1].codes.device != packed[0].codes.device:
+        return f"up_proj: device {packed[1].codes.device} differs from gate_proj's {packed[0].codes.device}"
     for attr in ("in_features", "out_features"):
         if getattr(up, attr) != getattr(gate, attr):
             return f"up_proj: {attr} {getattr(up, attr)} differs from gate_proj's {getattr(gate, attr)}"
-    return _formats_fit((gate, up), ("gate_proj", "up_proj"))
+    return _formats_fit(packed, ("gate_proj", "up_proj"), what)
 
 
-class CalderaGatedMLP(torch.nn.Module):
+def glu_fit(gate, up):
+    """None when the layers `gate` and `up` fit cq_linear_glu_forward, else the reason as a string that
+    names the attribute."""
+    return _pair_fit(gate, up, CalderaLinear, refused=(
+        HadamardCalderaLinear, "is a HadamardCalderaLinear: its input and output transforms are per layer, it does "
+                               "not fit the fused launch"))
+
+
+def hadamard_glu_fit(gate, up):
+    """None when the `HadamardCalderaLinear` layers `gate` and `up` fit `HadamardGatedMLP`'s fused launches,
+    else the reason as a string that names the attribute."""
+    return (_pair_fit(gate, up, HadamardCalderaLinear, "inner ")
+            or _signs_fit((gate, up), ("gate_proj", "up_proj")))
+
+
+class _GatedMLP(torch.nn.Module):
+    """What `CalderaGatedMLP` and `HadamardGatedMLP` share: the construction checks, the three submodules, the
+    choice between the fused launches and the formula, and `forward`.  A subclass provides `_misfit(gate, up)`
+    (its fit function, looked up when called), `_auto_limit` (whether `max_fused_tokens` may be "auto":
+    `FUSED_TOKEN_LIMIT` for the gate's Q bits) and `_fused_launches(x, gate, up, act)`."""
+
+    def __init__(self, gate_proj, up_proj, down_proj, act, max_fused_tokens):
+        super().__init__()
+        who = type(self).__name__
+        if act not in ACTIVATIONS:
+            raise ValueError(f"{who}: act {act!r} not in {tuple(ACTIVATIONS)}")
+        why = self._misfit(gate_proj, up_proj)
+        if why is not None:
+            raise ValueError(f"{who}: {why}")
+        if not isinstance(down_proj, torch.nn.Module):
+            raise ValueError(f"{who}: down_proj is a {type(down_proj).__name__}, not a module")
+        named = ("auto", None) if self._auto_limit else (None,)
+        if max_fused_tokens not in named and (isinstance(max_fused_tokens, bool)
+                                              or not isinstance(max_fused_tokens, int)):
+            words = "\"auto\", None" if self._auto_limit else "None"
+            raise ValueError(f"{who}: max_fused_tokens {max_fused_tokens!r} is not {words} or an int")
+        self.act = act
+        self.max_fused_tokens = max_fused_tokens
+        self.gate_proj, self.up_proj, self.down_proj = gate_proj, up_proj, down_proj
+
+    def extra_repr(self):
+        return f"act={self.act}"
+
+    def _fused(self, x) -> bool:
+        """Whether the fused launches are the layers' own inference launches for this x."""
+        gate, up = self.gate_proj, self.up_proj
+        if self._misfit(gate, up) is not None:
+            return False
+        limit = self.max_fused_tokens
+        if self._auto_limit and limit == "auto":
+            limit = FUSED_TOKEN_LIMIT.get(gate.bits)
+        return _own_inference_launch(x, (gate._packed, up._packed), limit)
+
+    def glu(self, x: torch.Tensor) -> torch.Tensor:
+        gate, up = self.gate_proj, self.up_proj
+        act = ACTIVATIONS[self.act]
+        if not self._fused(x):
+            return _act_torch(act, gate(x)) * up(x)
+        return self._fused_launches(x, gate, up, act)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.down_proj(self.glu(x))
+
+
+class CalderaGatedMLP(_GatedMLP):
     """A gated MLP block `down_proj(act(gate_proj(x)) * up_proj(x))` whose gate / up pair runs as one z
     launch and one code + L launch that applies the activation and the product in its epilogue
     (cq_linear_glu_forward): no separate activation and product launches, one (T, m) intermediate
@@ -1375,76 +1446,24 @@ class CalderaGatedMLP(torch.nn.Module):
     If the two layers stop fitting after construction (one of them replaced or unpacked), glu(x) takes
     the formula as well."""
 
+    _auto_limit = True
+
     def __init__(self, gate_proj, up_proj, down_proj, act="silu", max_fused_tokens="auto"):
-        super().__init__()
-        if act not in ACTIVATIONS:
-            raise ValueError(f"CalderaGatedMLP: act {act!r} not in {tuple(ACTIVATIONS)}")
-        why = glu_fit(gate_proj, up_proj)
-        if why is not None:
-            raise ValueError(f"CalderaGatedMLP: {why}")
-        if not isinstance(down_proj, torch.nn.Module):
-            raise ValueError(f"CalderaGatedMLP: down_proj is a {type(down_proj).__name__}, not a module")
-        self.act = act
-        if max_fused_tokens not in ("auto", None) and (isinstance(max_fused_tokens, bool)
-                                                       or not isinstance(max_fused_tokens, int)):
-            raise ValueError(f"CalderaGatedMLP: max_fused_tokens {max_fused_tokens!r} is not \"auto\", None or an int")
-        self.max_fused_tokens = max_fused_tokens
-        self.gate_proj, self.up_proj, self.down_proj = gate_proj, up_proj, down_proj
+        super().__init__(gate_proj, up_proj, down_proj, act, max_fused_tokens)
 
-    def extra_repr(self):
-        return f"act={self.act}"
+    def _misfit(self, gate, up):
+        return glu_fit(gate, up)
 
-    def _fused(self, x) -> bool:
-        """Whether the fused launch is the layers' own inference launch for this x."""
-        gate, up = self.gate_proj, self.up_proj
-        if glu_fit(gate, up) is not None:
-            return False
-        if torch.is_grad_enabled() and x.requires_grad:
-            return False
-        T = x.numel() // max(x.shape[-1], 1)
-        limit = FUSED_TOKEN_LIMIT.get(gate.bits) if self.max_fused_tokens == "auto" else self.max_fused_tokens
-        if limit is not None and T > limit:
-            return False
-        return not any(lin.factors_trainable or _use_dense(lin, T) for lin in (gate, up))
-
-    def glu(self, x: torch.Tensor) -> torch.Tensor:
-        gate, up = self.gate_proj, self.up_proj
-        act = ACTIVATIONS[self.act]
-        if not self._fused(x):
-            return _act_torch(act, gate(x)) * up(x)
+    def _fused_launches(self, x, gate, up, act):
         n, m = gate.in_features, gate.out_features
-        if x.shape[-1] != n:
-            raise ValueError(f"CalderaLinear: last dimension {x.shape[-1]} != in_features {n}")
-        x2 = x.reshape(-1, n).to(torch.float16)
-        if x2.stride(1) != 1:
-            x2 = x2.contiguous()
-        hdt = x.dtype if x.dtype in (torch.float16, torch.float32) else torch.float32
-        h = torch.empty((x2.shape[0], m), dtype=hdt, device=x.device)
+        _check_last_dim(x, n)
+        x2 = _fp16_rows(x, n)
+        h = torch.empty((x2.shape[0], m), dtype=_out_dtype(x.dtype), device=x.device)
         K.linear_glu_forward(x2, _group_operands(gate), _group_operands(up), h, gate.q_format, act)
-        return h.to(x.dtype).reshape(*x.shape[:-1], m)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.down_proj(self.glu(x))
+        return _like_input(h, x, m)
 
 
-def hadamard_glu_fit(gate, up):
-    """None when the `HadamardCalderaLinear` layers `gate` and `up` fit `HadamardGatedMLP`'s fused launches,
-    else the reason as a string that names the attribute."""
-    for name, had in (("gate_proj", gate), ("up_proj", up)):
-        if not isinstance(had, HadamardCalderaLinear):
-            return f"{name} is a {type(had).__name__}, not a HadamardCalderaLinear"
-    if gate is up:
-        return "gate_proj and up_proj are the same layer"
-    if up.inner.codes.device != gate.inner.codes.device:
-        return f"up_proj: device {up.inner.codes.device} differs from gate_proj's {gate.inner.codes.device}"
-    for attr in ("in_features", "out_features"):
-        if getattr(up, attr) != getattr(gate, attr):
-            return f"up_proj: {attr} {getattr(up, attr)} differs from gate_proj's {getattr(gate, attr)}"
-    return (_formats_fit((gate.inner, up.inner), ("gate_proj", "up_proj"), "inner ")
-            or _signs_fit((gate, up), ("gate_proj", "up_proj")))
-
-
-class HadamardGatedMLP(torch.nn.Module):
+class HadamardGatedMLP(_GatedMLP):
     """A gated MLP block `down_proj(act(gate_proj(x)) * up_proj(x))` whose gate and up are
     `HadamardCalderaLinear` layers, run as four launches: the input transform once (the two share
     x^ = H2 pad(x)), the inner layers' grouped launch pair (cq_linear_group_forward) into two fp32
@@ -1473,52 +1492,24 @@ class HadamardGatedMLP(torch.nn.Module):
     `HadamardLinearGroup` they belong to still serves them).  The fused path calls the entries on the
     layers' operands directly: it neither uses nor disturbs a group."""
 
-    def __init__(self, gate_proj, up_proj, down_proj, act="silu", max_fused_tokens=None):
-        super().__init__()
-        if act not in ACTIVATIONS:
-            raise ValueError(f"HadamardGatedMLP: act {act!r} not in {tuple(ACTIVATIONS)}")
-        why = hadamard_glu_fit(gate_proj, up_proj)
-        if why is not None:
-            raise ValueError(f"HadamardGatedMLP: {why}")
-        if not isinstance(down_proj, torch.nn.Module):
-            raise ValueError(f"HadamardGatedMLP: down_proj is a {type(down_proj).__name__}, not a module")
-        if max_fused_tokens is not None and (isinstance(max_fused_tokens, bool) or not isinstance(max_fused_tokens, int)):
-            raise ValueError(f"HadamardGatedMLP: max_fused_tokens {max_fused_tokens!r} is not None or an int")
-        self.act = act
-        self.max_fused_tokens = max_fused_tokens
-        self.gate_proj, self.up_proj, self.down_proj = gate_proj, up_proj, down_proj
+    _auto_limit = False
 
-    def extra_repr(self):
-        return f"act={self.act}"
+    def __init__(self, gate_proj, up_proj, down_proj, act="silu", max_fused_tokens=None):
+        super().__init__(gate_proj, up_proj, down_proj, act, max_fused_tokens)
+
+    def _misfit(self, gate, up):
+        return hadamard_glu_fit(gate, up)
 
     def _fused(self, x) -> bool:
-        """Whether the fused launches are the layers' own inference launches for this x."""
-        gate, up = self.gate_proj, self.up_proj
-        if hadamard_glu_fit(gate, up) is not None or gate.padded_shape[0] > K.HADAMARD_GLU_MAX_N:
-            return False
-        if torch.is_grad_enabled() and x.requires_grad:
-            return False
-        T = x.numel() // max(x.shape[-1], 1)
-        if self.max_fused_tokens is not None and T > self.max_fused_tokens:
-            return False
-        return not any(had.inner.factors_trainable or _use_dense(had.inner, T) for had in (gate, up))
+        return super()._fused(x) and self.gate_proj.padded_shape[0] <= K.HADAMARD_GLU_MAX_N
 
-    def glu(self, x: torch.Tensor) -> torch.Tensor:
-        gate, up = self.gate_proj, self.up_proj
-        act = ACTIVATIONS[self.act]
-        if not self._fused(x):
-            return _act_torch(act, gate(x)) * up(x)
+    def _fused_launches(self, x, gate, up, act):
         x2, xh = _hadamard_input(gate, x)
         T, pr, m = x2.shape[0], gate.padded_shape[0], gate.out_features
         v = [torch.empty((T, pr), dtype=torch.float32, device=x.device) for _ in range(2)]
         K.linear_group_forward(xh, [_group_operands(gate.inner), _group_operands(up.inner)], v, gate.inner.q_format)
         h = torch.empty((T, m), dtype=x2.dtype, device=x.device)
-        if gate.sign_seeds is None:
-            K.hadamard_glu_rows(v[0], v[1], h, n_in=pr, n_out=m, P=pr, bias_g=gate.bias, bias_u=up.bias, act=act)
-        else:
-            K.hadamard_signed_glu_rows(v[0], v[1], h, n_in=pr, n_out=m, P=pr, bias_g=gate.bias, bias_u=up.bias,
-                                       act=act, sign_g=gate.sign_out, sign_u=up.sign_out)
-        return h.to(x.dtype).reshape(*x.shape[:-1], m)
-
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.down_proj(self.glu(x))
+        entry, signed = _hadamard_entry(gate, "glu_rows")
+        signs = dict(sign_g=gate.sign_out, sign_u=up.sign_out) if signed else {}
+        entry(v[0], v[1], h, n_in=pr, n_out=m, P=pr, bias_g=gate.bias, bias_u=up.bias, act=act, **signs)
+        return _like_input(h, x, m)
