@@ -217,6 +217,10 @@ _SIGS = {
     "cq_quantize_nf": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
                                c_vp, c_vp, c_size, c_vp]),
     "cq_dequant_nf": (c_int, [c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
+    "cq_quantize_nf_std_workspace": (c_size, [c_i64, c_i64, c_i64]),
+    "cq_quantize_nf_std": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                   c_i64, c_vp, c_vp, c_size, c_vp]),
+    "cq_dequant_nf_std": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp]),
     "cq_bbint_workspace": (c_size, [c_i64, c_i64, c_i64]),
     "cq_bbint_stats": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_size, c_vp]),
     "cq_bbint_emit": (c_int, [c_vp, c_i64, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
@@ -556,6 +560,41 @@ def dequantize_nf(idx: torch.Tensor, scale: torch.Tensor, bits: int) -> torch.Te
     out = torch.empty(total, dtype=torch.float32, device=idx.device)
     _check(load().cq_dequant_nf(_p(idx), _p(scale), total, total // scale.numel(), bits, _p(out),
                                 _stream(idx.device)), "cq_dequant_nf")
+    return out
+
+
+def quantize_nf_std(x: torch.Tensor, block_size: int, bits: int, eps: float = 1e-8, *, idx=True, deq=True,
+                    err_w=None, err_ncols=None, err_out=None):
+    """Standardised NF4 / NF2 (quantization_stable_nf4.py:187-200).  x (B, numel) fp32 contiguous ->
+    dict(idx (B, numel) uint8, deq (B, numel) fp32, mean / std (B, numel // block_size) fp32).
+    block_size = 1 (no unbiased std) raises ValueError."""
+    _require_hip(x, err_w, err_out)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 2
+    B, numel = x.shape
+    dev = x.device
+    block_size = int(block_size)
+    nblk = numel // block_size if block_size > 0 else 0
+    out = {"idx": torch.empty((B, numel), dtype=torch.uint8, device=dev) if idx else None,
+           "deq": torch.empty((B, numel), dtype=torch.float32, device=dev) if deq else None,
+           "mean": torch.empty((B, nblk), dtype=torch.float32, device=dev),
+           "std": torch.empty((B, nblk), dtype=torch.float32, device=dev)}
+    lib = load()
+    ws = workspace(lib.cq_quantize_nf_std_workspace(B, numel, block_size), dev)
+    _check(lib.cq_quantize_nf_std(_p(x), B, numel, block_size, bits, eps, _p(out["idx"]), _p(out["deq"]),
+                                  _p(out["mean"]), _p(out["std"]), _p(err_w), err_ncols or 0, _wst(err_w, B),
+                                  _p(err_out), _p(ws), ws.numel(), _stream(dev)), "cq_quantize_nf_std")
+    return out
+
+
+def dequantize_nf_std(idx: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, bits: int) -> torch.Tensor:
+    """level[idx] * std[blk] + mean[blk] (quantization_stable_nf4.py:221-224); idx uint8, mean / std
+    (nblocks,) fp32."""
+    _require_hip(idx, mean, std)
+    assert mean.numel() == std.numel()
+    total = idx.numel()
+    out = torch.empty(total, dtype=torch.float32, device=idx.device)
+    _check(load().cq_dequant_nf_std(_p(idx), _p(mean), _p(std), total, total // mean.numel(), bits, _p(out),
+                                    _stream(idx.device)), "cq_dequant_nf_std")
     return out
 
 

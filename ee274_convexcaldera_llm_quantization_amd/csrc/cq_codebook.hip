@@ -5,9 +5,19 @@
 //                  dispatch :270-279 and :296-298);
 //   * bbint4 / bbint2 — per block: mean, unbiased std, |x - mean| > 6 std outliers replaced
 //                  by the mean and kept aside, min/max affine codes packed MSB-first
-//                  (quantization.py:107-243, dispatch :280-283 and :299-302).
+//                  (quantization.py:107-243, dispatch :280-283 and :299-302);
+// and the standardised NF4 / NF2 of quantization_stable_nf4.py:146-230 (cq_quantize_nf_std):
+//   per block mean and unbiased std (floored at eps) by bbint's statistics passes below, as they
+//   stand: mean32 in torch's CPU order for blocks of <= 256, else the fp64 sum / bs rounded once;
+//   std32 = max(f32(sqrt(sum (x - mean64)^2 / (bs - 1))), eps) with the fp64 sum, NaN-propagating;
+//   z = (x - mean32) / std32 (two fp32 operations), idx = #{t : z > thr_t} with nf_index's
+//   thresholds, deq = f32(level[idx] * std32) + mean32 (two roundings).  Its parameters are the
+//   pair (mean, std).  Deviation from the reference: a block of one element has no unbiased std
+//   (the reference returns NaN there); the entry refuses block_size < 2 with CQ_EINVAL.  Results
+//   for non-finite inputs are unspecified.  The whole-matrix form (block = matrix, what the engine
+//   calls) has its own emit kernel with 16-byte loads and stores (nfs_whole_kernel).
 //
-// Both are HBM-bound streaming kernels.  Numerics follow the reference op by op (this file
+// All are HBM-bound streaming kernels.  Numerics follow the reference op by op (this file
 // is built with -ffp-contract=off and IEEE division): x / scale in fp32, the thresholds
 // (l_i + l_{i+1}) / 2 in fp32, bbint's (x - min) / scale, rint (half-even) and the two
 // roundings of the dequant u * scale + min.  bbint's mean is the reference's fp32 mean: for
@@ -494,6 +504,226 @@ static BBGeom bb_geom(int64_t batch, int64_t numel, int64_t bs) {
     return g;
 }
 
+// ------------------------------------------------------------------ standardised NF
+// The block statistics are bbint's: bb_sum_kernel / bb_mean_kernel give the fp32 mean (into the
+// caller's array) and the fp64 mean, bb_var_kernel the chunk sums of (x - mean64)^2.
+
+// per block: std = max(f32(sqrt(sum (x - mean64)^2 / (bs - 1))), eps), NaN-propagating
+// (quantization_stable_nf4.py:190-193); bs >= 2 is the entry's precondition
+__global__ void nfs_std_kernel(BBGeom g, float eps, const double* __restrict__ psq, float* __restrict__ sd) {
+    const int64_t blk = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (blk >= g.nbt) return;
+    double s = 0.0;
+    for (int64_t c = 0; c < g.nch; ++c) s += psq[blk * g.nch + c];
+    sd[blk] = nanmax_f((float)sqrt(s / (double)(g.bs - 1)), eps);
+}
+
+// The same two per-block steps for blocks of several chunks (bs > 4096, mean32 = f32(mean64)): one
+// wave per block, lane l adds chunks l, l + 64, ... and the lanes are summed by wave_sum, a fixed
+// order.  A whole 4096 x 4096 matrix has 4096 chunk partials; added one by one by a single lane they
+// cost more than the three passes over the matrix.
+__global__ __launch_bounds__(kCbThreads) void nfs_mean_wave_kernel(BBGeom g, const double* __restrict__ psum,
+                                                                   double* __restrict__ mean64,
+                                                                   float* __restrict__ mean32) {
+    const int64_t blk = ((int64_t)blockIdx.x * kCbThreads + threadIdx.x) >> 6;
+    if (blk >= g.nbt) return;  // wave-uniform
+    double s = 0.0;
+    for (int64_t c = threadIdx.x & 63; c < g.nch; c += 64) s += psum[blk * g.nch + c];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) {
+        const double m = s / (double)g.bs;
+        mean64[blk] = m;
+        mean32[blk] = (float)m;
+    }
+}
+
+__global__ __launch_bounds__(kCbThreads) void nfs_std_wave_kernel(BBGeom g, float eps, const double* __restrict__ psq,
+                                                                  float* __restrict__ sd) {
+    const int64_t blk = ((int64_t)blockIdx.x * kCbThreads + threadIdx.x) >> 6;
+    if (blk >= g.nbt) return;  // wave-uniform
+    double s = 0.0;
+    for (int64_t c = threadIdx.x & 63; c < g.nch; c += 64) s += psq[blk * g.nch + c];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) sd[blk] = nanmax_f((float)sqrt(s / (double)(g.bs - 1)), eps);
+}
+
+// deq = f32(level * std) + mean: two roundings (no contraction in this file)
+__device__ __forceinline__ float nfs_deq(float level, float sd, float mu) {
+    const float p = level * sd;
+    return p + mu;
+}
+
+// any block size: one workgroup per chunk (the geometry of the statistics passes), 4 bytes per lane
+template <int BITS>
+__global__ __launch_bounds__(kCbThreads) void nfs_emit_kernel(
+    const float* __restrict__ x, BBGeom g, const float* __restrict__ mean, const float* __restrict__ sd,
+    uint8_t* __restrict__ idx, float* __restrict__ deq, const float* __restrict__ ew, int64_t encols,
+    double* __restrict__ perr, int64_t ews) {
+    __shared__ double lds[16];
+    const int64_t ch = blockIdx.x;
+    const int64_t blk = ch / g.nch, c = ch % g.nch;
+    const int64_t c0 = c * kChunk;
+    const int64_t base = blk * g.bs + c0;
+    const int64_t n = g.len(c);
+    const float mu = mean[blk], s = sd[blk];
+    const int64_t e0 = (blk % g.nblk_per) * g.bs + c0;  // of the chunk's first element, within its matrix
+    if (ew) ew += (blk / g.nblk_per) * ews;
+    double acc = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += kCbThreads) {
+        const float xv = x[base + i];
+        const int q = nf_index<BITS>((xv - mu) / s);
+        const float d = nfs_deq(nf_level<BITS>(q), s, mu);
+        if (idx) idx[base + i] = (uint8_t)q;
+        if (deq) deq[base + i] = d;
+        if (perr) {
+            const float df = d - xv;
+            acc += (double)(df * df) * (ew ? (double)ew[(e0 + i) % encols] : 1.0);
+        }
+    }
+    if (perr) {
+        const double t = block_sum_f64(acc, lds);
+        if (threadIdx.x == 0) perr[ch] = t;
+    }
+}
+
+// One element of the whole-matrix form.  y = RN(1 / s): div_rn gives the IEEE quotient in three
+// operations where `fast` (s is a normal number whose reciprocal is one too).
+template <int BITS>
+__device__ __forceinline__ int nfs_one(float xv, float mu, float s, float y, bool fast, const float* lev, float& d) {
+    const float a = xv - mu;
+    const int q = nf_index<BITS>(fast ? div_rn(a, s, y) : a / s);
+    d = nfs_deq(lev[q], s, mu);
+    return q;
+}
+
+// weighted squared error of one element: squared in fp32, weighted and summed in fp64
+__device__ __forceinline__ double nfs_err(float d, float xv, const float* __restrict__ ew, int64_t col) {
+    const float df = d - xv;
+    return (double)(df * df) * (ew ? (double)ew[col] : 1.0);
+}
+
+// block == matrix (quantize_matrix, alg.py:245-250): the form the engine runs at every Q update
+// and quantised-factor step.  Grid (g, batch); a lane takes 4 consecutive elements per step with
+// one 16-byte load of x, one 16-byte store of deq and one 4-byte store of the indices.  x + b numel
+// is 16-byte aligned only when b numel % 4 == 0, so the up to 3 elements before the first 16-byte
+// boundary of the matrix (head) and after the last whole vector (tail) are done one by one by the
+// first lanes of workgroup 0; deq / idx rows whose alignment differs from x's take scalar stores.
+template <int BITS>
+__global__ __launch_bounds__(kCbThreads) void nfs_whole_kernel(
+    const float* __restrict__ x, int64_t numel, const float* __restrict__ mean, const float* __restrict__ sd,
+    uint8_t* __restrict__ idx, float* __restrict__ deq, const float* __restrict__ ew, int64_t encols,
+    double* __restrict__ part, int64_t ews) {
+    __shared__ double lds[16];
+    __shared__ float lev[1 << BITS];
+    if (threadIdx.x < (1 << BITS)) lev[threadIdx.x] = nf_level<BITS>(threadIdx.x);
+    __syncthreads();
+    const int64_t b = blockIdx.y;
+    const float* xb = x + b * numel;
+    uint8_t* ib = idx ? idx + b * numel : nullptr;
+    float* db = deq ? deq + b * numel : nullptr;
+    if (ew) ew += b * ews;
+    const float mu = mean[b], s = sd[b];
+    const float y = 1.0f / s;
+    const bool fast = div_fast_ok(s);
+    int64_t head = (int64_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(xb) & 15u)) & 15u) >> 2);
+    head = head < numel ? head : numel;
+    const int64_t nvec = (numel - head) / 4;
+    const int64_t tail0 = head + 4 * nvec;
+    const bool dvec = db && (reinterpret_cast<uintptr_t>(db + head) & 15u) == 0;
+    const bool ivec = ib && (reinterpret_cast<uintptr_t>(ib + head) & 3u) == 0;
+    const float4* xv4 = reinterpret_cast<const float4*>(xb + head);
+    const int64_t stride = (int64_t)gridDim.x * kCbThreads;
+    int64_t v = (int64_t)blockIdx.x * kCbThreads + threadIdx.x;
+    // the column of a vector's first element, advanced by (4 stride) % encols per step
+    const bool werr = part && ew;
+    int64_t col = werr && v < nvec ? (head + 4 * v) % encols : 0;
+    const int64_t cstep = werr ? (4 * stride) % encols : 0;
+    double acc = 0.0;
+    for (; v < nvec; v += stride) {
+        const float4 xq = xv4[v];
+        const float xs[4] = {xq.x, xq.y, xq.z, xq.w};
+        float d[4];
+        int q[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) q[j] = nfs_one<BITS>(xs[j], mu, s, y, fast, lev, d[j]);
+        const int64_t e = head + 4 * v;
+        if (ib) {
+            if (ivec) {
+                *reinterpret_cast<uint32_t*>(ib + e) =
+                    (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ib[e + j] = (uint8_t)q[j];
+            }
+        }
+        if (db) {
+            if (dvec) {
+                *reinterpret_cast<float4*>(db + e) = make_float4(d[0], d[1], d[2], d[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) db[e + j] = d[j];
+            }
+        }
+        if (part) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int64_t cj = col + j;
+                if (cj >= encols) cj = werr ? cj % encols : 0;
+                acc += nfs_err(d[j], xs[j], ew, cj);
+            }
+            col += cstep;
+            if (col >= encols) col -= encols;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 8) {  // head: lanes 0-3, tail: lanes 4-7
+        const int t = threadIdx.x;
+        const int64_t e = t < 4 ? (t < head ? (int64_t)t : -1) : (tail0 + (t - 4) < numel ? tail0 + (t - 4) : -1);
+        if (e >= 0) {
+            const float xv = xb[e];
+            float d;
+            const int q = nfs_one<BITS>(xv, mu, s, y, fast, lev, d);
+            if (ib) ib[e] = (uint8_t)q;
+            if (db) db[e] = d;
+            if (part) acc += nfs_err(d, xv, ew, werr ? e % encols : 0);
+        }
+    }
+    if (part) {
+        const double t = block_sum_f64(acc, lds);
+        if (threadIdx.x == 0) part[b * gridDim.x + blockIdx.x] = t;
+    }
+}
+
+template <int BITS>
+__global__ void nfs_dequant_kernel(const uint8_t* __restrict__ idx, const float* __restrict__ mean,
+                                   const float* __restrict__ sd, int64_t total, int64_t bs, float* __restrict__ out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+        const int64_t blk = e / bs;
+        out[e] = nfs_deq(nf_level<BITS>(idx[e] & ((1 << BITS) - 1)), sd[blk], mean[blk]);
+    }
+}
+
+struct NfsWs {  // workspace of cq_quantize_nf_std
+    double *psum, *psq, *perr, *mean64, *part;
+    float* tsum;
+    size_t bytes;
+};
+
+static NfsWs nfs_carve(void* ws, int64_t batch, int64_t nbt, int64_t nchunks) {
+    NfsWs w{};
+    char* p = reinterpret_cast<char*>(ws);
+    size_t o = 0;
+    auto take = [&](size_t n) { char* r = p ? p + o : nullptr; o = align_up(o + n, 256); return r; };
+    w.psum = reinterpret_cast<double*>(take(nchunks * 8));
+    w.psq = reinterpret_cast<double*>(take(nchunks * 8));
+    w.perr = reinterpret_cast<double*>(take(nchunks * 8));
+    w.mean64 = reinterpret_cast<double*>(take(nbt * 8));
+    w.part = reinterpret_cast<double*>(take((size_t)batch * kMaxGrid * 8));
+    w.tsum = reinterpret_cast<float*>(take(nbt * 4));
+    w.bytes = o;
+    return w;
+}
+
 }  // namespace cq
 
 using namespace cq;
@@ -547,6 +777,66 @@ int cq_dequant_nf(const uint8_t* idx, const float* scale, int64_t total, int64_t
     if (bits == 4) nf_dequant_kernel<4><<<g, 256, 0, as_stream(stream)>>>(idx, scale, total, block_size, out);
     else nf_dequant_kernel<2><<<g, 256, 0, as_stream(stream)>>>(idx, scale, total, block_size, out);
     return check_launch("cq_dequant_nf");
+}
+
+size_t cq_quantize_nf_std_workspace(int64_t batch, int64_t numel, int64_t block_size) {
+    if (batch <= 0 || block_size <= 0 || numel % block_size) return 0;
+    const BBGeom g = bb_geom(batch, numel, block_size);
+    return nfs_carve(nullptr, batch, g.nbt, g.nbt * g.nch).bytes;
+}
+
+int cq_quantize_nf_std(const float* x, int64_t batch, int64_t numel, int64_t block_size, int bits, float eps,
+                       uint8_t* idx, float* deq, float* mean, float* sd, const float* err_w, int64_t err_ncols,
+                       int64_t err_w_stride, double* err_out, void* ws, size_t ws_bytes, void* stream) {
+    CQ_REQUIRE(x && mean && sd && batch > 0 && numel > 0, "cq_quantize_nf_std: bad args");
+    CQ_REQUIRE(bits == 2 || bits == 4, "cq_quantize_nf_std: bits must be 2 (nf2) or 4 (nf4)");
+    CQ_REQUIRE(block_size >= 2, "cq_quantize_nf_std: block_size must be >= 2 (one element has no unbiased std)");
+    CQ_REQUIRE(numel % block_size == 0, "cq_quantize_nf_std: numel %% block_size != 0");
+    CQ_REQUIRE(!err_w || err_ncols > 0, "cq_quantize_nf_std: err_ncols");
+    const BBGeom g = bb_geom(batch, numel, block_size);
+    const int64_t nchunks = g.nbt * g.nch;
+    CQ_REQUIRE(nchunks <= INT32_MAX, "cq_quantize_nf_std: too many chunks for one grid");
+    if (!ws || ws_bytes < cq_quantize_nf_std_workspace(batch, numel, block_size))
+        return set_error(CQ_EWORKSPACE, "cq_quantize_nf_std: workspace too small");
+    NfsWs w = nfs_carve(ws, batch, g.nbt, nchunks);
+    hipStream_t s = as_stream(stream);
+    const bool emit = idx || deq || err_out;
+    bb_sum_kernel<<<nchunks, kCbThreads, 0, s>>>(x, g, w.psum, w.tsum);
+    if (g.nch > 1) {  // a wave per block adds the chunk partials; a lane per block would add them one by one
+        const int gv = (int)ceil_div(g.nbt, kCbThreads / 64);
+        nfs_mean_wave_kernel<<<gv, kCbThreads, 0, s>>>(g, w.psum, w.mean64, mean);
+        bb_var_kernel<<<nchunks, kCbThreads, 0, s>>>(x, g, w.mean64, w.psq);
+        nfs_std_wave_kernel<<<gv, kCbThreads, 0, s>>>(g, eps, w.psq, sd);
+    } else {
+        const int gb = (int)ceil_div(g.nbt, 256);
+        bb_mean_kernel<<<gb, 256, 0, s>>>(g, w.psum, w.tsum, w.mean64, mean);
+        bb_var_kernel<<<nchunks, kCbThreads, 0, s>>>(x, g, w.mean64, w.psq);
+        nfs_std_kernel<<<gb, 256, 0, s>>>(g, eps, w.psq, sd);
+    }
+    if (!emit) return check_launch("cq_quantize_nf_std(stats)");
+    if (block_size == numel) {
+        const int gw = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(numel, kCbThreads * 16), std::max<int64_t>(64, kMaxGrid / batch)));
+        double* pw = err_out ? w.part : nullptr;
+        if (bits == 4) nfs_whole_kernel<4><<<dim3(gw, batch), kCbThreads, 0, s>>>(x, numel, mean, sd, idx, deq, err_w, err_ncols, pw, err_w_stride);
+        else nfs_whole_kernel<2><<<dim3(gw, batch), kCbThreads, 0, s>>>(x, numel, mean, sd, idx, deq, err_w, err_ncols, pw, err_w_stride);
+        if (err_out) cb_sum_parts_kernel<<<batch, 64, 0, s>>>(w.part, gw, err_out);
+        return check_launch("cq_quantize_nf_std(whole)");
+    }
+    double* pe = err_out ? w.perr : nullptr;
+    if (bits == 4) nfs_emit_kernel<4><<<nchunks, kCbThreads, 0, s>>>(x, g, mean, sd, idx, deq, err_w, err_ncols, pe, err_w_stride);
+    else nfs_emit_kernel<2><<<nchunks, kCbThreads, 0, s>>>(x, g, mean, sd, idx, deq, err_w, err_ncols, pe, err_w_stride);
+    if (err_out) cb_sum_parts_kernel<<<batch, 64, 0, s>>>(w.perr, g.nblk_per * g.nch, err_out);
+    return check_launch("cq_quantize_nf_std");
+}
+
+int cq_dequant_nf_std(const uint8_t* idx, const float* mean, const float* sd, int64_t total, int64_t block_size,
+                      int bits, float* out, void* stream) {
+    CQ_REQUIRE(idx && mean && sd && out && total > 0 && block_size > 0, "cq_dequant_nf_std: bad args");
+    CQ_REQUIRE(bits == 2 || bits == 4, "cq_dequant_nf_std: bits must be 2 or 4");
+    const int g = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(total, 256), 8192));
+    if (bits == 4) nfs_dequant_kernel<4><<<g, 256, 0, as_stream(stream)>>>(idx, mean, sd, total, block_size, out);
+    else nfs_dequant_kernel<2><<<g, 256, 0, as_stream(stream)>>>(idx, mean, sd, total, block_size, out);
+    return check_launch("cq_dequant_nf_std");
 }
 
 size_t cq_bbint_workspace(int64_t batch, int64_t numel, int64_t block_size) {

@@ -58,8 +58,8 @@ class EngineParams:
                    iters=qp.iters, lplr_iters=qp.lplr_iters,
                    activation_aware_LR=qp.activation_aware_LR,
                    update_order=list(qp.update_order),
-                   method_Q=qp.quant_factory_Q.method.lower(),
-                   method_LR=qp.quant_factory_LR.method.lower(),
+                   method_Q=qlog.engine_method(qp.quant_factory_Q),
+                   method_LR=qlog.engine_method(qp.quant_factory_LR),
                    rand_svd=qp.rand_svd, sigma_reg=qp.sigma_reg)
 
 
@@ -356,7 +356,7 @@ class CalderaEngine:
         self.lplr_trace = None       # list -> per-LPLR-iteration errors are appended (diagnostics)
         self._s_bm = None            # split scale of the last Y Rw^T product (lplr_rhs -> lplr_L_from)
         for meth in (params.method_Q, params.method_LR):
-            if meth not in ("uniform", "nf4", "nf2", "bbint4", "bbint2"):
+            if meth not in qlog.METHODS:
                 raise NotImplementedError(f"Quantization method '{meth}' not supported yet.")
 
     @property
@@ -426,7 +426,7 @@ class CalderaEngine:
         return err
 
     def _q_update_codebook(self, st: BatchState, Ws, res_buf, wts: _Weights, Kdim):
-        """Q update with a codebook quantiser (nf4/nf2/bbint4/bbint2): res = W - L R
+        """Q update with a codebook quantiser (nf4/nf2/bbint4/bbint2/nf4_std/nf2_std): res = W - L R
         (alg.py:262) into the fp32 work buffer, then the whole-matrix quantiser
         (alg.py:245-250) with the error sum_j h_j (deq - res)^2 fused."""
         p = self.p
@@ -453,6 +453,10 @@ class CalderaEngine:
         if method in ("nf4", "nf2"):
             out = K.quantize_nf(x, numel, qlog.code_bits(method, bits), **err)
             return [(out["idx"][b].view(1, -1), out["scale"][b].view(1, 1)) for b in range(B)], out["deq"]
+        if method in ("nf4_std", "nf2_std"):  # params: the pair (mean, std)
+            out = K.quantize_nf_std(x, numel, qlog.code_bits(method, bits), **err)
+            return [(out["idx"][b].view(1, -1), (out["mean"][b].view(1, 1), out["std"][b].view(1, 1)))
+                    for b in range(B)], out["deq"]
         cb = qlog.code_bits(method, bits)
         if numel % (8 // cb):
             raise RuntimeError(f"{method}: {numel} elements do not pack {8 // cb} codes per byte")

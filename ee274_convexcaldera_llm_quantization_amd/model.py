@@ -238,7 +238,8 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
       instead of receiving the dense `out`; the gate and the counters are unchanged.  Needs
       uniform 2- or 4-bit Q, or nf4 / nf2 Q (taken from `quant_params.quant_factory_Q.method`:
       the layer then holds the level indices); a bbint Q raises ValueError before anything is
-      decomposed (per-block affine codes plus an outlier list have no packed form); not with `hadamard` (the layer would need the transforms around
+      decomposed (per-block affine codes plus an outlier list have no packed form), and so does a
+      standardised nf4 / nf2 Q (a `quantization_stable_nf4` factory: its mean term); not with `hadamard` (the layer would need the transforms around
       it) and not with `scale_W=True`: like main.py, the gate and the dense write-back use
       Q + L R of the scaled W without its global scale, while a packed layer applies
       gs (Q + L R), so the two would be different models and the gate would judge a weight
@@ -297,6 +298,11 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
         # the Q quantiser must have a packed form (uniform, nf4, nf2: bbint raises), before
         # anything is decomposed
         from .linear import q_method_format
+        if (getattr(getattr(qp, "quant_factory_Q", None), "nf_variant", None) == "standardized"
+                and q_method in ("nf4", "nf2")):
+            raise ValueError(f"apply_caldera_quantization: packed=True: the standardised {q_method} Q "
+                             "(quantization_stable_nf4) has no packed form: Q = level * std + mean carries a "
+                             "mean term that no packed kernel applies")
         q_method_format(q_method, getattr(qp, "Q_bits", None))
     say = log or (lambda *a: None)
     jobs, rep = select_layers(model, hessians, selection, say)

@@ -114,6 +114,29 @@ int cq_dequant_nf(const uint8_t* idx, const float* scale, int64_t total, int64_t
                   float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Standardised NF4 / NF2.  Replaces RCR/src/caldera/utils/quantization_stable_nf4.py:146-230 (the
+ * nf4 / nf2 branches of quantize_block / dequantize_block).  x: batch x numel fp32 in blocks of
+ * block_size; per block, with the statistics of the bbint entries:
+ *   mean = fp32 mean (block_size <= 256: torch's CPU summation order; longer: the fp64 sum / n
+ *          rounded once)
+ *   std  = max(f32(sqrt(sum (x - mean64)^2 / (block_size - 1))), eps)   (fp64 sum, NaN-propagating)
+ *   idx  = #{t : (x - mean) / std > thr_t}   (two fp32 operations, IEEE division; uint8)
+ *   deq  = f32(level[idx] * std) + mean      (two roundings)
+ * mean, std [batch * numel / block_size] are required; idx / deq optional; err_out[b] = sum
+ * err_w[j % err_ncols] (deq - x)^2, the difference squared in fp32 and summed in fp64 in a fixed
+ * order, if non-NULL (err_w_stride as for cq_quantize_nf).  Deterministic, stream-ordered, no
+ * allocation, no host synchronisation.
+ * Deviation: block_size = 1 has no unbiased std (the reference returns NaN there): CQ_EINVAL.
+ * Non-finite inputs: results unspecified. */
+size_t cq_quantize_nf_std_workspace(int64_t batch, int64_t numel, int64_t block_size);
+int cq_quantize_nf_std(const float* x, int64_t batch, int64_t numel, int64_t block_size, int bits, float eps,
+                       uint8_t* idx, float* deq, float* mean, float* std, const float* err_w, int64_t err_ncols,
+                       int64_t err_w_stride, double* err_out, void* ws, size_t ws_bytes, void* stream);
+/* out[e] = f32(level[idx[e]] * std[e / block_size]) + mean[e / block_size] */
+int cq_dequant_nf_std(const uint8_t* idx, const float* mean, const float* std, int64_t total,
+                      int64_t block_size, int bits, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * bbint4 / bbint2 (bitsandbytes-style affine codes with 6-sigma outliers).  Replaces
  * quantization.py:107-154 (_quantize_bbint4), :175-222 (_quantize_bbint2) and their dequant
  * :157-172 / :224-243.  Two calls with the same workspace (the outlier list is variable
