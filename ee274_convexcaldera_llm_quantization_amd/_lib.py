@@ -202,6 +202,16 @@ class HadamardSignedGluArgs(ctypes.Structure):
     _fields_ = [("a", HadamardGluArgs), ("sign_g", c_vp), ("sign_u", c_vp)]
 
 
+class HadamardColsArgs(ctypes.Structure):
+    """cq_hadamard_cols_args: the column-wise transform of a row-major fp32 matrix."""
+    _fields_ = [
+        ("x", c_vp), ("ldx", c_i64),
+        ("y", c_vp), ("ldy", c_i64),
+        ("cols", c_i64), ("n_in", ctypes.c_int32), ("n_out", ctypes.c_int32), ("P", ctypes.c_int32),
+        ("sign_in", c_vp), ("sign_out", c_vp),
+    ]
+
+
 _SIGS = {
     "cq_abi_version": (c_int, []),
     "cq_last_error": (ctypes.c_char_p, []),
@@ -307,6 +317,8 @@ _SIGS = {
     "cq_hadamard_signed_rows": (c_int, [ctypes.POINTER(HadamardSignedArgs), c_vp]),
     "cq_hadamard_signed_group_rows": (c_int, [ctypes.POINTER(HadamardSignedGroupArgs), c_vp]),
     "cq_hadamard_signed_glu_rows": (c_int, [ctypes.POINTER(HadamardSignedGluArgs), c_vp]),
+    "cq_hadamard_cols_workspace": (c_size, [ctypes.POINTER(HadamardColsArgs)]),
+    "cq_hadamard_cols": (c_int, [ctypes.POINTER(HadamardColsArgs), c_vp, c_size, c_vp]),
     # masked entries: the unmasked signature with `active` ([batch] int32 or NULL) added
     "cq_gemm_x3_skip": (c_int, [ctypes.POINTER(X3Args), c_vp]),
     "cq_gram_f64_masked": (c_int, [c_i64, c_i64, c_i64, c_i64, c_vp, c_int, c_i64, c_i64, c_vp, c_int, c_i64,
@@ -2048,3 +2060,42 @@ def hadamard_signed_glu_rows(g, u, h, *, n_in, n_out, P, bias_g=None, bias_u=Non
                                                    act=act, sign_g=sign_g, sign_u=sign_u),
                   (g, u, h, bias_g, bias_u, sign_g, sign_u), built_first=True)
     return h
+
+
+# ---------------------------------------------------------------------------- column-wise Hadamard transform
+def hadamard_cols_args(x, y, *, n_in, n_out, P, sign_in=None, sign_out=None) -> HadamardColsArgs:
+    """cq_hadamard_cols_args for x (n_in, cols) and y (n_out, cols), fp32 and possibly views with a row stride
+    (unit column stride); sign_in (>= n_in,) / sign_out (>= n_out,): contiguous int8 vectors on x's device, or
+    None.  An entry flips its row iff it is negative."""
+    who = "cq_hadamard_cols"
+    a = HadamardColsArgs()
+    for name, t, rows in (("x", x, n_in), ("y", y, n_out)):
+        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError(f"{who}: {name} must be a matrix with unit column stride")
+        if t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name} must be fp32, got {t.dtype}")
+        if t.shape[0] != rows or t.shape[1] != x.shape[1]:
+            raise ValueError(f"{who}: {name} {tuple(t.shape)} is not ({rows}, {x.shape[1]})")
+        setattr(a, name, t.data_ptr())
+        setattr(a, "ld" + name, t.stride(0) if rows > 1 else max(t.stride(0), t.shape[1]))
+    P = int(P)
+    if not 1 <= P <= HADAMARD_MAX_N or P & (P - 1):
+        raise ValueError(f"{who}: P = {P} is not a power of two in [1, {HADAMARD_MAX_N}]")
+    if not (1 <= n_in <= P and 1 <= n_out <= P):
+        raise ValueError(f"{who}: n_in = {n_in} / n_out = {n_out} do not fit P = {P}")
+    a.cols, a.n_in, a.n_out, a.P = x.shape[1], n_in, n_out, P
+    _hadamard_sign(a, who, "sign_in", sign_in, n_in, x.device)
+    _hadamard_sign(a, who, "sign_out", sign_out, n_out, x.device)
+    return a
+
+
+def hadamard_cols(x, y, *, n_in, n_out, P, sign_in=None, sign_out=None):
+    """y[:n_out] = sign_out * (H_P pad(sign_in * x[:n_in]))[:n_out] / sqrt(P) down every column
+    (cq_hadamard_cols): x (n_in, cols) and y (n_out, cols) fp32, rows n_in .. P of x count as zero.  P above 256
+    takes a cached scratch buffer of P x cols fp32.  x and y must not overlap.  No host synchronisation."""
+    a = hadamard_cols_args(x, y, n_in=n_in, n_out=n_out, P=P, sign_in=sign_in, sign_out=sign_out)
+    _require_hip(x, y, sign_in, sign_out)
+    lib = load()
+    ws = scratch.get_flat("hadamard_cols.ws", lib.cq_hadamard_cols_workspace(ctypes.byref(a)), torch.uint8, x.device)
+    _check(lib.cq_hadamard_cols(ctypes.byref(a), _p(ws), ws.numel(), _stream(x.device)), "cq_hadamard_cols")
+    return y

@@ -13,10 +13,12 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libcaldera_hip.so")
 SOURCES = ["cq_quant.hip", "cq_gemm.hip", "cq_small.hip", "cq_x3.hip", "cq_qtile.hip", "cq_split.hip", "cq_qupdate.hip",
            "cq_codebook.hip", "cq_calib.hip", "cq_bjacobi.hip", "cq_sgram.hip", "cq_linear.hip",
-           "cq_linear_bwd.hip", "cq_linear_dequant.hip", "cq_hadamard.hip"]
+           "cq_linear_bwd.hip", "cq_linear_dequant.hip", "cq_hadamard.hip", "cq_hadamard_cols.hip"]
 # per-source extra flags: the row-panel Q update keeps its per-element epilogue in scalar fp32
-# (packed fp32 VALU beside MFMAs costs more issue cycles than the scalar pair it replaces)
-EXTRA = {"cq_qupdate.hip": ["-fno-slp-vectorize"]}
+# (packed fp32 VALU beside MFMAs costs more issue cycles than the scalar pair it replaces); the column
+# transform's butterflies are compiled without the packed fp32 instructions altogether
+EXTRA = {"cq_qupdate.hip": ["-fno-slp-vectorize"],
+         "cq_hadamard_cols.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-shared", "-std=c++17",
          # bit-exact quantiser: no FMA contraction, IEEE-correct fp32 division/sqrt
          "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]

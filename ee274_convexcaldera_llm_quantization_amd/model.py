@@ -115,7 +115,7 @@ def _next_pow2(n: int) -> int:
     return 1 << (n - 1).bit_length()
 
 
-def hadamard_transform(W: torch.Tensor, inverse: bool = False, original_shape=None, signs=None):
+def hadamard_transform(W: torch.Tensor, inverse: bool = False, original_shape=None, signs=None, kernels: bool = False):
     """main.py:108-133 on the device: forward pads W to powers of two and returns
     (H1 W H2, (rows, cols)); inverse returns (H1 W H2)[:rows, :cols] (H symmetric and
     orthogonal).  Two fp32 HIP GEMMs.
@@ -123,10 +123,16 @@ def hadamard_transform(W: torch.Tensor, inverse: bool = False, original_shape=No
     signs = (su, sv), +-1 vectors of at least rows resp. cols entries (`linear.hadamard_sign_vector`): the
     randomised transform H1 diag(su) pad(W) diag(sv) H2.  Forward flips W's rows and columns in the padded
     matrix before the two GEMMs (the pad is zero), inverse flips the rows and columns of the cut result
-    after them; every flip is a multiplication by +-1, which is exact."""
+    after them; every flip is a multiplication by +-1, which is exact.
+
+    kernels=True: the same transform by the FWHT kernels instead of the GEMMs (`_hadamard_transform_kernels`):
+    equal up to fp32 rounding, not to the bit.  Needs a device tensor (RuntimeError for a CPU one: there is no
+    CPU path) and padded dimensions up to `_lib.HADAMARD_MAX_N`."""
     rows, cols = (W.shape if not inverse else original_shape)
     pr, pc = _next_pow2(rows), _next_pow2(cols)
     dev = W.device
+    if kernels:
+        return _hadamard_transform_kernels(W, inverse, rows, cols, pr, pc, signs)
     H1, H2 = normalized_hadamard(pr, dev), normalized_hadamard(pc, dev)
     flip = None
     if signs is not None:
@@ -143,6 +149,44 @@ def hadamard_transform(W: torch.Tensor, inverse: bool = False, original_shape=No
     out = K.gemm(T, H2, C=torch.empty((pr, pc), dtype=torch.float32, device=dev))
     if inverse:
         return out[:rows, :cols] if flip is None else out[:rows, :cols] * flip
+    return out, (rows, cols)
+
+
+def _hadamard_transform_kernels(W, inverse, rows, cols, pr, pc, signs):
+    """`hadamard_transform` by cq_hadamard_rows / cq_hadamard_signed_rows along the rows and cq_hadamard_cols
+    down the columns.  Forward: the rows entry reads the m real rows of W in W's own dtype and pads them to pc
+    (sv on the way in), the column entry pads the (m, pc) fp32 intermediate to pr rows (su on the way in).
+    Inverse: the column entry cuts to `rows` (su on the way out), the rows entry to `cols` (sv on the way out).
+    The zero pad is never stored: no Hadamard matrix, no padded copy of W and no flip matrix is allocated.
+    int8 sign vectors that already live on W's device are used as they are (no copy)."""
+    if not W.is_cuda:
+        raise RuntimeError("hadamard_transform(kernels=True) needs a HIP device tensor (no CPU path)")
+    dev = W.device
+    su = sv = None
+    if signs is not None:
+        su, sv = signs
+        if su.dim() != 1 or sv.dim() != 1 or su.numel() < rows or sv.numel() < cols:
+            raise ValueError(f"hadamard_transform: signs {tuple(su.shape)}, {tuple(sv.shape)} do not cover {(rows, cols)}")
+        su, sv = (s.to(dev, torch.int8).contiguous() for s in (su, sv))
+
+    def along_rows(x, y, **kw):
+        if signs is None:
+            return K.hadamard_rows(x, y, n_in=x.shape[1], n_out=y.shape[1], P=pc)
+        return K.hadamard_signed_rows(x, y, n_in=x.shape[1], n_out=y.shape[1], P=pc, **kw)
+
+    if W.dtype not in (torch.float16, torch.bfloat16, torch.float32) or (inverse and W.dtype != torch.float32):
+        W = W.float()
+    if W.dim() != 2 or (W.shape[1] > 1 and W.stride(1) != 1):
+        W = W.contiguous()
+    if inverse:
+        if tuple(W.shape) != (pr, pc):
+            raise ValueError(f"hadamard_transform: inverse of {tuple(W.shape)}, expected the padded {(pr, pc)}")
+        T = K.hadamard_cols(W, torch.empty((rows, pc), dtype=torch.float32, device=dev), n_in=pr, n_out=rows, P=pr,
+                            sign_out=su)
+        return along_rows(T, torch.empty((rows, cols), dtype=torch.float32, device=dev), sign_out=sv)
+    T = along_rows(W, torch.empty((rows, pc), dtype=torch.float32, device=dev), sign_in=sv)
+    out = K.hadamard_cols(T, torch.empty((pr, pc), dtype=torch.float32, device=dev), n_in=rows, n_out=pr, P=pr,
+                          sign_in=su)
     return out, (rows, cols)
 
 
@@ -219,7 +263,8 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                                log: Callable | None = None, hadamard_gate: bool = False,
                                packed: bool = False, packed_factors: bool = False,
                                packed_hadamard: bool = False,
-                               hadamard_signs: int | None = None) -> QuantizationReport:
+                               hadamard_signs: int | None = None,
+                               hadamard_kernels: bool = False) -> QuantizationReport:
     """main.py:135-251 on the MI355X engine.
 
     hessians: {module name: diagonal (n,) or dense (n, n)} — `Hall` (a missing name raises
@@ -265,6 +310,11 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
       gate are those of the signed transform; the Hessian is not transformed (as without signs).  Needs
       packed_hadamard=True: otherwise, or for a value outside the range, ValueError before anything is
       decomposed.  None, the default: the plain transform, as before.
+    hadamard_kernels: with hadamard=True or packed_hadamard=True (ValueError before anything is decomposed
+      otherwise), form H1 pad(W) H2 and its inverse with the FWHT kernels (`hadamard_transform(kernels=True)`)
+      instead of two dense fp32 GEMMs against Hadamard matrices: the same transform up to fp32 rounding,
+      with and without `hadamard_signs`.  A padded dimension above `_lib.HADAMARD_MAX_N` raises ValueError,
+      for hadamard=True as well.  False, the default: the GEMMs, as before.
     Returns the QuantizationReport (counters + per-layer outcomes)."""
     qp = quant_params if quant_params is not None else driver_params()
     if packed_hadamard and not packed:
@@ -277,6 +327,9 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
             hadamard_sign_seeds(hadamard_signs, "", 1)
         except ValueError as e:
             raise ValueError(f"apply_caldera_quantization: {e}") from None
+    if hadamard_kernels and not (hadamard or packed_hadamard):
+        raise ValueError("apply_caldera_quantization: hadamard_kernels=True needs hadamard=True or "
+                         "packed_hadamard=True (there is no transform to run otherwise)")
     if packed and hadamard:
         raise ValueError("apply_caldera_quantization: packed=True cannot be combined with hadamard=True (the dense "
                          "write-back of main.py); packed_hadamard=True runs the Hadamard branch packed")
@@ -307,12 +360,15 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
     say = log or (lambda *a: None)
     jobs, rep = select_layers(model, hessians, selection, say)
     transform = hadamard or packed_hadamard  # decompose H1 pad(W) H2
-    if packed_hadamard:
+    if packed_hadamard or hadamard_kernels:
         for name, module, _ in jobs:
             pshape = tuple(_next_pow2(d) for d in module.weight.shape)
             if max(pshape) > K.HADAMARD_MAX_N:
-                raise ValueError(f"apply_caldera_quantization: packed_hadamard=True: {name}: padded shape {pshape} "
+                raise ValueError(f"apply_caldera_quantization: {'packed_hadamard' if packed_hadamard else 'hadamard_kernels'}"
+                                 f"=True: {name}: padded shape {pshape} "
                                  f"exceeds {K.HADAMARD_MAX_N} (cq_hadamard_rows' largest transform)")
+    kernels = {"kernels": True} if hadamard_kernels else {}  # nothing new is passed without the switch
+    dev_signs = {}  # name -> (su, sv) on the device, with the switch: copied once for the transform and its inverse
     # batches: same shape; every layer keeps its own Hessian (a list of per-matrix H, or one
     # shared H / None when the whole batch has the same object)
     groups: dict = {}
@@ -334,7 +390,10 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                             raise ValueError(f"{name}: Hadamard padding changes n ({W.shape[1]}) but H is n x n")
                         if hadamard_signs is not None:
                             seeds[name] = hadamard_sign_seeds(hadamard_signs, name, W.shape[1])
-                        Wt, shp = hadamard_transform(W.to(device), signs=_sign_vectors(seeds.get(name), W.shape))
+                        signs = _sign_vectors(seeds.get(name), W.shape)
+                        if hadamard_kernels and signs is not None:
+                            signs = dev_signs[name] = tuple(s.to(device) for s in signs)
+                        Wt, shp = hadamard_transform(W.to(device), signs=signs, **kernels)
                         Ws.append(Wt)
                         shapes.append(shp)
                     else:
@@ -352,8 +411,9 @@ def apply_caldera_quantization(model: torch.nn.Module, hessians=None, quant_para
                 dev = W.device if W.device.type == "cuda" else torch.device(device)
                 out = _reconstruct(dec, dev)
                 if transform:
-                    out = hadamard_transform(out, inverse=True, original_shape=shapes[i],
-                                             signs=_sign_vectors(seeds.get(name), shapes[i])).contiguous()
+                    signs = dev_signs.get(name) or _sign_vectors(seeds.get(name), shapes[i])
+                    out = hadamard_transform(out, inverse=True, original_shape=shapes[i], signs=signs,
+                                             **kernels).contiguous()
                 err = _rel_error(W.to(dev), out)
                 if hadamard and not hadamard_gate:
                     # main.py:221-240: the Hadamard branch always writes the recovered

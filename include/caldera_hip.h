@@ -1132,6 +1132,42 @@ typedef struct cq_hadamard_signed_glu_args {
 
 int cq_hadamard_signed_glu_rows(const cq_hadamard_signed_glu_args* a, void* stream);
 
+/* Column-wise transform (ABI 5, additive): the same normalised Sylvester-Hadamard transform down the
+ * columns of a row-major fp32 matrix, with optional sign vectors.  With cq_hadamard_rows it forms
+ * H1 diag(su) pad(W) diag(sv) H2 of a weight (and its inverse) without a Hadamard matrix:
+ *
+ *   y[i, j] = s_out[i] * c * sum_{k < n_in} (-1)^popcount(i & k) s_in[k] x[k, j]    i < n_out, j < cols
+ *   c = (float)(1.0 / sqrt((double)P)),   P = 2^p,   1 <= P <= CQ_HADAMARD_MAX_N
+ *
+ * Contract:
+ *   - x (n_in x cols) and y (n_out x cols) are fp32, row-major with leading dimensions ldx, ldy >= cols.
+ *     Rows n_in .. P of x count as zero and are never read; rows of y at or past n_out and whatever lies
+ *     between cols and ldx / ldy are neither read nor written;
+ *   - sign_in (n_in int8) and sign_out (n_out int8) live on the device; either may be NULL (no flips).
+ *     An element is negated iff its byte is negative (cq_hadamard_signed_rows' rule); both flips are exact;
+ *   - every butterfly runs in fp32, c is applied once to the finished sum.  No atomics; a column's stage
+ *     order is a function of P alone: its bits do not depend on its index, on cols, on the leading
+ *     dimensions or on the alignment (a cut or unaligned chunk of four columns loads the same values one
+ *     by one);
+ *   - P <= 256 is one pass and needs no workspace; a larger P is two passes through a workspace of
+ *     P x cols fp32, cq_hadamard_cols_workspace bytes (0 for one pass, and for arguments that are refused);
+ *   - stream-ordered, no allocation, no host synchronisation (graph-capturable).  x, y and the workspace
+ *     must not overlap one another.
+ * CQ_EINVAL (before any HIP call): null args; P not a power of two or out of range; n_in or n_out outside
+ * [1, P]; cols < 0 or above 2^35; ldx or ldy below cols; x, y or the workspace not aligned to fp32; with
+ * cols > 0 a null x or y, x overlapping y, or the needed bytes of the workspace overlapping either.  CQ_EWORKSPACE: ws_bytes below cq_hadamard_cols_workspace.  cols == 0
+ * returns 0 without a launch. */
+typedef struct cq_hadamard_cols_args {
+    const float* x; int64_t ldx;               /* n_in x cols fp32  */
+    float* y;       int64_t ldy;               /* n_out x cols fp32 */
+    int64_t cols; int32_t n_in, n_out, P;      /* P = 2^p, 1 <= P <= CQ_HADAMARD_MAX_N */
+    const int8_t* sign_in;                     /* n_in int8 or NULL: row k of x is negated iff sign_in[k] < 0 */
+    const int8_t* sign_out;                    /* n_out int8 or NULL: row i of y is negated iff sign_out[i] < 0 */
+} cq_hadamard_cols_args;
+
+size_t cq_hadamard_cols_workspace(const cq_hadamard_cols_args* a);
+int cq_hadamard_cols(const cq_hadamard_cols_args* a, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
